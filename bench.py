@@ -12,7 +12,14 @@ around every launch of the dominant kernel family (the MFMA implicit-GEMM conv) 
 The default workload is BASELINE.json's metric (configs[1]: training images/s).  Two more workloads make the other
 single-GPU configurations driver-measurable with the same JSON contract:
     python bench.py --workload kmeans   # configs[3]: Lloyd iterations over 1M x 768 synthetic DINO embeddings, K = 300 (s/iter)
-    python bench.py --workload infer    # configs[4]: u2seg_eval_800 panoptic inference, batch 32 (img/s)"""
+    python bench.py --workload infer    # configs[4]: u2seg_eval_800 panoptic inference, batch 32 (img/s)
+
+`--dump-outputs DIR` writes outputs as DIR/<name>.npy after the timed region, so that two builds can be compared output for output
+on identical inputs.  Inference writes every image's output fields of the last timed step; k-means, whose last timed iteration
+starts from the initial centroids, writes its labels and centroids.  The production training step does not repeat from run to
+run (fp32-atomic BN statistics move proposals across NMS / sampling decisions), so training writes one untimed step from the
+seeded initial state with fixed-order BN statistics as fixed_order_*: its losses, a sample of the updated parameters, and the
+statistics the production conv epilogue accumulates for the same conv outputs."""
 import argparse
 import json
 import os
@@ -326,6 +333,131 @@ def _per_step_stats(marks, sampled):
             "note": "the last %d step(s) run in one stream with HIP events around every conv launch (roofline sample)" % sampled}
 
 
+DUMP_LIMIT_BYTES = 48 * 10 ** 6   # --dump-outputs: the whole directory (its limit is 64 MB)
+DUMP_WHOLE_ELEMS = 1 << 16       # arrays up to this many elements are written whole; the larger ones share the rest as samples
+DUMP_HEADER_BYTES = 256          # room for one .npy header
+
+
+SEGMENT_FIELDS = ("area", "category_id", "id", "instance_id", "isthing", "score")   # of a panoptic segments_info entry
+
+
+def segments_table(info):
+    """A panoptic segments_info list as a float64 table: a row per segment, SEGMENT_FIELDS as columns, NaN where a segment has
+    no such field (stuff segments have no score / instance_id, thing segments no area); an empty list gives a (0, 6) table."""
+    for d in info:
+        assert set(d) <= set(SEGMENT_FIELDS), sorted(d)
+    rows = [[float(d[k]) if k in d else float("nan") for k in SEGMENT_FIELDS] for d in info]
+    return torch.tensor(rows, dtype=torch.float64).reshape(len(rows), len(SEGMENT_FIELDS))
+
+
+def output_arrays(obj, name, out):
+    """Flattens what a step returned into {name: tensor}: tensors, Boxes / masks (their .tensor), Instances (one entry per
+    field), dicts, lists and tuples (entry i as name_i) and numbers.  Strings and None are left out."""
+    if isinstance(obj, torch.Tensor):
+        out[name] = obj.detach()
+    elif isinstance(getattr(obj, "tensor", None), torch.Tensor):
+        out[name] = obj.tensor.detach()
+    elif hasattr(obj, "get_fields"):
+        for k in obj.get_fields():
+            output_arrays(getattr(obj, k), "%s_%s" % (name, k), out)
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            output_arrays(v, "%s_%s" % (name, k), out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            output_arrays(v, "%s_%d" % (name, i), out)
+    elif isinstance(obj, (bool, int, float)):
+        out[name] = torch.tensor(float(obj), dtype=torch.float64)
+
+
+def dump_outputs(dirname, arrays):
+    """Writes {name: tensor} as dirname/<name>.npy: floating point as float32 (float64 stays float64), integers and booleans as
+    float64.  Arrays of up to DUMP_WHOLE_ELEMS elements are written whole, in their shape; each larger one gets an equal share
+    of what is left of DUMP_LIMIT_BYTES and, when it does not fit, is written as a flat sample at sorted indices drawn from a
+    generator seeded by its name (the same name and size give the same indices in every run), with its original shape as
+    dirname/<name>_shape.npy.  Returns (bytes, sampled names)."""
+    import zlib
+
+    import numpy as np
+
+    def target(t):
+        return torch.float64 if t.dtype == torch.float64 or not t.dtype.is_floating_point else torch.float32
+
+    def width(t):
+        return 8 if target(t) == torch.float64 else 4
+
+    os.makedirs(dirname, exist_ok=True)
+    large = [k for k, t in arrays.items() if t.numel() > DUMP_WHOLE_ELEMS]
+    left = DUMP_LIMIT_BYTES - sum(t.numel() * width(t) + DUMP_HEADER_BYTES for k, t in arrays.items() if k not in large)
+    share = left // max(1, len(large)) - 2 * DUMP_HEADER_BYTES - 8 * 8   # (a sampled array's shape file: header + <= 8 dims)
+    if large and share < 1024:
+        raise RuntimeError("--dump-outputs: %d arrays do not fit in %d bytes" % (len(arrays), DUMP_LIMIT_BYTES))
+    total, sampled = 0, []
+    for k, t in arrays.items():
+        n = share // width(t)
+        if k in large and t.numel() > n:
+            g = torch.Generator().manual_seed(zlib.crc32(k.encode()))
+            idx = torch.randint(0, t.numel(), (n,), generator=g).sort().values
+            shape_path = os.path.join(dirname, k + "_shape.npy")   # the sample is flat: its array's shape beside it
+            np.save(shape_path, np.array(t.shape, dtype=np.float64))
+            total += os.path.getsize(shape_path)
+            t = t.reshape(-1)[idx.to(t.device)]
+            sampled.append(k)
+        path = os.path.join(dirname, k + ".npy")
+        np.save(path, t.to(target(t)).cpu().numpy())
+        total += os.path.getsize(path)
+    assert total <= DUMP_LIMIT_BYTES, total
+    return total, sampled
+
+
+def fixed_order_step(trainer, model, opt, start, batch):
+    """One training step from the state `start` (flat parameter and momentum arenas, named buffers, generator state) with the BN
+    statistics taken by the fixed-order reduction; returns {name: tensor}: its losses, the updated parameter arena and, as
+    epilogue_stats, the [sum | sum of squares] rows that the production conv epilogue accumulates for the same conv outputs
+    (each conv forward of the step launched once more into scratch buffers with the epilogue's statistics on)."""
+    from u2seg_amd import _hip
+    from u2seg_amd.layers import functional as Fn
+
+    with torch.no_grad():
+        opt.flat_param.copy_(start["param"])
+        opt.flat_mom.copy_(start["mom"])
+        for k, b in model.named_buffers():
+            if k in start["buffers"]:
+                b.copy_(start["buffers"][k])
+    opt.refresh_layouts()   # the kernels' cached weight layouts, as after an optimizer step
+    torch.cuda.set_rng_state(start["rng"], opt.flat_param.device)
+
+    epilogue, last = [], {}
+    call, fixed_stats = _hip.call, Fn._fixed_order_stats
+
+    def recording_call(name, *args):
+        if name == "u2_conv_igemm":
+            last["args"] = args
+        return call(name, *args)
+
+    def with_epilogue(out, n):
+        args = last.pop("args", None)
+        # (in, wt, out, bias, stats, ...): the same launch into a scratch output with a zeroed statistics buffer; an accumulating
+        # launch (argument 21) reads its output and is not repeated
+        if args is not None and args[2] is out and args[4] is None and args[21] == 0:
+            st = torch.zeros(2 * n + 1, dtype=torch.float32, device=out.device)
+            call("u2_conv_igemm", args[0], args[1], torch.empty_like(out), args[3], st, *args[5:])
+            epilogue.append(st[: 2 * n])
+        return fixed_stats(out, n)
+
+    _hip.call, Fn._fixed_order_stats = recording_call, with_epilogue
+    Fn.set_deterministic_stats(True)
+    try:
+        losses = trainer.run_step(batch)
+    finally:
+        Fn.set_deterministic_stats(False)
+        _hip.call, Fn._fixed_order_stats = call, fixed_stats
+    arrays = {"fixed_order_" + k: v.detach() for k, v in losses.items()}
+    arrays["fixed_order_parameters"] = opt.flat_param
+    arrays["fixed_order_epilogue_stats"] = torch.cat(epilogue)
+    return arrays
+
+
 def cpu_baselines_parallel(workloads):
     """The oracle samples of several workloads at once, one child process each (32 threads each, GPUs hidden)."""
     import concurrent.futures as cf
@@ -374,6 +506,10 @@ def main():
                          "for the rocprofv3 summary that the per-kernel durations of the roofline object are checked against")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="internal: time the CPU oracle and print its JSON object")
     ap.add_argument("--per-layer", action="store_true", help="debug: print the conv launches grouped by shape")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the workload's last timed step returned as DIR/<name>.npy (rank 0; "
+                         "float32 / float64, at most 64 MB in all, fixed seeded samples of the larger arrays; training: one "
+                         "untimed step from the seeded initial state with fixed-order BN statistics)")
     args = ap.parse_args()
     if args.cpu_baseline_only:
         res = cpu_baseline_worker(args.workload)
@@ -420,6 +556,13 @@ def main():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
+
+    def dump(dirname, arrays):
+        if dirname is None or rank != 0:
+            return
+        nbytes, sampled = dump_outputs(dirname, arrays)
+        print("bench.py: wrote %d arrays (%.1f MB) to %s; sampled: %s" % (len(arrays), nbytes / 2 ** 20, dirname,
+                                                                         ", ".join(sampled) or "none"), file=sys.stderr)
 
     def timed(step_fn, steps, warmup):
         """W untimed steps, then exactly K timed ones between barriers; MAX over ranks.  Only the last step(s) carry the
@@ -487,7 +630,7 @@ def main():
             dt = float(t[0])
         return dt, sampled
 
-    def run_train(steps, warmup):
+    def run_train(steps, warmup, dump_dir=None):
         from u2seg_amd.config import get_cfg
         from u2seg_amd.data import make_synthetic_batch
         from u2seg_amd.engine import SimpleTrainer
@@ -509,8 +652,21 @@ def main():
         batches = [make_synthetic_batch(batch, start_index=(rank * nb + i) * batch, height=args.height, width=args.width,
                                         device=dev) for i in range(nb)]
         torch.manual_seed(1000 + rank)  # per-rank sampling randomness
+        # --dump-outputs: the production step does not repeat from run to run, even from identical weights: the conv epilogues'
+        # BN column statistics are fp32 atomics, and a last-bit difference moves proposals across NMS / sampling decisions (two
+        # runs of the same step: box losses 12-16 % apart).  So the timed region stays the production path, and after it one
+        # untimed step from the seeded initial state (weights, momentum, BN buffers, generator state) normalises with the
+        # fixed-order statistics (functional.set_deterministic_stats) and is dumped as fixed_order_*.  The production epilogue
+        # still runs in that step: every conv forward is launched once more into scratch buffers with the epilogue's statistics
+        # on, and those statistics (identical conv outputs, so last-bit differences only) are dumped as well.
+        start = None
+        if dump_dir is not None:
+            start = {"param": opt.flat_param.clone(), "mom": opt.flat_mom.clone(),
+                     "buffers": {k: b.clone() for k, b in model.named_buffers()}, "rng": torch.cuda.get_rng_state(dev)}
         dt, sampled = timed(lambda i: trainer.run_step(batches[i % nb]), steps, warmup)
         total = trainer.check_finite()
+        if dump_dir is not None:
+            dump(dump_dir, fixed_order_step(trainer, model, opt, start, batches[(warmup + steps - 1) % nb]))
         imgs_per_s = batch * world * steps / dt
         out.update({"metric": "training images/sec (whole node) u2seg_R50_800 @ 800x1333", "value": imgs_per_s, "unit": "img/s",
                     "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "dtype": "bf16",
@@ -524,7 +680,7 @@ def main():
                 per_layer_report(timer, sampled)
         return out
 
-    def run_infer(steps, warmup):
+    def run_infer(steps, warmup, dump_dir=None):
         from u2seg_amd.config import get_cfg
         from u2seg_amd.data import make_synthetic_batch
         from u2seg_amd.modeling import build_model
@@ -546,6 +702,14 @@ def main():
                 res["out"] = model(data)
 
         dt, sampled = timed(step, steps, warmup)
+        arrays = {}
+        for i, r in enumerate(res["out"]):
+            r = dict(r)
+            seg, info = r.pop("panoptic_seg")
+            output_arrays(r, "image%02d" % i, arrays)
+            arrays["image%02d_panoptic_seg" % i] = seg
+            arrays["image%02d_segments_info" % i] = segments_table(info)
+        dump(dump_dir, arrays)
         imgs_per_s = batch * world * steps / dt
         out.update({"metric": "panoptic inference images/sec (whole node) u2seg_eval_800 @ 800x1333", "value": imgs_per_s,
                     "unit": "img/s", "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -562,7 +726,7 @@ def main():
                 per_layer_report(timer, sampled)
         return out
 
-    def run_kmeans(steps, warmup, data_kind, k=KMEANS_K):
+    def run_kmeans(steps, warmup, data_kind, k=KMEANS_K, dump_dir=None):
         from u2seg_amd.cluster import kmeans as KM
 
         out = {}
@@ -583,9 +747,15 @@ def main():
                 dist.broadcast(state["c"], 0)
         rechecks = []
 
+        # --dump-outputs: the last timed iteration starts from the initial centroids, so that what it computes does not depend on
+        # the earlier iterations (their M steps sum with fp32 atomics; a last-bit difference can move a point across a near-tie)
+        c0 = state["c"].clone() if dump_dir is not None else None
+
         def step(i):
-            lab = KM.assign(x, state["c"])
-            state["c"], _ = KM.update_sharded(x, lab, k) if world > 1 else KM.update(x, lab, k)
+            if c0 is not None and i == warmup + steps - 1:
+                state["c"] = c0.clone()
+            state["labels"] = KM.assign(x, state["c"])
+            state["c"], _ = KM.update_sharded(x, state["labels"], k) if world > 1 else KM.update(x, state["labels"], k)
 
         # once per run of kmeans(), not per iteration: the 16-bit shadow of x the first screening pass streams (timed on its own here;
         # the reference's niter is 100 - nn_utils.py:382 - so it adds a hundredth of this to an iteration)
@@ -596,6 +766,7 @@ def main():
         torch.cuda.synchronize()
         prepare_ms = e0.elapsed_time(e1) if made is not None else None
         dt, sampled = timed(step, steps, warmup)
+        dump(dump_dir, {"labels": state["labels"], "centroids": state["c"]})
         rechecks.append(KM.last_recheck_count(x.device))
         s_per_iter = dt / steps
         out.update({"metric": "k-means seconds per Lloyd iteration (u2seg_R50_%d Instance_Clustering: N = 1M x 768 DINO-sized "
@@ -657,11 +828,11 @@ def main():
     if share_gpu:
         out["data"] = "synthetic; SMOKE TEST of the multi-rank code path: %d ranks share cuda:0 over gloo (U2_BENCH_SHARE_GPU=1) - not a measurement" % world
     if args.workload == "train":
-        out.update(run_train(args.steps, args.warmup))
+        out.update(run_train(args.steps, args.warmup, args.dump_outputs))
     elif args.workload == "infer":
-        out.update(run_infer(args.steps, args.warmup))
+        out.update(run_infer(args.steps, args.warmup, args.dump_outputs))
     else:
-        out.update(run_kmeans(args.steps, args.warmup, args.kmeans_data))
+        out.update(run_kmeans(args.steps, args.warmup, args.kmeans_data, dump_dir=args.dump_outputs))
     extra = {}
     if args.workload == "train" and not args.no_extra:
         # BASELINE.json configs[3] and configs[4] in the same invocation, after the timed training region and

@@ -6,7 +6,7 @@ container (the reference does not travel to the GPU box); the resulting .npz / .
 
 Without --only: kmeans, knn, ops, model_small, trajectory, inference.  The host-side fixtures need their stand-ins in place
 before detectron2.data is imported and therefore run one per process:
-    --only data | eval | pseudo_panoptic | label_prep | config
+    --only data | eval | pseudo_panoptic | label_prep | config | yaml_chain
 
 Stand-ins (none of them carries hot-path arithmetic except the two torchvision ops):
   * fvcore / iopath / yacs / omegaconf / termcolor / cv2 ... : registry, config node, weight init, smooth_l1 etc.
@@ -1295,6 +1295,27 @@ def gen_config_fixture():
     print("wrote config_golden", {k: len(v) for k, v in out.items()})
 
 
+def gen_yaml_chain_fixture():
+    """The reference's yaml files of the three U2Seg configs as parsed data, every file of their _BASE_ chains under its path
+    relative to configs/ (comments dropped): the test writes them back and loads the chain through this repo's loader."""
+    names = ["u2seg_R50_800", "u2seg_R50_300", "u2seg_eval_800"]
+    files = {}
+    todo = ["COCO-PanopticSegmentation/%s.yaml" % n for n in names]
+    while todo:
+        rel = todo.pop()
+        if rel in files:
+            continue
+        with open(os.path.join(REF, "configs", rel)) as f:
+            files[rel] = yaml.safe_load(f) or {}
+        base = files[rel].get("_BASE_")
+        if base is not None:
+            todo.append(os.path.normpath(os.path.join(os.path.dirname(rel), base)))
+    out = {"configs": names, "files": files}
+    assert json.loads(json.dumps(out)) == out, "a yaml value without a JSON form"
+    json.dump(out, open(os.path.join(HERE, "yaml_chain_golden.json"), "w"), indent=1, sort_keys=True)
+    print("wrote yaml_chain_golden", sorted(files))
+
+
 def gen_refunit_fixture():
     """The seeded scenarios of the reference's own unit tests with published expected values - tests/modeling/test_rpn.py:35-67,
     test_fast_rcnn.py:17-45, test_roi_heads.py:39-92 - run through the reference here.  The reference's results are first
@@ -1941,6 +1962,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if a.only == "config":
         gen_config_fixture()
+        sys.exit(0)
+    if a.only == "yaml_chain":
+        gen_yaml_chain_fixture()
         sys.exit(0)
     if a.only == "label_prep":
         gen_label_prep_fixture()

@@ -44,14 +44,22 @@ def test_config_chain_and_overrides():
     assert "PanopticFPN" in cfg.dump()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="reference tree not present")
-def test_reference_yaml_chain_loads_unchanged():
-    """The reference's own 3-file _BASE_ chain gives the same tree as this repo's flat files."""
+def test_reference_yaml_chain_loads_unchanged(tmp_path):
+    """The reference's own 3-file _BASE_ chain gives the same tree as this repo's flat files.  The chain's files are stored
+    as parsed data (fixture: tests/golden/make_fixtures.py --only yaml_chain) and written back as yaml at their relative paths."""
+    import yaml
+
     from u2seg_amd.config import get_cfg
 
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "yaml_chain_golden.json")))
+    for rel, content in gold["files"].items():
+        path = tmp_path / "configs" / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(yaml.safe_dump(content))
+    assert sorted(gold["configs"]) == ["u2seg_R50_300", "u2seg_R50_800", "u2seg_eval_800"]
     for name in ("u2seg_R50_800.yaml", "u2seg_R50_300.yaml", "u2seg_eval_800.yaml"):
         ref = get_cfg()
-        ref.merge_from_file(os.path.join("/root/reference/configs/COCO-PanopticSegmentation", name))
+        ref.merge_from_file(str(tmp_path / "configs" / "COCO-PanopticSegmentation" / name))
         mine = _cfg(name)
         for k in ("WEIGHTS", "DEVICE"):
             mine.MODEL[k] = ref.MODEL[k]
