@@ -6,8 +6,12 @@ COCO-shaped 3x800x1333 batches, bf16 activations / fp32 master weights, one proc
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (contract in the task statement).  `roofline` is measured live with HIP events
-around every launch of the dominant kernel family (the MFMA implicit-GEMM conv) inside the timed region;
-`cpu_baseline` times the CPU oracle (oracle/) on a bounded sample (rank 0, N = 1 only).
+around every launch of the dominant kernel family (the MFMA implicit-GEMM conv) inside the timed region.
+
+A plain run does only what its headline figure needs: set-up, the W warm-up and K timed steps, --dump-outputs if given, the
+JSON line.  `--full` adds what takes runs of its own: `cpu_baseline` times the CPU oracle (oracle/) on a bounded sample (rank 0,
+N = 1 only), and the training workload appends the k-means and inference workloads as `extra_workloads` (--no-cpu-baseline and
+--no-extra leave either out again).
 
 The default workload is BASELINE.json's metric (configs[1]: training images/s).  Two more workloads make the other
 single-GPU configurations driver-measurable with the same JSON contract:
@@ -124,7 +128,7 @@ class KernelTimer:
 
 
 CPU_BASELINE_THREADS = 32     # more threads than this slow the oracle's small fp32 convolutions down (256 threads: 15x slower)
-CPU_BASELINE_TIMEOUT_S = 200  # the default bench.py run must stay within a few minutes
+CPU_BASELINE_TIMEOUT_S = 200  # a --full bench.py run must stay within a few minutes
 CFG_DIR = os.path.join(ROOT, "configs", "COCO-PanopticSegmentation")
 KMEANS_D, KMEANS_K = 768, 300
 
@@ -497,10 +501,13 @@ def main():
     ap.add_argument("--kmeans-n", type=int, default=1000000, help="points in total (sharded over the GPUs)")
     ap.add_argument("--kmeans-data", choices=["randn", "mixture"], default="mixture",
                     help="SURVEY 8(d) config 4: x = randn(N, 768) (base case) or the mixture of 300 Gaussians, sigma 0.5")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU oracle's `cpu_baseline` (N = 1) and, for the train "
+                         "workload, the k-means and inference workloads as `extra_workloads`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave `cpu_baseline` out")
     ap.add_argument("--no-extra", action="store_true",
-                    help="train workload only: do not append the k-means (config 4) and inference (config 5) measurements as "
-                         "`extra_workloads` (they run after the timed training region, N = 1 only)")
+                    help="with --full, train workload only: do not append the k-means (config 4) and inference (config 5) "
+                         "measurements as `extra_workloads` (they run after the timed training region)")
     ap.add_argument("--serial", action="store_true",
                     help="every step in one stream (no side / second stream): the mode the roofline sample steps run in; used "
                          "for the rocprofv3 summary that the per-kernel durations of the roofline object are checked against")
@@ -834,7 +841,7 @@ def main():
     else:
         out.update(run_kmeans(args.steps, args.warmup, args.kmeans_data, dump_dir=args.dump_outputs))
     extra = {}
-    if args.workload == "train" and not args.no_extra:
+    if args.workload == "train" and args.full and not args.no_extra:
         # BASELINE.json configs[3] and configs[4] in the same invocation, after the timed training region and
         # with the training state released; each entry is a full bench object (own timed region, roofline, cpu_baseline at N = 1).
         # At N > 1 every rank takes part: k-means shards the rows (the M step all-reduces K*D + K partial sums), inference runs
@@ -849,7 +856,7 @@ def main():
                 extra[name] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
             release()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             kinds = [args.workload] + (["kmeans", "infer"] if extra else [])
             cb = cpu_baselines_parallel(kinds)
             out["cpu_baseline"] = cb[args.workload]
