@@ -154,6 +154,26 @@ int u2_bn_bwd_apply_fused(const float* sums, float count, const float* count_dev
                           const float* invstd, const float* local_sums, float* dgamma, float* dbeta, float* k123, int accumulate,
                           const void* dout, const void* mask, const void* x, void* dx, void* dres, int rows, int C, int ld,
                           int relu, const float* mask_scale, const float* mask_shift, void* stream);
+/* Precise BatchNorm statistics (fvcore.nn.precise_bn.update_bn_stats behind detectron2/engine/hooks.py:567-636): the population
+ * mean and variance of every training-mode BN layer over K batches, from the batch statistics a momentum-1.0 training forward
+ * leaves in running_mean / running_var.  One row per layer; the table is built once per pass.  The layer's batch size b
+ * (N * H * W of its input) is derived on the device from the padded canvas: b = n * ceil(h / stride) * ceil(w / stride). */
+typedef struct {
+  float* running_mean;  /* [channels] fp32: this iteration's batch mean (update); the population mean (finalize writes) */
+  float* running_var;   /* [channels] fp32: the batch's unbiased variance (update); the population variance (finalize writes) */
+  int offset;           /* first channel of the layer in the packed accumulators */
+  int channels;
+  int stride;           /* spatial stride of the layer's map relative to the padded canvas */
+  int reserved;
+} U2PreciseBnLayer;
+/* acc: fp64 [2][total_channels] (A = sum b * mean, Q = sum b * mean^2 + (b - 1) * var), tot: fp64 [n_layers] (T = sum b), zeroed
+ * by the caller before the first update.  One work-group per layer, one thread per channel: no atomics, bit-reproducible.
+ * (n, h, w): images and padded canvas of this iteration's batch. */
+int u2_bn_precise_update(const U2PreciseBnLayer* table, int n_layers, double* acc, double* tot, int total_channels, int n, int h,
+                         int w, void* stream);
+/* running_mean = A / T, running_var = Q / T - (A / T)^2 (population variance, no Bessel factor), rounded once to fp32. */
+int u2_bn_precise_finalize(const U2PreciseBnLayer* table, int n_layers, const double* acc, const double* tot, int total_channels,
+                           void* stream);
 int u2_relu_bwd(const void* dout, const void* out, void* dz, long long numel, void* stream);
 /* The same with the bias gradient of the layer in the same pass: dst[c] += sum over rows of dz[row][c] for c < n_valid (dz: [rows][ld],
  * C physical channels; zeros: C floats of 0).  Replaces u2_relu_bwd + u2_colsum_add for a conv with bias and ReLU. */

@@ -6,6 +6,7 @@ Data: when the dataset DATASETS.TRAIN names is on disk (builtin registration und
 u2seg_amd/data/datasets.py) batches come from the real pipeline - DatasetMapper in DataLoader workers, aspect-ratio
 grouping, DevicePrefetcher into HBM; otherwise (or with DATASETS.TRAIN ("synthetic",)) from the synthetic generator.
 Deviation (recorded in DESIGN.md): the reference hard-wires --eval-only to True (engine/defaults.py:109); here it is a flag."""
+import itertools
 import os
 import sys
 import time
@@ -19,7 +20,8 @@ from u2seg_amd.checkpoint import DetectionCheckpointer  # noqa: E402
 from u2seg_amd.config import get_cfg  # noqa: E402
 from u2seg_amd.data import (DatasetCatalog, DevicePrefetcher, MetadataCatalog, build_detection_train_loader,  # noqa: E402
                             make_synthetic_batch, register_all_coco)
-from u2seg_amd.engine import SimpleTrainer, default_argument_parser, launch_info  # noqa: E402
+from u2seg_amd.engine import (SimpleTrainer, default_argument_parser, get_bn_modules, launch_info,  # noqa: E402
+                              precise_bn_due, update_bn_stats)
 from u2seg_amd.modeling import build_model  # noqa: E402
 from u2seg_amd.solver import build_lr_scheduler, build_optimizer  # noqa: E402
 from u2seg_amd.utils.env import configure_host_threads  # noqa: E402
@@ -33,8 +35,9 @@ def setup(args):
     return cfg
 
 
-def real_batches(cfg, device):
-    """Iterator over device-resident training batches of the real dataset, or None when it is not on disk."""
+def real_batches(cfg, device, seed=None):
+    """Iterator over device-resident training batches of the real dataset, or None when it is not on disk.
+    seed: the sampler's seed (default: cfg.SEED, or a shared random one when it is negative)."""
     names = [n for n in cfg.DATASETS.TRAIN if n != "synthetic"]
     if not names:
         return None
@@ -43,8 +46,31 @@ def real_batches(cfg, device):
         meta = MetadataCatalog.get(n)
         if n not in DatasetCatalog or not os.path.isfile(meta.get("json_file", "")) or not os.path.isdir(meta.get("image_root", "")):
             return None
-    loader = build_detection_train_loader(cfg, seed=None if cfg.SEED < 0 else cfg.SEED)
+    if seed is None and cfg.SEED >= 0:
+        seed = cfg.SEED
+    loader = build_detection_train_loader(cfg, seed=seed)
     return iter(DevicePrefetcher(loader, device) if str(device).startswith("cuda") else loader)
+
+
+def precise_bn_batches(cfg, device, per_gpu, rank, world):
+    """The precise-BN pass's own stream of training batches (engine/defaults.py:439-446), independent of the training stream,
+    created on the first pass and continued by later ones.  Real data: a second training loader from the same config with
+    DATALOADER.NUM_WORKERS = 0, as the reference builds it "to not affect training", and a sampler seed of its own.  Synthetic
+    data: generator indices past every index the training stream can reach (it uses (it * world + rank) * per_gpu + i for
+    it < MAX_ITER)."""
+    c = cfg.clone()
+    c.defrost()
+    c.DATALOADER.NUM_WORKERS = 0
+    stream = real_batches(c, device, seed=None if cfg.SEED < 0 else cfg.SEED + 1)
+    if stream is not None:
+        return stream
+
+    def synthetic():
+        base = cfg.SOLVER.MAX_ITER * world
+        for k in itertools.count():
+            yield make_synthetic_batch(per_gpu, start_index=(base + k * world + rank) * per_gpu, device=device)
+
+    return synthetic()
 
 
 def evaluate_on_disk_datasets(cfg, model, eval_mode, device):
@@ -112,6 +138,12 @@ def main(args):
     stream = real_batches(cfg, c.MODEL.DEVICE)
     if rank == 0:
         print("data: %s" % ("real pipeline over %s" % (cfg.DATASETS.TRAIN,) if stream is not None else "synthetic generator"))
+    # engine/defaults.py:428-452: the PreciseBN hook, registered before the checkpointer, so that the checkpoint of the same
+    # iteration (model_final included) holds the recomputed statistics
+    precise_bn = cfg.TEST.PRECISE_BN.ENABLED and len(get_bn_modules(model)) > 0
+    if cfg.TEST.PRECISE_BN.ENABLED and not precise_bn and rank == 0:
+        print("PreciseBN is disabled because model doesn't contain BN layers in training mode.")
+    bn_stream = None
     t0 = time.time()
     for it in range(start_iter, cfg.SOLVER.MAX_ITER):
         if stream is not None:
@@ -122,6 +154,13 @@ def main(args):
         if rank == 0 and (it % 20 == 0 or it == cfg.SOLVER.MAX_ITER - 1):
             total = trainer.check_finite()
             print("iter %d  total_loss %.4f  lr %.6f  %.2f s/iter" % (it, total, opt.lr, (time.time() - t0) / (it - start_iter + 1)))
+        if precise_bn and precise_bn_due(it, cfg.SOLVER.MAX_ITER, cfg.TEST.EVAL_PERIOD):
+            if bn_stream is None:
+                bn_stream = precise_bn_batches(cfg, c.MODEL.DEVICE, per_gpu, rank, world)
+            if rank == 0:
+                print("Running precise-BN for %d iterations...  Note that this could produce different statistics every time."
+                      % cfg.TEST.PRECISE_BN.NUM_ITER)
+            update_bn_stats(model, bn_stream, cfg.TEST.PRECISE_BN.NUM_ITER)
         if (it + 1) % cfg.SOLVER.CHECKPOINT_PERIOD == 0 or it == cfg.SOLVER.MAX_ITER - 1:
             checkpointer.save("model_%07d" % it if it < cfg.SOLVER.MAX_ITER - 1 else "model_final", iteration=it)
     if world > 1:
