@@ -465,6 +465,37 @@ int u2_knn_workspace_ints(int Nq, int Nt, int D, int K, long long* n_ints);
 int u2_knn(const float* x_query, const float* x_train, void* workspace, float* d_knn /*[Nq][K]*/,
            long long* ind_knn /*[Nq][K]*/, int Nq, int Nt, int D, int K, void* stream);
 
+/* ---- DINO ViT instance features (vit.hip): u2seg/Instance_Clustering/selective_labeling/dino.py:77-308 --------------------
+ * Stage 1's feature extractor (ViTFeat.forward, dino.py:296-308).  The linears (qkv, proj, fc1, fc2, patch_embed.proj) run
+ * through u2_conv_igemm; these kernels do the rest.  bf16 = raw uint16 bits; the residual stream is fp32 [B][T][D].
+ *
+ * Patch rows for patch_embed.proj (dino.py:170-173): out bf16 [B * P][3 * patch * patch], P = (H / patch) * (W / patch) in
+ * row-major grid order, columns in (c, kh, kw) order (the weight [D][3][p][p] viewed as [D][3 p p]).  in_u8 = 1: img is
+ * uint8 NHWC RGB [B][H][W][3] and norm device fp32 [6] = mean[3], std[3]: (u / 255 - mean) / std in fp32, torchvision's
+ * ToTensor + Normalize (shared/utils/nn_utils_imagenet.py:411-430); in_u8 = 0: img is fp32 NCHW already normalised
+ * (norm may be NULL).  C must be 3. */
+int u2_vit_patchify(const void* img, const float* norm, void* out, int B, int H, int W, int C, int patch, int in_u8,
+                    void* stream);
+/* prepare_tokens (dino.py:224-235): x[b][0] = cls[:] + pos[0], x[b][1 + p] = (patch_out[b * (T - 1) + p] + bias) + pos[1 + p],
+ * all adds in fp32; patch_out is the bf16 GEMM output [B * (T - 1)][out_ld] without its bias, pos fp32 [T][D]. */
+int u2_vit_embed(const void* patch_out, int out_ld, const float* bias, const float* cls, const float* pos, float* x,
+                 int B, int T, int D, void* stream);
+/* Block.forward's residual add and the next LayerNorm (dino.py:135-142, 281/292 LayerNorm(eps)), one pass per row:
+ * row r of the residual is x + r * x_stride; if branch != NULL: x += branch[r * branch_stride] (bf16) + branch_bias (fp32,
+ * may be NULL), written back; then out[r * out_stride] = LayerNorm(x) with fp32 statistics (biased variance), bf16, or fp32
+ * when out_fp32 (the final norm; dino.py:304-308).  D % 64 == 0, D <= 1024.  x_stride = T * D visits only the CLS rows. */
+int u2_vit_residual_layernorm(float* x, long long x_stride, const void* branch, long long branch_stride,
+                              const float* branch_bias, const float* gamma, const float* beta, void* out,
+                              long long out_stride, int out_fp32, int rows, int D, float eps, void* stream);
+/* Attention.forward (dino.py:108-120) without the attention matrix: q, k, v of (image b, token t, head h, d) are columns
+ * s * D + h * 64 + d (s = 0, 1, 2) of qkv row b * T + t (qkv_ld elements per row, D = heads * 64: reshape(B, N, 3, H, C/H));
+ * out bf16 [B][q_rows][D], column h * 64 + d: (softmax(q k^T * head_dim^-0.5) v).transpose(1, 2).reshape(B, N, C) for the
+ * first q_rows queries of every image (q_rows = T, or 1 for the CLS row alone).  bf16 operands, fp32 accumulation and
+ * softmax.  head_dim must be 64; qkv 16-byte aligned, qkv_ld % 8 == 0. */
+int u2_vit_attention(const void* qkv, void* out, int B, int T, int heads, int head_dim, int qkv_ld, int q_rows, void* stream);
+/* nn.GELU() (exact erf form, dino.py:77-93) in place on n bf16 elements (n % 8 == 0, 16-byte aligned). */
+int u2_vit_gelu(void* x, long long n, void* stream);
+
 /* library self-description */
 int u2_abi_version(void);
 
