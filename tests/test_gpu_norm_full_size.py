@@ -103,7 +103,7 @@ class Check:
         got = got.detach().to(F64)
         err = (got - rnd(ref)).abs()
         tol = e + step(ref.abs() + e)
-        self._count(got, ref, err > tol, err / (tol + 1e-300), tol)
+        self._count(got, ref, (err > tol) | err.isnan(), err / (tol + 1e-300), tol)   # NaN: never within a bound
 
     def add_interval(self, got, lo, hi, ref):
         """got must lie in [lo, hi]: the reference chain (monotone in its input: roundings, sums with a fixed addend, ReLU)
@@ -111,7 +111,7 @@ class Check:
         exact: it allows a second step only where the interval straddles a rounding midpoint of an intermediate bf16 tensor."""
         got = got.detach().to(F64)
         dist = torch.maximum(lo - got, got - hi).clamp_min(0)
-        self._count(got, ref, dist > 0, dist, hi - lo)
+        self._count(got, ref, (dist > 0) | got.isnan(), dist, hi - lo)
 
     def _count(self, got, ref, bad, ratio, tol):
         self.bad += int(bad.sum())
