@@ -465,6 +465,18 @@ int u2_knn_workspace_ints(int Nq, int Nt, int D, int K, long long* n_ints);
 int u2_knn(const float* x_query, const float* x_train, void* workspace, float* d_knn /*[Nq][K]*/,
            long long* ind_knn /*[Nq][K]*/, int Nq, int Nt, int D, int K, void* stream);
 
+/* ---- USL selection regularizer (usl.hip): nn_utils_imagenet.py:147-212 (get_selection_with_reg_imagenet's update) -------
+ * For every row i of x [N][D]: the H smallest sum_d (x[i][d] - sel[j][d])^2 over the S rows of sel [S][D] (ties: smaller j),
+ * masked (exclude_same_cluster != 0: 1e10 where the position j == labels[i]; else 1e10 where the distance is 0), then
+ * new = sum 1 / v (alpha == 1) or sum 1 / v ** alpha, and reg_out[i] = reg_in[i] * momentum + new * one_minus_momentum.
+ * Rows that keep a 0 after the mask add 1 to *zero_count (device int, zeroed by the caller): the reference's
+ * AssertionError.  D % 16 == 0, 1 <= H <= 64, S >= H (else -2); N == 0 is a no-op.
+ * workspace: u2_usl_reg_workspace_ints() 4-byte words of device memory. */
+int u2_usl_reg_workspace_ints(int N, int S, int D, int H, long long* n_ints);
+int u2_usl_regularizer(const float* x, const float* sel, const long long* labels, const float* reg_in, float* reg_out,
+                       int* zero_count, void* workspace, int N, int S, int D, int H, float alpha, float momentum,
+                       float one_minus_momentum, int exclude_same_cluster, void* stream);
+
 /* ---- DINO ViT instance features (vit.hip): u2seg/Instance_Clustering/selective_labeling/dino.py:77-308 --------------------
  * Stage 1's feature extractor (ViTFeat.forward, dino.py:296-308).  The linears (qkv, proj, fc1, fc2, patch_embed.proj) run
  * through u2_conv_igemm; these kernels do the rest.  bf16 = raw uint16 bits; the residual stream is fp32 [B][T][D].

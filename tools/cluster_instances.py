@@ -10,6 +10,13 @@ ROOT is an ImageFolder tree (ROOT/train/<class>/<crop> as the reference reads it
   memory_feats_list.npy                 fp32 [N, 768] features in dataset order
   cluster_labels_<K>_<seed>.npy, centroids_<K>_<seed>.npy   (nn_utils.py:380-405)
 and prints the time of each phase.  --num-centroids is explicit: the reference's get_sample_info_coco does not exist.
+With --num-selected S it also runs the regularised selection of one representative per cluster that the shipped USL config
+takes (get_selection_with_reg_imagenet, nn_utils_imagenet.py:105-218; the --reg-* defaults are USL.REG of
+configs/ImageNet_usl_dino_0.2.yaml) and writes what the reference run writes from it:
+  selected_indices_<S>_<seed>.npy                                    (nn_utils.py:442-460)
+  train_<p>p_gen_<run>_index.csv, train_<100-p>p_gen_<run>_index.csv  (nn_utils_imagenet.py:36-75; p from
+                                      get_sample_info_imagenet(S), <run> = --run-name, + _seed<s> for a seed other than 0)
+Existing files are overwritten, as the other outputs are (the reference refuses to overwrite them).
 The architecture follows the checkpoint (--arch auto); --arch base|small --patch-size P forces one of dino.py's."""
 import argparse
 import json
@@ -26,6 +33,7 @@ sys.path.insert(0, ROOT)
 from u2seg_amd import _hip  # noqa: E402
 from u2seg_amd.cluster import dino  # noqa: E402
 from u2seg_amd.cluster.kmeans import run_kmeans  # noqa: E402
+from u2seg_amd.cluster import select  # noqa: E402
 from u2seg_amd.cluster.knn import first_order_density, partitioned_kNN  # noqa: E402
 from u2seg_amd.data.crops import CropFolder, crop_loader  # noqa: E402
 
@@ -44,6 +52,15 @@ def parse_args(argv=None):
     p.add_argument("--arch", choices=("auto", "base", "small"), default="auto")
     p.add_argument("--patch-size", type=int, default=8)
     p.add_argument("--out", default="output/cluster_instances")
+    p.add_argument("--num-selected", type=int, default=None, help="run the regularised USL selection of S representatives")
+    p.add_argument("--reg-niters", type=int, default=2)
+    p.add_argument("--reg-w", type=float, default=0.05)
+    p.add_argument("--reg-momentum", type=float, default=0.0)
+    p.add_argument("--reg-horizon", type=int, default=32)
+    p.add_argument("--reg-alpha", type=float, default=1.0)
+    p.add_argument("--reg-keep-same-cluster", action="store_true",
+                   help="exclude_same_cluster=False (the shipped config excludes them)")
+    p.add_argument("--run-name", default="imagenet_usl_dino_0.2")
     return p.parse_args(argv)
 
 
@@ -86,6 +103,15 @@ def run(args):
     table = {key: int(c) for key, c in zip(ds.keys(), labels.cpu().tolist())}
     with open(os.path.join(args.out, "cluster_labels_decode.json"), "w") as f:
         json.dump(table, f)
+    if args.num_selected is not None:
+        t = time.time()
+        _, chosen_percent = select.get_sample_info_imagenet(args.num_selected)
+        selected = select.get_selection(
+            select.get_selection_with_reg_imagenet, feats, d_knns.mean(dim=1), labels, k, final_sample_num=args.num_selected,
+            iters=args.reg_niters, w=args.reg_w, momentum=args.reg_momentum, horizon_num=args.reg_horizon,
+            alpha=args.reg_alpha, exclude_same_cluster=not args.reg_keep_same_cluster, seed=s, run_dir=args.out)
+        select.save_split_csvs(args.out, selected, ds.keys(), chosen_percent, args.run_name, seed=s)
+        times["selection_s"] = time.time() - t
     for name, v in times.items():
         print("%-12s %.3f" % (name, v))
     print("crops %d  features %s  clusters used %d  mean density %.4g" % (
