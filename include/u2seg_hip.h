@@ -414,6 +414,46 @@ typedef struct U2PanopticImage {
 int u2_panoptic_merge(const U2PanopticImage* images, int n_images, float overlap_thr, int stuff_area_thr, float score_thr,
                       int mask_res, void* stream);
 
+/* ---- mask evaluation (maskeval.hip): the "segm" task of evaluation/coco_evaluation.py, DESIGN.md section 11 -----------------
+ * Bit planes: a mask of H x W is W columns of wpc = ceil(H / 64) 64-bit words, column-major like COCO's RLE scan: bit b of
+ * word j of column x = pixel (y = 64 j + b, x), padding bits zero.  A ragged batch is described by a HOST array: image i owns
+ * the per-mask entries [first, first + n) of area / box / offs, its n canvases of H x W bytes start at byte in_offset (a
+ * multiple of 16) of the 16-byte aligned canvases, its n planes of W * wpc words at word plane_offset of `planes`, and its
+ * n * W per-column entries at col_offset of colcnt / last3 / cntcum / lastne / collen / strcum.  H * W < 2^31, n <= 65535;
+ * images with n, H or W == 0 are skipped.  All results are integers: exact. */
+typedef struct U2MaskImage { int first, n, H, W; long long in_offset, plane_offset, col_offset; } U2MaskImage;
+/* canvases (uint8, nonzero = set; what u2_paste_masks_batch writes) -> planes; every byte is read once (16-byte loads, a
+ * 64-row band transposed through LDS).  area [M] (set pixels) and box [M][4] = x, y, w, h of the tight box (zeros for an
+ * empty mask) are written when both are given. */
+int u2_mask_pack_planes(const void* canvases, void* planes, int* area, int* box, const U2MaskImage* images, int num_images,
+                        void* stream);
+/* The COCO counts strings of the planes' masks, byte for byte data/rle.py's encode: count -> scan -> lengths -> scan -> emit.
+ * u2_mask_rle_count: colcnt[col] = run starts (pixels that differ from their predecessor in the column-major scan, the
+ * predecessor of pixel (0, 0) being 0) in that column, last3[col][3] = scan positions x H + y of its last three, newest first.
+ * The caller then forms cntcum = inclusive prefix sum of colcnt and lastne[col] = the last col' <= col with colcnt > 0 (-1:
+ * none), both over the flat column list.  u2_mask_rle_lengths: collen[col] = characters the column's counts take (the final
+ * count of a mask belongs to its last column).  With strcum = inclusive prefix sum of collen, u2_mask_rle_emit writes the
+ * characters of column col at arena[strcum[col - 1]...] (nothing at or past arena_bytes): the string of a mask is
+ * arena[strcum[c0 - 1] : strcum[c0 + W - 1]) with c0 its first column. */
+int u2_mask_rle_count(const void* planes, int* colcnt, int* last3, const U2MaskImage* images, int num_images, void* stream);
+int u2_mask_rle_lengths(const void* planes, const int* colcnt, const int* last3, const long long* cntcum,
+                        const long long* lastne, int* collen, const U2MaskImage* images, int num_images, void* stream);
+int u2_mask_rle_emit(const void* planes, const int* colcnt, const int* last3, const long long* cntcum, const long long* lastne,
+                     const long long* strcum, void* arena, long long arena_bytes, const U2MaskImage* images, int num_images,
+                     void* stream);
+/* Ground truth: uncompressed counts -> planes.  cum = inclusive prefix sums of the flat list of all masks' counts, offs
+ * [M + 1] = index of every mask's first count (mask first + k of image i uses offs[first + k], offs[first + k + 1]); the counts
+ * of a mask must sum to H * W (the caller checks).  Every word of the planes is written, padding included. */
+int u2_mask_planes_from_counts(const long long* cum, const long long* offs, void* planes, const U2MaskImage* images,
+                               int num_images, void* stream);
+/* inter[out_offset + d * G + g] = popcount(dt plane d & gt plane g) for every image of the HOST array: its D detection planes
+ * start at word dt_offset of dt_planes, its G ground-truth planes at word gt_offset of gt_planes, both H x W.  dt_boxes
+ * (optional, [..][4] as written by u2_mask_pack_planes, the image's rows starting at dt_first) limits the words read to the
+ * detection's columns.  D == 0 or G == 0: nothing is written. */
+typedef struct U2PairImage { long long dt_offset, gt_offset, out_offset; int D, G, H, W, dt_first, pad_; } U2PairImage;
+int u2_mask_pair_counts(const void* dt_planes, const void* gt_planes, const int* dt_boxes, int* inter,
+                        const U2PairImage* images, int num_images, void* stream);
+
 /* ---- optimizer (optim.hip): solver/build.py:36-37,63-73,119-139 ------------------------------- */
 int u2_sgd_clip_step(float* params, const float* grads, float* momentum_buf, const int* chunk_tensor,
                      const long long* chunk_begin, const int* chunk_len, int n_chunks, float* partial /*[n_chunks]*/,

@@ -73,7 +73,7 @@ def precise_bn_batches(cfg, device, per_gpu, rank, world):
     return synthetic()
 
 
-def evaluate_on_disk_datasets(cfg, model, eval_mode, device):
+def evaluate_on_disk_datasets(cfg, model, eval_mode, device, tasks=("bbox",)):
     """The reference's Trainer.test (engine/defaults.py:591-640) for the DATASETS.TEST entries that are on disk: first run
     with --eval-mode hungarian_matching (writes ./hungarian_matching/*.json), then with --eval-mode eval.  None when no
     test dataset is available."""
@@ -88,7 +88,7 @@ def evaluate_on_disk_datasets(cfg, model, eval_mode, device):
             continue
         loader = build_detection_test_loader(cfg, name)
         stream = DevicePrefetcher(loader, device) if str(device).startswith("cuda") else loader
-        results[name] = inference_on_dataset(model, stream, build_evaluator(cfg, name, eval_mode=eval_mode))
+        results[name] = inference_on_dataset(model, stream, build_evaluator(cfg, name, eval_mode=eval_mode, tasks=tasks))
     return results or None
 
 
@@ -111,7 +111,8 @@ def main(args):
         # tools/train_net.py:135-141 of the reference: weights from MODEL.WEIGHTS (or the last checkpoint with --resume)
         if cfg.MODEL.WEIGHTS and os.path.isfile(cfg.MODEL.WEIGHTS):
             DetectionCheckpointer(model, cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
-        results = evaluate_on_disk_datasets(cfg, model, args.eval_mode, c.MODEL.DEVICE)
+        tasks = tuple(t for t in args.eval_tasks.split(",") if t)
+        results = evaluate_on_disk_datasets(cfg, model, args.eval_mode, c.MODEL.DEVICE, tasks)
         if results is not None:
             if rank == 0:
                 print(results)

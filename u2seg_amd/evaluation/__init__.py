@@ -5,9 +5,9 @@ from .sem_seg_evaluation import SemSegEvaluator
 
 
 
-def build_evaluator(cfg, dataset_name, output_folder=None, eval_mode="eval"):
+def build_evaluator(cfg, dataset_name, output_folder=None, eval_mode="eval", tasks=("bbox",)):
     """tools/train_net.py:42-81 of the reference for the evaluator types the U2Seg datasets carry: semantic, instance and
-    panoptic evaluators for "coco_panoptic_seg"."""
+    panoptic evaluators for "coco_panoptic_seg".  tasks: what the instance evaluator scores, ("bbox",) or ("bbox", "segm")."""
     import os
 
     from ..data.catalog import MetadataCatalog
@@ -19,7 +19,7 @@ def build_evaluator(cfg, dataset_name, output_folder=None, eval_mode="eval"):
     if kind in ("sem_seg", "coco_panoptic_seg"):
         evaluators.append(SemSegEvaluator(dataset_name, output_dir=output_folder, mode=eval_mode))
     if kind in ("coco", "coco_panoptic_seg"):
-        evaluators.append(COCOEvaluator(dataset_name, output_dir=output_folder, mode=eval_mode))
+        evaluators.append(COCOEvaluator(dataset_name, output_dir=output_folder, mode=eval_mode, tasks=tasks))
     if kind == "coco_panoptic_seg":
         evaluators.append(COCOPanopticEvaluator(dataset_name, output_folder))
     if not evaluators:

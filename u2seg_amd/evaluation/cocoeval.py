@@ -9,7 +9,8 @@ C++ on the same instances.
 
 Stages: prepare (group ground truth and detections by (image, category); a crowd region is "ignore"; a detection's area is
 its box area) -> IoU of the score-sorted detections with the ground truth (intersection over the detection's area for
-crowd regions) -> per (category, area range, image) greedy matching at every IoU threshold -> per (category, area range,
+crowd regions; for masks, `evaluate_segm`: the area is the mask's and the IoU comes from pixel counts) -> per (category, area
+range, image) greedy matching at every IoU threshold -> per (category, area range,
 detection budget) precision / recall curves over all images -> the twelve summary numbers."""
 import numpy as np
 
@@ -42,9 +43,10 @@ def box_ious(dt_boxes, gt_boxes, gt_crowd):
     return inter / union
 
 
-def prepare(gt_annotations, results, params):
+def prepare(gt_annotations, results, params, dt_areas=None):
     """{(image id, category id): [instances]} for ground truth and detections.  Instances are dicts with id, bbox, area,
-    score (detections), iscrowd and ignore (ground truth: a crowd region is ignored, cocoeval.py `_prepare`)."""
+    score (detections), iscrowd and ignore (ground truth: a crowd region is ignored, cocoeval.py `_prepare`).  dt_areas
+    (mask evaluation): the area of every result, in place of its box area; the results then need no "bbox"."""
     imgs, cats = set(params.imgIds), set(params.catIds)
     gts, dts = {}, {}
     for ann in gt_annotations:
@@ -53,11 +55,11 @@ def prepare(gt_annotations, results, params):
             area = ann["area"] if "area" in ann else ann["bbox"][2] * ann["bbox"][3]
             gts.setdefault((ann["image_id"], ann["category_id"]), []).append(
                 {"id": ann["id"], "bbox": ann["bbox"], "area": area, "iscrowd": crowd, "ignore": crowd})
-    for k, res in enumerate(results):  # loadRes: ids 1.., area = box area, not a crowd
+    for k, res in enumerate(results):  # loadRes: ids 1.., area = box area (mask area for "segm"), not a crowd
         if res["image_id"] in imgs and res["category_id"] in cats:
+            area = res["bbox"][2] * res["bbox"][3] if dt_areas is None else dt_areas[k]
             dts.setdefault((res["image_id"], res["category_id"]), []).append(
-                {"id": k + 1, "bbox": res["bbox"], "area": res["bbox"][2] * res["bbox"][3], "score": res["score"],
-                 "iscrowd": 0, "ignore": 0})
+                {"id": k + 1, "bbox": res.get("bbox"), "area": area, "score": res["score"], "iscrowd": 0, "ignore": 0})
     return gts, dts
 
 
@@ -194,3 +196,84 @@ def evaluate_bbox(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100)):
     acc = accumulate(evaluate_images(gts, dts, ious, params), params)
     return {"stats": dict(zip(STAT_NAMES, summarize(acc, params))), "precision": acc["precision"], "recall": acc["recall"],
             "scores": acc["scores"], "params": params}
+
+
+def mask_ious(inter, area_dt, area_gt, gt_crowd):
+    """[D, G] float64 mask IoU from pixel counts: inter / (area_dt + area_gt - inter); for a crowd ground truth the union is
+    the detection's own area, inter / area_dt (cocoapi's rleIou, as its documentation states the rule).  A pair whose
+    denominator is 0 (an empty detection against an empty or crowd ground truth) has IoU 0: cocoapi is not available to this
+    project's tests, so its behaviour in that corner is not pinned."""
+    inter = np.asarray(inter, dtype=np.int64).reshape(len(area_dt), len(area_gt))
+    ad = np.asarray(area_dt, dtype=np.int64).reshape(-1, 1)
+    ag = np.asarray(area_gt, dtype=np.int64).reshape(1, -1)
+    union = np.where(np.asarray(gt_crowd, dtype=bool).reshape(1, -1), ad + 0 * ag, ad + ag - inter)
+    return np.where(union > 0, inter.astype(np.float64) / np.maximum(union, 1).astype(np.float64), 0.0)
+
+
+def host_pair_counts(gt_dataset, results, img_ids):
+    """The pair counts `evaluate_segm` takes, computed on the host from the RLEs of the results and of the ground truth:
+    {image id: {"gt_ids": [annotation ids], "inter": int64 [D, G], "area_dt": [D], "area_gt": [G]}}, the D rows in the order
+    of that image's entries in `results`, the G columns over all of the image's annotations."""
+    from ..data import rle
+    from . import mask_ops
+
+    imgs = set(img_ids)
+    anns, dets = {}, {}
+    for a in gt_dataset["annotations"]:
+        if a["image_id"] in imgs:
+            anns.setdefault(a["image_id"], []).append(a)
+    for r in results:
+        if r["image_id"] in imgs:
+            dets.setdefault(r["image_id"], []).append(r)
+    out = {}
+    for img, rs in dets.items():
+        h, w = rs[0]["segmentation"]["size"]
+        for r in rs:
+            if list(r["segmentation"]["size"]) != [h, w]:
+                raise ValueError("image %s: predicted masks of different sizes" % img)
+        masks = np.stack([rle.decode(r["segmentation"]) for r in rs]) if rs else np.zeros((0, h, w), dtype=np.uint8)
+        gts = anns.get(img, [])
+        inter, area_dt, area_gt = mask_ops.mask_pair_counts(masks, gts, h, w)
+        out[img] = {"gt_ids": [a["id"] for a in gts], "inter": inter, "area_dt": area_dt, "area_gt": area_gt}
+    return out
+
+
+def evaluate_segm(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100), pair_counts=None):
+    """Mask AP / AR: `evaluate_bbox` with two differences (the reference's _evaluate_predictions_on_coco with iou_type "segm",
+    coco_evaluation.py:672-679, drops "bbox" from the results for the first): a detection's area is its mask area (the
+    ground truth keeps ann["area"]), and the IoU tables come from masks.  results: COCO result dicts with an RLE
+    "segmentation".  pair_counts: what `host_pair_counts` returns, collected elsewhere (the evaluator does it per batch on the
+    device); None: computed here.  Returns evaluate_bbox's dict plus "ious" {(image, category): [D', G]}."""
+    imgs = sorted(im["id"] for im in gt_dataset["images"]) if img_ids is None else sorted(set(img_ids))
+    cats = sorted(c["id"] for c in gt_dataset["categories"])
+    params = Params(imgs, cats, max_dets)
+    if pair_counts is None:
+        pair_counts = host_pair_counts(gt_dataset, results, imgs)
+    row, seen, dt_areas = [], {}, []
+    for res in results:  # row of every result in its image's table
+        k = seen.get(res["image_id"], 0)
+        seen[res["image_id"]] = k + 1
+        row.append(k)
+        pc = pair_counts.get(res["image_id"])
+        dt_areas.append(int(pc["area_dt"][k]) if pc is not None else 0)
+    gts, dts = prepare(gt_dataset["annotations"], results, params, dt_areas)
+    ious = {}
+    for img in params.imgIds:
+        pc = pair_counts.get(img)
+        col = {a: j for j, a in enumerate(pc["gt_ids"])} if pc is not None else {}
+        for cat in params.catIds:
+            gt, dt = gts.get((img, cat), []), dts.get((img, cat), [])
+            if not gt and not dt:
+                ious[img, cat] = []
+                continue
+            order = np.argsort([-d["score"] for d in dt], kind="mergesort")[: params.maxDets[-1]]
+            if len(order) == 0 or not gt:
+                ious[img, cat] = np.zeros((len(order), len(gt)))
+                continue
+            rows = [row[dt[i]["id"] - 1] for i in order]
+            cols = [col[g["id"]] for g in gt]
+            ious[img, cat] = mask_ious(np.asarray(pc["inter"])[np.ix_(rows, cols)], np.asarray(pc["area_dt"])[rows],
+                                       np.asarray(pc["area_gt"])[cols], [g["iscrowd"] for g in gt])
+    acc = accumulate(evaluate_images(gts, dts, ious, params), params)
+    return {"stats": dict(zip(STAT_NAMES, summarize(acc, params))), "precision": acc["precision"], "recall": acc["recall"],
+            "scores": acc["scores"], "params": params, "ious": ious}
