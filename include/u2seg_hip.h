@@ -454,6 +454,28 @@ typedef struct U2PairImage { long long dt_offset, gt_offset, out_offset; int D, 
 int u2_mask_pair_counts(const void* dt_planes, const void* gt_planes, const int* dt_boxes, int* inter,
                         const U2PairImage* images, int num_images, void* stream);
 
+/* ---- panoptic quality (panopticeval.hip): evaluation/panoptic_ops.py, DESIGN.md section 12 ------------------------------------
+ * The joint histogram PQ is computed from: for every image of the HOST array, counts[(G + 2)][P] = pixels shared by a
+ * ground-truth row and a predicted id.  pred: the [H][W] int32 id map u2_panoptic_merge writes (0 = void), P = its largest
+ * segment id + 1.  gt: the ground-truth png's pixels [H][W][3] uint8, id = R + 256 G + 65536 B formed on the device, or with
+ * gt_is_ids = 1 an [H][W] int32 id map.  gt_table [G]: the ids of the ground truth's segments_info, strictly ascending.  Row 0 =
+ * ground-truth id 0 (void), rows 1..G = the table's ids in order, row G + 1 = every id the table does not list.  A pixel whose
+ * predicted id is < 0 or >= P enters no row and is counted in out_of_range[image] instead.  pred and gt must be 16-byte
+ * aligned (the image is read as one flat run of pixels: rows need no alignment, the last partial piece is read pixel by
+ * pixel, nothing past H * W pixels is touched); counts and out_of_range need no initialisation.  H * W < 2^31,
+ * (G + 2) * P < 2^31.  A table of at most u2_panoptic_pair_lds_ints() entries is accumulated in LDS per work-group and folded
+ * into counts, a larger one straight in counts; integer atomics either way: exact. */
+typedef struct U2PanopticPairImage {
+  const int* pred;           /* [H][W] */
+  const void* gt;            /* [H][W][3] uint8, or [H][W] int32 with gt_is_ids */
+  const int* gt_table;       /* [G] ascending (may be NULL when G == 0) */
+  int* counts;               /* [(G + 2)][P] out */
+  int H, W, G, P;
+  int gt_is_ids, pad_;
+} U2PanopticPairImage;
+int u2_panoptic_pair_counts(const U2PanopticPairImage* images, int n_images, int* out_of_range, void* stream);
+int u2_panoptic_pair_lds_ints(void);
+
 /* ---- optimizer (optim.hip): solver/build.py:36-37,63-73,119-139 ------------------------------- */
 int u2_sgd_clip_step(float* params, const float* grads, float* momentum_buf, const int* chunk_tensor,
                      const long long* chunk_begin, const int* chunk_len, int n_chunks, float* partial /*[n_chunks]*/,

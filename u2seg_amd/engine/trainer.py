@@ -69,6 +69,8 @@ def default_argument_parser():
     p.add_argument("--eval-only", action="store_true")
     p.add_argument("--eval-mode", default="hungarian_matching")
     p.add_argument("--eval-tasks", default="bbox", help="what the instance evaluator scores: bbox or bbox,segm (mask AP)")
+    p.add_argument("--panoptic-pq", default="files", choices=("files", "counts"),
+                   help="PQ from the written pngs (files) or from segment-pair counts made on the device (counts)")
     p.add_argument("--num-gpus", type=int, default=1)
     p.add_argument("--num-machines", type=int, default=1)
     p.add_argument("--machine-rank", type=int, default=0)

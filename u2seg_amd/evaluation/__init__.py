@@ -5,9 +5,10 @@ from .sem_seg_evaluation import SemSegEvaluator
 
 
 
-def build_evaluator(cfg, dataset_name, output_folder=None, eval_mode="eval", tasks=("bbox",)):
+def build_evaluator(cfg, dataset_name, output_folder=None, eval_mode="eval", tasks=("bbox",), panoptic_pq="files"):
     """tools/train_net.py:42-81 of the reference for the evaluator types the U2Seg datasets carry: semantic, instance and
-    panoptic evaluators for "coco_panoptic_seg".  tasks: what the instance evaluator scores, ("bbox",) or ("bbox", "segm")."""
+    panoptic evaluators for "coco_panoptic_seg".  tasks: what the instance evaluator scores, ("bbox",) or ("bbox", "segm");
+    panoptic_pq: "files" (PQ from the written pngs) or "counts" (from pair counts made on the device)."""
     import os
 
     from ..data.catalog import MetadataCatalog
@@ -21,7 +22,7 @@ def build_evaluator(cfg, dataset_name, output_folder=None, eval_mode="eval", tas
     if kind in ("coco", "coco_panoptic_seg"):
         evaluators.append(COCOEvaluator(dataset_name, output_dir=output_folder, mode=eval_mode, tasks=tasks))
     if kind == "coco_panoptic_seg":
-        evaluators.append(COCOPanopticEvaluator(dataset_name, output_folder))
+        evaluators.append(COCOPanopticEvaluator(dataset_name, output_folder, pq=panoptic_pq))
     if not evaluators:
         raise NotImplementedError("no Evaluator for the dataset {} with the type {}".format(dataset_name, kind))
     return evaluators[0] if len(evaluators) == 1 else DatasetEvaluators(evaluators)

@@ -135,3 +135,84 @@ def pq_compute(gt_json, pred_json, gt_folder, pred_folder):
                    rgb2id(np.asarray(Image.open(os.path.join(pred_folder, pa["file_name"])))), pa["segments_info"])
 
     return pq_compute_arrays(samples(), categories)
+
+
+def accumulate_counts(stat, counts, gt_table, gt_segments, pred_segments, categories):
+    """`accumulate_image` from the pair-count table of evaluation/panoptic_ops.py instead of the two id maps: counts
+    [G + 2, P] with row 0 = ground-truth void, rows 1..G = the ids of gt_table (ascending), row G + 1 = ground-truth ids that
+    segments_info does not list, column p = predicted id p.  The table holds what the three np.unique calls above find - a
+    predicted area is a column sum, a ground-truth area a row sum - and the candidate pairs are visited in ascending
+    (ground-truth id, predicted id) order, which is the order np.unique gives the packed keys: the float64 IoU sums are
+    bit-equal to accumulate_image's, not merely close.  An erased predicted segment needs no edit of the id map: moving its
+    column into column 0 is what turning its pixels to void amounts to, and predicted void never enters PQ."""
+    counts = np.asarray(counts, dtype=np.int64)
+    table = [int(g) for g in np.asarray(gt_table).reshape(-1).tolist()]
+    if counts.ndim != 2 or counts.shape[0] != len(table) + 2:
+        raise ValueError("a table of shape %s for %d ground-truth ids" % (tuple(counts.shape), len(table)))
+    gt_seg = {s["id"]: s for s in gt_segments}
+    pred_seg = {s["id"]: dict(s) for s in pred_segments}
+    col_area = counts.sum(axis=0).tolist()
+    labels = [p for p, a in enumerate(col_area) if a > 0]
+    for label in labels:
+        if label == VOID:
+            continue
+        if label not in pred_seg:
+            raise KeyError("segment id %d is in the predicted png but not in segments_info" % label)
+        if pred_seg[label]["category_id"] not in categories:
+            raise KeyError("segment %d has unknown category %r" % (label, pred_seg[label]["category_id"]))
+        pred_seg[label]["area"] = col_area[label]
+    missing = set(pred_seg) - set(labels)
+    if missing:
+        raise KeyError("segments_info lists ids that are not in the predicted png: %s" % sorted(missing))
+    row_of = {g: r + 1 for r, g in enumerate(table)}
+    row_area = counts.sum(axis=1).tolist()
+    void = counts[0].tolist()
+    gt_matched, pred_matched = set(), set()
+    for g in table:  # ascending
+        if g not in gt_seg:
+            continue
+        row = counts[row_of[g]]
+        for p in np.flatnonzero(row).tolist():  # ascending
+            if p == VOID or p not in pred_seg:
+                continue
+            if gt_seg[g].get("iscrowd", 0) == 1 or gt_seg[g]["category_id"] != pred_seg[p]["category_id"]:
+                continue
+            area = int(row[p])
+            union = pred_seg[p]["area"] + gt_seg[g].get("area", row_area[row_of[g]]) - area - void[p]
+            iou = area / union
+            if iou > 0.5:
+                cat = gt_seg[g]["category_id"]
+                stat.add(stat.tp, cat)
+                stat.add(stat.iou, cat, iou)
+                gt_matched.add(g)
+                pred_matched.add(p)
+    crowd_of = {}
+    for g, info in gt_seg.items():
+        if g in gt_matched:
+            continue
+        if info.get("iscrowd", 0) == 1:
+            crowd_of[info["category_id"]] = g
+            continue
+        stat.add(stat.fn, info["category_id"])
+    for p, info in pred_seg.items():
+        if p in pred_matched:
+            continue
+        excused = void[p]
+        if info["category_id"] in crowd_of and crowd_of[info["category_id"]] in row_of:
+            excused += int(counts[row_of[crowd_of[info["category_id"]]], p])
+        if excused / info["area"] > 0.5:
+            continue
+        stat.add(stat.fp, info["category_id"])
+
+
+def pq_compute_counts(samples, categories):
+    """`pq_compute_arrays` for samples of (counts, gt_table, gt_segments, pred_segments)."""
+    stat = PQStat()
+    for counts, gt_table, gt_segments, pred_segments in samples:
+        accumulate_counts(stat, counts, gt_table, gt_segments, pred_segments, categories)
+    out = {}
+    for name, flag in (("All", None), ("Things", True), ("Stuff", False)):
+        out[name], per_class = stat.average(categories, flag)
+        if name == "All":
+            out["per_class"] = per_class
+    return out
