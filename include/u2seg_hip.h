@@ -241,6 +241,12 @@ int u2_scale_to_bf16(const float* acc, const float* num, const float* den, float
                      void* stream);
 int u2_softmax_ce(const void* logits, const void* labels, void* dlogits, float* loss_sum, int R, int NC, int LP,
                   float gscale, void* stream);
+/* u2_softmax_ce plus the classification counts of fast_rcnn.py:88-115, made by the same kernel body (dlogits bit-identical):
+ * counters[0..4] += rows, pred == gt, fg (0 <= gt < bg_label), fg and pred == gt, fg and pred == bg_label, with pred = argmax
+ * over the NC valid columns (lowest index among equal maxima).  int32, integer atomics, one per counter and work-group (per
+ * wave where LP > 1024 or LP % 8 != 0); R == 0 adds nothing.  NaN logits are outside the contract. */
+int u2_softmax_ce_stats(const void* logits, const void* labels, void* dlogits, float* loss_sum, int R, int NC, int LP,
+                        float gscale, int* counters, int bg_label, void* stream);
 /* (u2_mask_predict_bce: phased_side = 0: x / dx are [N][P][C] in pixel order; phased_side = S2 (P = S2 * S2): they are the
  * 2x2 / stride-2 deconvolution's unshuffled GEMM output [N][S2/2][S2/2][2][2][C], target / logit_out stay in pixel order.
  * dx, dWp, dbp, loss_sum may each be NULL (not produced): the forward pass asks for the loss alone, the backward pass for the
@@ -248,6 +254,13 @@ int u2_softmax_ce(const void* logits, const void* labels, void* dlogits, float* 
 int u2_mask_predict_bce(const void* x, const float* Wp, const float* bp, const void* cls, const void* target, void* dx,
                         float* dWp, float* dbp, float* loss_sum, void* logit_out, int N, int P, int C, float gscale,
                         int phased_side, const float* gmul, void* stream);
+/* The loss-only form of u2_mask_predict_bce plus the counts of mask_head.py:90-102 over the rounded logit z and the target t:
+ * counters[0..3] += (z > 0 and t == 0), (z <= 0 and t != 0), (t != 0), positions.  One integer atomic per counter and
+ * work-group. */
+int u2_mask_predict_bce_stats(const void* x, const float* Wp, const float* bp, const void* cls, const void* target,
+                              float* loss_sum, int* counters, int N, int P, int C, int phased_side, void* stream);
+/* counters[0] += #(labels == 1), counters[1] += #(labels == 0) over n int8 labels (rpn.py:396-403 on the subsampled labels). */
+int u2_count_labels_i8(const void* labels, long long n, int* counters, void* stream);
 /* proposal_generator/rpn.py:366-429, one feature level.  dlt == NULL (and ddlt == NULL, A == 3): `obj` is the output of the
  * objectness and anchor-delta 1x1 convs run as ONE conv (columns 0-2 objectness, 3-14 deltas of an LPo-wide NHWC map) and dobj
  * receives both gradients in the same columns - the map their common input's gradient is then formed from by one data-gradient

@@ -25,6 +25,7 @@ from u2seg_amd.engine import (SimpleTrainer, default_argument_parser, get_bn_mod
 from u2seg_amd.modeling import build_model  # noqa: E402
 from u2seg_amd.solver import build_lr_scheduler, build_optimizer  # noqa: E402
 from u2seg_amd.utils.env import configure_host_threads  # noqa: E402
+from u2seg_amd.utils.events import EventStorage, JSONWriter  # noqa: E402
 
 
 def setup(args):
@@ -146,25 +147,46 @@ def main(args):
     if cfg.TEST.PRECISE_BN.ENABLED and not precise_bn and rank == 0:
         print("PreciseBN is disabled because model doesn't contain BN layers in training mode.")
     bn_stream = None
+    # OUTPUT_DIR/metrics.json, one line per 20 iterations (engine/defaults.py:build_writers): appended to on --resume, and the
+    # storage starts at start_iter so that the iteration numbers continue
+    writer = None
+    if rank == 0:
+        os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)
+        writer = JSONWriter(os.path.join(cfg.OUTPUT_DIR, "metrics.json"))
     t0 = time.time()
-    for it in range(start_iter, cfg.SOLVER.MAX_ITER):
-        if stream is not None:
-            batch = next(stream)
-        else:
-            batch = make_synthetic_batch(per_gpu, start_index=(it * world + rank) * per_gpu, device=c.MODEL.DEVICE)
-        trainer.run_step(batch)
-        if rank == 0 and (it % 20 == 0 or it == cfg.SOLVER.MAX_ITER - 1):
-            total = trainer.check_finite()
-            print("iter %d  total_loss %.4f  lr %.6f  %.2f s/iter" % (it, total, opt.lr, (time.time() - t0) / (it - start_iter + 1)))
-        if precise_bn and precise_bn_due(it, cfg.SOLVER.MAX_ITER, cfg.TEST.EVAL_PERIOD):
-            if bn_stream is None:
-                bn_stream = precise_bn_batches(cfg, c.MODEL.DEVICE, per_gpu, rank, world)
-            if rank == 0:
-                print("Running precise-BN for %d iterations...  Note that this could produce different statistics every time."
-                      % cfg.TEST.PRECISE_BN.NUM_ITER)
-            update_bn_stats(model, bn_stream, cfg.TEST.PRECISE_BN.NUM_ITER)
-        if (it + 1) % cfg.SOLVER.CHECKPOINT_PERIOD == 0 or it == cfg.SOLVER.MAX_ITER - 1:
-            checkpointer.save("model_%07d" % it if it < cfg.SOLVER.MAX_ITER - 1 else "model_final", iteration=it)
+    with EventStorage(start_iter) as storage:
+        for it in range(start_iter, cfg.SOLVER.MAX_ITER):
+            t_data = time.perf_counter()
+            if stream is not None:
+                batch = next(stream)
+            else:
+                batch = make_synthetic_batch(per_gpu, start_index=(it * world + rank) * per_gpu, device=c.MODEL.DEVICE)
+            trainer.data_time = time.perf_counter() - t_data
+            trainer.run_step(batch)
+            last = it == cfg.SOLVER.MAX_ITER - 1
+            if it % 20 == 0 or last:
+                # the loop's one wait for the device; the metrics of the period that ended at iteration it - 1 (or ends here)
+                # were copied to the host behind that iteration's optimizer step and are complete by now
+                if rank == 0:
+                    total = trainer.check_finite()
+                    print("iter %d  total_loss %.4f  lr %.6f  %.2f s/iter" % (it, total, opt.lr, (time.time() - t0) / (it - start_iter + 1)))
+                new = trainer.collect_metrics(storage, write=rank == 0)
+                if last:  # the rows of a period that the end of training cut short
+                    trainer.flush_metrics()
+                    new = trainer.collect_metrics(storage, write=rank == 0) or new
+                if new and writer is not None:
+                    writer.write(storage)
+            if precise_bn and precise_bn_due(it, cfg.SOLVER.MAX_ITER, cfg.TEST.EVAL_PERIOD):
+                if bn_stream is None:
+                    bn_stream = precise_bn_batches(cfg, c.MODEL.DEVICE, per_gpu, rank, world)
+                if rank == 0:
+                    print("Running precise-BN for %d iterations...  Note that this could produce different statistics every time."
+                          % cfg.TEST.PRECISE_BN.NUM_ITER)
+                update_bn_stats(model, bn_stream, cfg.TEST.PRECISE_BN.NUM_ITER)
+            if (it + 1) % cfg.SOLVER.CHECKPOINT_PERIOD == 0 or last:
+                checkpointer.save("model_%07d" % it if it < cfg.SOLVER.MAX_ITER - 1 else "model_final", iteration=it)
+    if writer is not None:
+        writer.close()
     if world > 1:
         dist.destroy_process_group()
 

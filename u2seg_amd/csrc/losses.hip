@@ -225,11 +225,64 @@ __global__ __launch_bounds__(256) void scale_to_bf16_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------------
 // Row softmax cross-entropy: logits [R][LP] bf16 (NC valid columns), labels int64; one wave per row.
 // loss_sum += sum_r (lse - z[label]);  dlogits[r][c] = (softmax - onehot) * gscale  (pad columns = 0)
+//
+// STATS (u2_softmax_ce_stats): the wave also forms pred = argmax over the NC valid columns (lowest index among equal maxima, as
+// torch.argmax documents) and counts what fast_rcnn.py:88-115 logs, counters[0..4] += rows, pred == gt, fg (0 <= gt < bg),
+// fg and pred == gt, fg and pred == bg.  The counts of the rows a wave walks stay in registers.  In the register-resident form
+// the four waves of a work-group then meet in LDS and threads 0-4 send one integer atomic each (at most 512 x 5 per launch);
+// the general form, one row per wave, sends them per wave.  The float arithmetic is that of the instantiation without STATS.
 // ------------------------------------------------------------------------------------------------
+constexpr int SC_ROWS = 0, SC_ACC = 1, SC_FG = 2, SC_FG_ACC = 3, SC_FN = 4;
+
+__device__ __forceinline__ int wave_min_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+struct CeCounts {
+  int n[5] = {0, 0, 0, 0, 0};
+  // best: the lowest column holding the row's maximum (INT_MAX when no column compared equal: a row of -inf, argmax 0)
+  __device__ __forceinline__ void add(int best, int t, int bg) {
+    const int pred = best == 0x7fffffff ? 0 : best;
+    const bool fg = t >= 0 && t < bg;
+    n[SC_ROWS] += 1;
+    n[SC_ACC] += pred == t;
+    n[SC_FG] += fg;
+    n[SC_FG_ACC] += fg && pred == t;
+    n[SC_FN] += fg && pred == bg;
+  }
+  // the four waves of a work-group meet in LDS and threads 0-4 send one atomic each: a quarter of the same-address atomics
+  // (every thread of the work-group must arrive here)
+  __device__ __forceinline__ void send_group(int* __restrict__ counters) const {
+    __shared__ int part[4][5];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane < 5) {
+      int mine = 0;
+#pragma unroll
+      for (int i = 0; i < 5; ++i) mine = lane == i ? n[i] : mine;
+      part[wv][lane] = mine;
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+      const int c = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+      if (c != 0) atomicAdd(counters + threadIdx.x, c);
+    }
+  }
+  __device__ __forceinline__ void send(int lane, int* __restrict__ counters) const {
+    int mine = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) mine = lane == i ? n[i] : mine;
+    if (lane < 5 && mine != 0) atomicAdd(counters + lane, mine);
+  }
+};
+
+template <bool STATS>
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const bf16_t* __restrict__ logits, const long long* __restrict__ labels,
                                                          bf16_t* __restrict__ dlogits, float* __restrict__ loss_sum, int R,
-                                                         int NC, int LP, float gscale) {
+                                                         int NC, int LP, float gscale, int* __restrict__ counters, int bg) {
   const int lane = threadIdx.x & 63;
+  CeCounts cnt;
   if (LP <= 1024 && (LP & 7) == 0) {
     // a wave walks rows with the grid's stride and sends ONE atomic at the end: 8192 same-address atomics (one per row) were
     // the whole 0.11 ms of this kernel
@@ -252,6 +305,17 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const bf16_t* __restric
       }
     }
     mx = wave_max(mx);
+    int best = 0x7fffffff;
+    if constexpr (STATS) {
+#pragma unroll
+      for (int it = 1; it >= 0; --it)
+#pragma unroll
+        for (int e = 7; e >= 0; --e) {
+          const int c = (it * 64 + lane) * 8 + e;
+          if (c < NC && v[it][e] == mx) best = c;  // (walked downwards: the lane's lowest such column stays)
+        }
+      best = wave_min_int(best);
+    }
     float se = 0.f;
 #pragma unroll
     for (int it = 0; it < 2; ++it)
@@ -278,8 +342,10 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const bf16_t* __restric
       }
     }
     loss_acc += mx + __logf(se) - bf2f(zr[t]);
+    if constexpr (STATS) cnt.add(best, t, bg);
     }
     if (lane == 0 && loss_acc != 0.f) atomicAdd(loss_sum, loss_acc);
+    if constexpr (STATS) cnt.send_group(counters);
     return;
   }
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -288,6 +354,12 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const bf16_t* __restric
   float mx = -INFINITY;
   for (int c = lane; c < NC; c += 64) mx = fmaxf(mx, bf2f(zr[c]));
   mx = wave_max(mx);
+  int best = 0x7fffffff;
+  if constexpr (STATS) {
+    for (int c = lane; c < NC && best == 0x7fffffff; c += 64)
+      if (bf2f(zr[c]) == mx) best = c;
+    best = wave_min_int(best);
+  }
   float se = 0.f;
   for (int c = lane; c < NC; c += 64) se += __expf(bf2f(zr[c]) - mx);
   se = wave_sum(se);
@@ -300,21 +372,34 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const bf16_t* __restric
     dr[c] = f2bf(g);
   }
   if (lane == 0) atomicAdd(loss_sum, mx + __logf(se) - bf2f(zr[t]));
+  if constexpr (STATS) {
+    cnt.add(best, t, bg);
+    cnt.send(lane, counters);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
 // Mask head: logit[n][p] = x[n][p][:] . Wp[cls_n][:] + bp[cls_n] (rounded to bf16 like the autocast conv),
 // loss_sum += BCEwithLogits(logit, target);  dx = dlogit * Wp[cls];  dWp[cls] += sum_p dlogit x;  dbp[cls] += sum dlogit
 // x: [N][P][C] bf16 (C = 256), target uint8 [N][P].  One workgroup per ROI, one wave per position.
+//
+// STATS (u2_mask_predict_bce_stats, the loss-only form): what mask_head.py:90-102 logs, from the rounded logit z and the target
+// t of every position: incorrect = (z > 0) != (t != 0); counters[0..3] += incorrect & !t, incorrect & t, t != 0, 1.  A wave keeps
+// its counts in registers, the four waves meet in four more columns of red[][] (integers, bit-cast), and threads 0-3 send one
+// integer atomic each per work-group.
 // ------------------------------------------------------------------------------------------------
+constexpr int MC_FALSE_POS = 0, MC_FALSE_NEG = 1, MC_POS = 2, MC_TOTAL = 3;
+
+template <bool STATS>
 __global__ __launch_bounds__(256) void mask_predict_bce_kernel(const bf16_t* __restrict__ x, const float* __restrict__ Wp,
                                                                const float* __restrict__ bp, const long long* __restrict__ cls,
                                                                const uint8_t* __restrict__ target, bf16_t* __restrict__ dx,
                                                                float* __restrict__ dWp, float* __restrict__ dbp,
                                                                float* __restrict__ loss_sum, bf16_t* __restrict__ logit_out,
                                                                int P, int C, float gscale, int phased_side,
-                                                               const float* __restrict__ gmul) {
-  __shared__ float red[4][260];
+                                                               const float* __restrict__ gmul, int* __restrict__ counters) {
+  __shared__ float red[4][STATS ? 264 : 260];
+  int mc[4] = {0, 0, 0, 0};
   const int n = blockIdx.x;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int k = (int)cls[n];
@@ -348,6 +433,13 @@ __global__ __launch_bounds__(256) void mask_predict_bce_kernel(const bf16_t* __r
     const float t = (float)target[(size_t)n * P + o];
     // max(z,0) - z*t + log1p(exp(-|z|))
     ls += fmaxf(z, 0.f) - z * t + log1pf(__expf(-fabsf(z)));
+    if constexpr (STATS) {
+      const bool on = t != 0.f, wrong = (z > 0.f) != on;
+      mc[MC_FALSE_POS] += wrong && !on;
+      mc[MC_FALSE_NEG] += wrong && on;
+      mc[MC_POS] += on;
+      mc[MC_TOTAL] += 1;
+    }
     const float sg = 1.f / (1.f + __expf(-z));
     const float g = (sg - t) * gscale;
     bf16_t ov[4];
@@ -363,6 +455,12 @@ __global__ __launch_bounds__(256) void mask_predict_bce_kernel(const bf16_t* __r
 #pragma unroll
   for (int e = 0; e < 4; ++e) red[wv][lane * 4 + e] = dw[e];
   if (lane == 0) { red[wv][256] = db; red[wv][257] = ls; }
+  if constexpr (STATS) {
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[wv][260 + i] = __int_as_float(mc[i]);
+    }
+  }
   __syncthreads();
   const int t = threadIdx.x;
   const float s = red[0][t] + red[1][t] + red[2][t] + red[3][t];
@@ -370,6 +468,62 @@ __global__ __launch_bounds__(256) void mask_predict_bce_kernel(const bf16_t* __r
   if (t == 0) {
     if (dbp) atomicAdd(dbp + k, red[0][256] + red[1][256] + red[2][256] + red[3][256]);
     if (loss_sum) atomicAdd(loss_sum, red[0][257] + red[1][257] + red[2][257] + red[3][257]);
+  }
+  if constexpr (STATS) {
+    if (t < 4) {
+      const int c = __float_as_int(red[0][260 + t]) + __float_as_int(red[1][260 + t]) + __float_as_int(red[2][260 + t]) +
+                    __float_as_int(red[3][260 + t]);
+      if (c != 0) atomicAdd(counters + t, c);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// counters[0] += #(labels == 1), counters[1] += #(labels == 0) over n int8 labels (the RPN's subsampled anchor labels,
+// rpn.py:396-403).  16 labels per load where the address allows it, a work-group's counts meet in LDS, two integer atomics
+// per work-group.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void count_labels_i8_kernel(const int8_t* __restrict__ labels, long long n,
+                                                              int* __restrict__ counters) {
+  __shared__ int red[2][4];
+  // [0, head): bytes in front of the first 16-byte boundary; [head, head + 16 * nvec): whole vectors; the rest: the tail
+  long long head = (long long)((16 - (reinterpret_cast<uintptr_t>(labels) & 15)) & 15);
+  if (head > n) head = n;
+  const long long nvec = (n - head) >> 4;
+  const uint4* vec = reinterpret_cast<const uint4*>(labels + head);
+  int ones = 0, zeros = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
+    const uint4 q = vec[i];
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const unsigned v = (w[k] >> (8 * b)) & 0xffu;
+        ones += v == 1u;
+        zeros += v == 0u;
+      }
+  }
+  if (blockIdx.x == 0) {  // head and tail: fewer than 32 labels
+    const long long tail0 = head + (nvec << 4);
+    const long long rest = head + (n - tail0);
+    for (long long i = threadIdx.x; i < rest; i += 256) {
+      const int8_t v = labels[i < head ? i : tail0 + (i - head)];
+      ones += v == 1;
+      zeros += v == 0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ones += __shfl_xor(ones, o, 64);
+    zeros += __shfl_xor(zeros, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) { red[0][wv] = ones; red[1][wv] = zeros; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int c = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    if (c != 0) atomicAdd(counters + threadIdx.x, c);
   }
 }
 
@@ -513,8 +667,20 @@ extern "C" int u2_softmax_ce(const void* logits, const void* labels, void* dlogi
   if (R <= 0) return 0;
   int grid = (R + 3) / 4;
   if (LP <= 1024 && (LP & 7) == 0 && grid > 512) grid = 512;  // the register-resident form loops over rows
-  hipLaunchKernelGGL(softmax_ce_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits,
-                     (const long long*)labels, (bf16_t*)dlogits, loss_sum, R, NC, LP, gscale);
+  hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits,
+                     (const long long*)labels, (bf16_t*)dlogits, loss_sum, R, NC, LP, gscale, (int*)nullptr, 0);
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int u2_softmax_ce_stats(const void* logits, const void* labels, void* dlogits, float* loss_sum, int R, int NC,
+                                   int LP, float gscale, int* counters, int bg_label, void* stream) {
+  if (!counters) return -1;
+  if (R <= 0) return 0;  // (nothing is added: a launch without rows leaves its counter slice untouched)
+  int grid = (R + 3) / 4;
+  if (LP <= 1024 && (LP & 7) == 0 && grid > 512) grid = 512;
+  hipLaunchKernelGGL(softmax_ce_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits,
+                     (const long long*)labels, (bf16_t*)dlogits, loss_sum, R, NC, LP, gscale, counters, bg_label);
   U2_CHECK_LAUNCH();
   return 0;
 }
@@ -526,9 +692,31 @@ extern "C" int u2_mask_predict_bce(const void* x, const float* Wp, const float* 
   if (N <= 0) return 0;
   // 8 slices: 0.184 -> 0.074 ms per launch at N = 260, P = 784; 24 slices measure 0.081 (256 more atomics per work-group)
   const int slices = P >= 512 ? 8 : (P >= 128 ? 4 : 1);
-  hipLaunchKernelGGL(mask_predict_bce_kernel, dim3(N, slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, Wp, bp,
-                     (const long long*)cls, (const uint8_t*)target, (bf16_t*)dx, dWp, dbp, loss_sum, (bf16_t*)logit_out,
-                     P, C, gscale, phased_side, gmul);
+  hipLaunchKernelGGL(mask_predict_bce_kernel<false>, dim3(N, slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, Wp,
+                     bp, (const long long*)cls, (const uint8_t*)target, (bf16_t*)dx, dWp, dbp, loss_sum, (bf16_t*)logit_out,
+                     P, C, gscale, phased_side, gmul, (int*)nullptr);
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int u2_mask_predict_bce_stats(const void* x, const float* Wp, const float* bp, const void* cls, const void* target,
+                                         float* loss_sum, int* counters, int N, int P, int C, int phased_side, void* stream) {
+  if (!counters || C != 256 || (phased_side && ((phased_side & 1) || phased_side * phased_side != P))) return -1;
+  if (N <= 0) return 0;
+  const int slices = P >= 512 ? 8 : (P >= 128 ? 4 : 1);  // (the launch shape of u2_mask_predict_bce)
+  hipLaunchKernelGGL(mask_predict_bce_kernel<true>, dim3(N, slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, Wp,
+                     bp, (const long long*)cls, (const uint8_t*)target, (bf16_t*)nullptr, (float*)nullptr, (float*)nullptr,
+                     loss_sum, (bf16_t*)nullptr, P, C, 0.f, phased_side, (const float*)nullptr, counters);
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int u2_count_labels_i8(const void* labels, long long n, int* counters, void* stream) {
+  if (!counters) return -1;
+  if (n <= 0) return 0;
+  long long g = ((n >> 4) + 255) / 256;
+  g = g < 1 ? 1 : (g > 1024 ? 1024 : g);
+  hipLaunchKernelGGL(count_labels_i8_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, (const int8_t*)labels, n, counters);
   U2_CHECK_LAUNCH();
   return 0;
 }

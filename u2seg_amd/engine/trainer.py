@@ -10,6 +10,7 @@ import torch
 import torch.distributed as dist
 
 from ..layers import functional as F
+from ..utils.events import get_event_storage, has_event_storage
 
 
 def launch_info():
@@ -22,6 +23,11 @@ class SimpleTrainer:
         self.model, self.optimizer, self.scheduler = model, optimizer, scheduler
         self.iter = 0
         self.last_losses = None
+        # metrics (engine/metrics.py): only inside an EventStorage; `data_time` is set by the loop that fetches the batches
+        self.metrics = None
+        self.metrics_period = None
+        self.data_time = 0.0
+        self._clock = None
         # gradient exchange overlapped with backward: the model calls this when the gradients of the FPN outputs exist,
         # i.e. when every head parameter's gradient is final (the heads come after the backbone in the arena)
         heads = [m for name, m in model.named_children() if name != "backbone"]
@@ -34,22 +40,57 @@ class SimpleTrainer:
 
     def run_step(self, batched_inputs):
         assert self.model.training, "[SimpleTrainer] model was changed to eval mode!"
+        storage = get_event_storage() if has_event_storage() else None
+        if storage is not None:
+            step_time = self._begin_metrics(storage, batched_inputs)
         self.optimizer.zero_grad()
         loss_dict = self.model(batched_inputs)
         # train_loop.py:491 sums the dict; here one stack + one sum instead of a chain of len - 1 scalar adds (and no kernels in
         # backward: the gradient of every entry is a view of the same 1.0)
         vals = list(loss_dict.values())
-        losses = torch.stack(vals).sum() if len(vals) > 1 and all(v.dim() == 0 and v.dtype == vals[0].dtype for v in vals) \
-            else sum(vals)
+        stacked = torch.stack(vals) if len(vals) > 1 and all(v.dim() == 0 and v.dtype == vals[0].dtype for v in vals) else None
+        losses = stacked.sum() if stacked is not None else sum(vals)
         losses.backward()
         F.assert_no_deferred_gradients()
         grad_scale = self.optimizer.all_reduce_grads()
         self.optimizer.step(grad_scale)
+        if storage is not None:
+            # behind the optimizer step; the learning rate is the one this step was taken with
+            if stacked is None:
+                stacked = torch.stack([v.detach().float().reshape(()) for v in vals])
+            self.metrics.end_step(storage, stacked, list(loss_dict.keys()), storage.iter, float(getattr(self.optimizer, "lr", 0.0)),
+                                  step_time, self.data_time, len(batched_inputs))
+            storage.step()
         if self.scheduler is not None:
             self.scheduler.step()
         self.iter += 1
         self.last_losses = loss_dict
         return loss_dict
+
+    # ---- metrics: device counters and loss rows, read once per period (engine/metrics.py) ----
+    def _begin_metrics(self, storage, batched_inputs):
+        from .metrics import PERIOD, MetricsRing, StepClock
+
+        if self.metrics is None:
+            device = next(self.model.parameters()).device
+            self.metrics = MetricsRing(device, self.metrics_period or PERIOD)
+            self._clock = StepClock()
+        self.metrics.begin_step(storage, storage.iter)
+        return self._clock.lap()
+
+    def flush_metrics(self):
+        """Starts the read-out of a period that the last iteration left unfinished (no wait)."""
+        if self.metrics is not None:
+            self.metrics.start_readout(launch_info()[2] if dist.is_available() and dist.is_initialized() else 1)
+
+    def collect_metrics(self, storage=None, write=True):
+        """Waits for a started read-out (the one wait on behalf of the metrics) and puts its scalars into the storage; call it
+        where the loop waits for the device anyway.  False when no read-out was started since the last call."""
+        if self.metrics is None:
+            return False
+        storage = get_event_storage() if storage is None else storage
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        return self.metrics.collect(storage, write=write, world_size=world)
 
     def check_finite(self):
         """train_loop.py:411-415 raises on non-finite total loss; call off the critical path."""

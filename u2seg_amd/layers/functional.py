@@ -1057,23 +1057,37 @@ class _SoftmaxCEFn(Function):
     """cross_entropy(scores, labels, reduction='mean') (roi_heads/fast_rcnn.py:344)."""
 
     @staticmethod
-    def forward(ctx, logits, labels, num_classes):
+    def forward(ctx, logits, labels, num_classes, counters=None):
         r, lp = logits.shape
         d = torch.empty_like(logits)
         loss = zeros_f32((1,), logits.device)
-        _hip.call("u2_softmax_ce", logits.contiguous(), labels.contiguous(), d, loss, r, num_classes, lp,
-                  1.0 / max(r, 1))
+        if counters is None:
+            _hip.call("u2_softmax_ce", logits.contiguous(), labels.contiguous(), d, loss, r, num_classes, lp,
+                      1.0 / max(r, 1))
+        else:  # the same kernel body, which also counts fast_rcnn.py:88-115 into counters[0..4] (background = the last class)
+            _check_counters(counters, 5, logits.device)
+            _hip.call("u2_softmax_ce_stats", logits.contiguous(), labels.contiguous(), d, loss, r, num_classes, lp,
+                      1.0 / max(r, 1), counters, num_classes - 1)
         ctx.save_for_backward(d)
         return loss[0] / max(r, 1)
 
     @staticmethod
     def backward(ctx, g):
         (d,) = ctx.saved_tensors
-        return d * g, None, None   # g: 0-dim fp32, the product keeps d's dtype (one launch)
+        return d * g, None, None, None   # g: 0-dim fp32, the product keeps d's dtype (one launch)
 
 
-def softmax_cross_entropy(logits, labels, num_classes):
-    return _SoftmaxCEFn.apply(logits, labels, num_classes)
+def _check_counters(counters, n, device):
+    assert counters.dtype == torch.int32 and counters.is_contiguous() and counters.numel() >= n and counters.device == device, (
+        "expected >= %d contiguous int32 counters on %s" % (n, device))
+
+
+def softmax_cross_entropy(logits, labels, num_classes, counters=None):
+    """counters (int32 [>= 5], optional): rows, pred == gt, fg, fg and pred == gt, fg and pred == background are ADDED to it
+    (u2_softmax_ce_stats); the loss and its gradient do not depend on it."""
+    if counters is None:
+        return _SoftmaxCEFn.apply(logits, labels, num_classes)
+    return _SoftmaxCEFn.apply(logits, labels, num_classes, counters)
 
 
 class _BoxRegL1Fn(Function):
@@ -1105,7 +1119,7 @@ class _MaskPredictBCEFn(Function):
     (roi_heads/mask_head.py:258 + :33-112)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, classes, target_u8, phased=False):
+    def forward(ctx, x, weight, bias, classes, target_u8, phased=False, counters=None):
         n, ph, pw, c = x.shape
         if phased:  # x = the deconvolution's unshuffled phases [n, P, P, 4 C]: the kernel reads (and writes dx) in place
             ph, pw, c = 2 * ph, 2 * pw, c // 4
@@ -1118,8 +1132,12 @@ class _MaskPredictBCEFn(Function):
         denom = float(max(n * p, 1))
         # the loss alone here; the gradients come from a second launch in backward, scaled by the loss's upstream gradient inside
         # the kernel (forming dx here and multiplying it by that scalar in backward was a 0.2 ms pass over dx per step)
-        _hip.call("u2_mask_predict_bce", x, w2, b2, classes, target_u8, None, None, None, loss, None, n, p, c, 1.0 / denom,
-                  ph if phased else 0, None)
+        if counters is None:
+            _hip.call("u2_mask_predict_bce", x, w2, b2, classes, target_u8, None, None, None, loss, None, n, p, c, 1.0 / denom,
+                      ph if phased else 0, None)
+        else:  # the same loss, and mask_head.py:90-102's counts into counters[0..3]
+            _check_counters(counters, 4, x.device)
+            _hip.call("u2_mask_predict_bce_stats", x, w2, b2, classes, target_u8, loss, counters, n, p, c, ph if phased else 0)
         ctx.save_for_backward(x, w2, b2, classes, target_u8)
         ctx.cfg = (n, p, c, k, denom, ph if phased else 0, weight.shape)
         return loss[0] / denom
@@ -1132,11 +1150,22 @@ class _MaskPredictBCEFn(Function):
         dw, db = zeros_f32((k, c), x.device), zeros_f32((k,), x.device)
         _hip.call("u2_mask_predict_bce", x, w2, b2, classes, target_u8, dx, dw, db, None, None, n, p, c, 1.0 / denom, phased_side,
                   g.detach().float().reshape(1).contiguous())
-        return dx, dw.view(wshape), db, None, None, None
+        return dx, dw.view(wshape), db, None, None, None, None
 
 
-def mask_predict_bce_loss(x, weight, bias, classes, target_u8, phased=False):
-    return _MaskPredictBCEFn.apply(x, weight, bias, classes, target_u8, phased)
+def mask_predict_bce_loss(x, weight, bias, classes, target_u8, phased=False, counters=None):
+    """counters (int32 [>= 4], optional): false positives, false negatives, positives and positions are ADDED to it
+    (u2_mask_predict_bce_stats)."""
+    if counters is None:
+        return _MaskPredictBCEFn.apply(x, weight, bias, classes, target_u8, phased)
+    return _MaskPredictBCEFn.apply(x, weight, bias, classes, target_u8, phased, counters)
+
+
+def count_labels_i8(labels, counters):
+    """counters[0] += #(labels == 1), counters[1] += #(labels == 0) over an int8 tensor (the RPN's subsampled anchor labels)."""
+    assert labels.dtype == torch.int8 and labels.is_contiguous()
+    _check_counters(counters, 2, labels.device)
+    _hip.call("u2_count_labels_i8", labels, labels.numel(), counters)
 
 
 def mask_predict_prob(x, weight, bias, classes, phased=False):

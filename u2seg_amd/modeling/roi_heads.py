@@ -3,6 +3,7 @@ three-stage cascade (detectron2/modeling/poolers.py:23-263, roi_heads/box_head.p
 roi_heads/fast_rcnn.py:46-569, roi_heads/mask_head.py:33-298, roi_heads/roi_heads.py:46-846,
 roi_heads/cascade_rcnn.py:20-299).  Per-image Python loops remain only for the index bookkeeping the
 reference also does per image; all arithmetic on features runs in the HIP kernels."""
+import contextlib
 import math
 
 import os
@@ -14,6 +15,10 @@ from ..config import configurable
 from ..layers import Conv2d, ConvTranspose2d, Linear, ShapeSpec, c2_msra_fill, c2_xavier_fill
 from ..layers import functional as F
 from ..structures import BitMasks, Boxes, Instances
+from ..utils.events import MASK_SLOT as _MASK_SLOT
+from ..utils.events import get_event_storage, has_event_storage
+from ..utils.events import stage_counters as _stage_counters
+from ..utils.events import step_counters as _step_counters
 from ..utils.registry import Registry
 from .batched import BatchList, PaddedTargets, check_finite, device_constant, device_upload, image_index, proposals_from_list
 from .sampling import subsample_labels
@@ -170,7 +175,7 @@ class FastRCNNOutputLayers(nn.Module):
         if r == 0:
             z = scores.float().sum() * 0.0
             return {"loss_cls": z, "loss_box_reg": deltas.float().sum() * 0.0}
-        loss_cls = F.softmax_cross_entropy(scores, gt_classes, self.num_classes + 1)
+        loss_cls = F.softmax_cross_entropy(scores, gt_classes, self.num_classes + 1, _stage_counters())
         loss_box = F.box_reg_l1_loss(deltas, proposal_boxes, gt_boxes, gt_classes, self.num_classes,
                                      self.box2box_weights, max(r, 1.0))
         losses = {"loss_cls": loss_cls, "loss_box_reg": loss_box}
@@ -263,7 +268,9 @@ class MaskRCNNConvUpsampleHead(nn.Module):
                                          side).to(torch.uint8)
         if self.num_classes == 1:
             gt_classes = torch.zeros_like(gt_classes)
-        return F.mask_predict_bce_loss(x, self.predictor.weight, self.predictor.bias, gt_classes, gt_masks, phased)
+        counters = _step_counters()
+        return F.mask_predict_bce_loss(x, self.predictor.weight, self.predictor.bias, gt_classes, gt_masks, phased,
+                                       None if counters is None else counters[_MASK_SLOT:_MASK_SLOT + 4])
 
     def mask_inference(self, x, pred_instances, phased=False):
         """mask_rcnn_inference (mask_head.py:115-158): sigmoid of the predicted-class channel.  x: the trunk output
@@ -660,8 +667,11 @@ class CascadeROIHeads(StandardROIHeads):
         if self.training:
             losses = {}
             F.issue_deferred_piece()
+            storage = get_event_storage() if has_event_storage() else None
             for stage, (predictor, predictions, props) in enumerate(head_outputs):
-                stage_losses = predictor.losses(predictions, props)
+                # cascade_rcnn.py:180-184: the stage's statistics are named stage{k}/...; the scope also selects its counters
+                with storage.name_scope("stage{}".format(stage)) if storage is not None else contextlib.nullcontext():
+                    stage_losses = predictor.losses(predictions, props)
                 losses.update({k + "_stage{}".format(stage): v for k, v in stage_losses.items()})
             return losses
         from .inference import fast_rcnn_inference

@@ -14,6 +14,7 @@ from ..config import configurable
 from ..layers import Conv2d
 from ..layers import functional as F
 from ..structures import Boxes, Instances
+from ..utils.events import RPN_SLOT, step_counters
 from ..utils.registry import Registry
 from .batched import LazyProposals, PaddedTargets, device_constant
 from .sampling import subsample_labels
@@ -279,6 +280,9 @@ class RPN(nn.Module):
     def losses(self, anchors_per_level, objs, dlts, labels, match, gt_boxes_pad):
         b = labels.shape[0]
         normalizer = self.batch_size_per_image * b
+        counters = step_counters()
+        if counters is not None:  # rpn.py:396-403: the subsampled positives / negatives, counted on the device
+            F.count_labels_i8(labels.contiguous(), counters[RPN_SLOT:RPN_SLOT + 2])
         loss_cls, loss_loc = F.rpn_losses(labels, match, gt_boxes_pad, anchors_per_level, self.rpn_head.num_anchors,
                                           normalizer, objs, dlts)
         losses = {"loss_rpn_cls": loss_cls, "loss_rpn_loc": loss_loc}
