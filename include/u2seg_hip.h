@@ -466,6 +466,20 @@ int u2_mask_planes_from_counts(const long long* cum, const long long* offs, void
 typedef struct U2PairImage { long long dt_offset, gt_offset, out_offset; int D, G, H, W, dt_first, pad_; } U2PairImage;
 int u2_mask_pair_counts(const void* dt_planes, const void* gt_planes, const int* dt_boxes, int* inter,
                         const U2PairImage* images, int num_images, void* stream);
+/* Ground truth: polygon annotations -> planes (polygon.hip), bit for bit data/polygon.py's
+ * polygons_to_bitmask: cocoapi's rleFrPoly per polygon, the union over an annotation's polygons.  xy: device float64, the
+ * vertices x0, y0, x1, y1, ... of all polygons; |5 x + .5| must stay below 2^31 (the caller checks).  poly_offs [P + 1]: device,
+ * index of every polygon's first vertex; a polygon has at least one vertex.  masks: a HOST array, one entry per output mask:
+ * its plane of W * ceil(H / 64) words at word plane_offset of `planes`, its polygons [first_poly, first_poly + num_polys).
+ * Every word of every addressed plane is written, padding included (num_polys == 0: zeros); masks with H or W == 0 are skipped
+ * and their area entry is left alone.  area [num_masks] (optional) = set pixels.  H * W < 2^31.  scratch: device words for the
+ * toggle planes of every polygon after a mask's first (the first uses the mask's own plane): at least
+ * u2_mask_polygon_scratch_words(masks, num_masks) = sum of (num_polys - 1) * W * ceil(H / 64) over the masks with num_polys > 1;
+ * may be NULL when that is 0.  Integer XOR atomics and plain stores only: the result does not depend on any order. */
+typedef struct U2PolyMask { int H, W; long long plane_offset; int first_poly, num_polys; } U2PolyMask;
+long long u2_mask_polygon_scratch_words(const U2PolyMask* masks, int num_masks);
+int u2_mask_planes_from_polygons(const double* xy, const long long* poly_offs, const U2PolyMask* masks, int num_masks,
+                                 void* planes, int* area, void* scratch, long long scratch_words, void* stream);
 
 /* ---- panoptic quality (panopticeval.hip): evaluation/panoptic_ops.py, DESIGN.md section 12 ------------------------------------
  * The joint histogram PQ is computed from: for every image of the HOST array, counts[(G + 2)][P] = pixels shared by a

@@ -7,7 +7,7 @@ import torch
 from PIL import Image
 
 from ..structures import BitMasks, Boxes, Instances
-from . import rle
+from . import polygon, rle
 from . import transforms as T
 
 _EXIF_ORIENT = 274  # exif 'Orientation' tag
@@ -116,7 +116,8 @@ def transform_instance_annotations(annotation, transforms, image_size):
 
 
 def annotations_to_instances(annos, image_size, mask_format="polygon"):
-    """detection_utils.py:382-455 for the bitmask format the U2Seg configs use."""
+    """detection_utils.py:382-455 for the bitmask format the U2Seg configs use; a polygon-list segmentation is rasterised
+    there as the reference does (polygons_to_bitmask, here data/polygon.py)."""
     boxes = (np.stack([BoxMode.convert(obj["bbox"], obj["bbox_mode"], BoxMode.XYXY_ABS) for obj in annos])
              if len(annos) else np.zeros((0, 4)))
     target = Instances(image_size)
@@ -124,13 +125,15 @@ def annotations_to_instances(annos, image_size, mask_format="polygon"):
     target.gt_classes = torch.tensor([int(obj["category_id"]) for obj in annos], dtype=torch.int64)
     if len(annos) and "segmentation" in annos[0]:
         if mask_format != "bitmask":
-            raise NotImplementedError("INPUT.MASK_FORMAT '%s': the U2Seg configs use 'bitmask' (RLE pseudo-labels); polygon "
-                                      "rasterisation needs pycocotools" % mask_format)
+            raise NotImplementedError("INPUT.MASK_FORMAT '%s': the U2Seg configs use 'bitmask' (RLE pseudo-labels); PolygonMasks "
+                                      "and their per-ROI rasterisation in the mask loss are not part of this project" % mask_format)
         out = torch.empty((len(annos),) + tuple(image_size), dtype=torch.bool)
         view = out.numpy()  # written in place: one pass per mask, whatever its strides (flipped views, Fortran order)
         for i, obj in enumerate(annos):
             segm = obj["segmentation"]
-            if isinstance(segm, dict):
+            if isinstance(segm, list):
+                segm = polygon.polygons_to_bitmask(segm, *image_size)
+            elif isinstance(segm, dict):
                 segm = rle.decode(segm)
             elif not isinstance(segm, np.ndarray):
                 raise ValueError("Cannot convert segmentation of type '{}' to BitMasks!".format(type(segm)))

@@ -8,7 +8,10 @@ unmapped clusters are dropped, category ids go back to dataset ids, the results 
 evaluation/cocoeval.py (box AP / AR without pycocotools; its matching and accumulation are pinned to the reference's C++
 evaluation core).  With "segm" among the tasks the same core also scores the masks (mask AP; the reference's evaluator skips
 that task, :352-354, but carries the code for it, :672-679): process() collects, per image, the pixel counts mask IoU needs
-(evaluation/mask_ops.py, on the device when the predictions are there), evaluate() turns them into IoU tables."""
+(evaluation/mask_ops.py, on the device when the predictions are there), evaluate() turns them into IoU tables.  Ground truth
+stored as polygons (COCO's instances_val2017.json: every non-crowd instance) is refused by default and, with
+gt_polygons="rasterize", rasterised by data/polygon.py's restatement of cocoapi's conversion - on the device next to the
+predictions' planes (csrc/polygon.hip), by the definition itself on a CPU-only evaluator."""
 import itertools
 import json
 import os
@@ -51,9 +54,12 @@ def instances_to_coco_json(instances, img_id, rles=None):
 
 class COCOEvaluator(DatasetEvaluator):
     def __init__(self, dataset_name, output_dir=None, *, mode="hungarian_matching",
-                 mapping_path="./hungarian_matching/instance_mapping.json", tasks=("bbox",)):
+                 mapping_path="./hungarian_matching/instance_mapping.json", tasks=("bbox",), gt_polygons="refuse"):
         self._metadata = MetadataCatalog.get(dataset_name)
         self._tasks = tuple(tasks)
+        if gt_polygons not in ("refuse", "rasterize"):
+            raise ValueError('gt_polygons must be "refuse" or "rasterize", got %r' % (gt_polygons,))
+        self._gt_polygons = gt_polygons
         if "bbox" not in self._tasks or set(self._tasks) - {"bbox", "segm"}:
             raise ValueError('tasks must be ("bbox",) or ("bbox", "segm"), got %r' % (tasks,))
         self._output_dir = output_dir
@@ -69,7 +75,9 @@ class COCOEvaluator(DatasetEvaluator):
                 if ann.get("segmentation") is None:
                     raise ValueError("annotation %s of %s has no segmentation: mask AP needs RLE ground truth"
                                      % (ann.get("id"), dataset_name))
-                if mask_ops.is_polygon(ann["segmentation"]):
+                if mask_ops.is_polygon(ann["segmentation"]) and gt_polygons == "rasterize":
+                    mask_ops.gt_polygons(ann)  # the json is read as it is: every polygon of k >= 1 points is rasterised
+                elif mask_ops.is_polygon(ann["segmentation"]):
                     raise NotImplementedError(
                         "annotation %s of %s has a polygon segmentation: mask AP needs RLE ground truth, polygons are not "
                         "supported (no polygon rasteriser in this project)" % (ann.get("id"), dataset_name))
@@ -89,14 +97,16 @@ class COCOEvaluator(DatasetEvaluator):
             sel = [k for k in work if items[k][1].pred_masks.is_cuda == on_gpu]
             if not sel:
                 continue
-            gts = None
-            if pairs:
+            gts = anns = None
+            if pairs and self._gt_polygons == "rasterize":
+                anns = [self._img_to_anns.get(items[k][0]["image_id"], []) for k in sel]
+            elif pairs:
                 gts = []
                 for k in sel:
                     inp, inst = items[k]
                     h, w = (int(v) for v in inst.pred_masks.shape[1:])
                     gts.append([mask_ops.gt_counts(a, h, w, inp["image_id"]) for a in self._img_to_anns.get(inp["image_id"], [])])
-            for k, res in zip(sel, mask_ops.mask_batch_any([items[k][1].pred_masks for k in sel], gts)):
+            for k, res in zip(sel, mask_ops.mask_batch_any([items[k][1].pred_masks for k in sel], gts, gt=anns)):
                 done[k] = res
         for k, (inp, inst) in enumerate(items):
             res = done.get(k)
@@ -108,8 +118,8 @@ class COCOEvaluator(DatasetEvaluator):
             if pairs and res is not None:
                 anns = self._img_to_anns.get(inp["image_id"], [])
                 h, w = (int(v) for v in items[k][1].pred_masks.shape[1:])
-                pred["segm_pairs"] = {"gt_ids": [a["id"] for a in anns], "inter": res["inter"], "area_dt": res["area"],
-                                      "area_gt": np.array([rle.area(a["segmentation"]) for a in anns], dtype=np.int64)}
+                area_gt = res["area_gt"] if "area_gt" in res else np.array([rle.area(a["segmentation"]) for a in anns], dtype=np.int64)
+                pred["segm_pairs"] = {"gt_ids": [a["id"] for a in anns], "inter": res["inter"], "area_dt": res["area"], "area_gt": area_gt}
             self._predictions.append(pred)
 
     def cluster_mapping(self, coco_results, num_clusters=NUM_EVAL_CLUSTERS):
@@ -175,7 +185,8 @@ class COCOEvaluator(DatasetEvaluator):
                 sp = p["segm_pairs"]
                 pair_counts[p["image_id"]] = {"gt_ids": sp["gt_ids"], "inter": np.asarray(sp["inter"])[rows],
                                               "area_dt": np.asarray(sp["area_dt"])[rows], "area_gt": sp["area_gt"]}
-        return self._metrics(coco_results, lambda ds, rs: cocoeval.evaluate_segm(ds, rs, pair_counts=pair_counts))
+        polygons = self._gt_polygons == "rasterize"
+        return self._metrics(coco_results, lambda ds, rs: cocoeval.evaluate_segm(ds, rs, pair_counts=pair_counts, polygons=polygons))
 
     def _box_metrics(self, coco_results):
         """AP, AP50, AP75, APs, APm, APl (x 100, NaN where undefined) and the per-category APs, as _derive_coco_results

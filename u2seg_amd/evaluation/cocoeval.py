@@ -210,10 +210,11 @@ def mask_ious(inter, area_dt, area_gt, gt_crowd):
     return np.where(union > 0, inter.astype(np.float64) / np.maximum(union, 1).astype(np.float64), 0.0)
 
 
-def host_pair_counts(gt_dataset, results, img_ids):
+def host_pair_counts(gt_dataset, results, img_ids, polygons=False):
     """The pair counts `evaluate_segm` takes, computed on the host from the RLEs of the results and of the ground truth:
     {image id: {"gt_ids": [annotation ids], "inter": int64 [D, G], "area_dt": [D], "area_gt": [G]}}, the D rows in the order
-    of that image's entries in `results`, the G columns over all of the image's annotations."""
+    of that image's entries in `results`, the G columns over all of the image's annotations.  polygons=True: ground truth
+    stored as polygon lists is rasterised (data/polygon.py) instead of refused; area_gt is the rasterised area."""
     from ..data import rle
     from . import mask_ops
 
@@ -233,22 +234,23 @@ def host_pair_counts(gt_dataset, results, img_ids):
                 raise ValueError("image %s: predicted masks of different sizes" % img)
         masks = np.stack([rle.decode(r["segmentation"]) for r in rs]) if rs else np.zeros((0, h, w), dtype=np.uint8)
         gts = anns.get(img, [])
-        inter, area_dt, area_gt = mask_ops.mask_pair_counts(masks, gts, h, w)
+        inter, area_dt, area_gt = mask_ops.mask_pair_counts(masks, gts, h, w, polygons=polygons)
         out[img] = {"gt_ids": [a["id"] for a in gts], "inter": inter, "area_dt": area_dt, "area_gt": area_gt}
     return out
 
 
-def evaluate_segm(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100), pair_counts=None):
+def evaluate_segm(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100), pair_counts=None, polygons=False):
     """Mask AP / AR: `evaluate_bbox` with two differences (the reference's _evaluate_predictions_on_coco with iou_type "segm",
     coco_evaluation.py:672-679, drops "bbox" from the results for the first): a detection's area is its mask area (the
     ground truth keeps ann["area"]), and the IoU tables come from masks.  results: COCO result dicts with an RLE
     "segmentation".  pair_counts: what `host_pair_counts` returns, collected elsewhere (the evaluator does it per batch on the
-    device); None: computed here.  Returns evaluate_bbox's dict plus "ious" {(image, category): [D', G]}."""
+    device); None: computed here, with `polygons` as in `host_pair_counts`.  Returns evaluate_bbox's dict plus "ious"
+    {(image, category): [D', G]}."""
     imgs = sorted(im["id"] for im in gt_dataset["images"]) if img_ids is None else sorted(set(img_ids))
     cats = sorted(c["id"] for c in gt_dataset["categories"])
     params = Params(imgs, cats, max_dets)
     if pair_counts is None:
-        pair_counts = host_pair_counts(gt_dataset, results, imgs)
+        pair_counts = host_pair_counts(gt_dataset, results, imgs, polygons=polygons)
     row, seen, dt_areas = [], {}, []
     for res in results:  # row of every result in its image's table
         k = seen.get(res["image_id"], 0)

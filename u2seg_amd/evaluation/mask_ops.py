@@ -6,16 +6,19 @@ Two paths with identical results.  Host: data/rle.py's encode / decode in numpy,
 the strings are made from the planes (count -> scan -> lengths -> scan -> emit; the scans are torch.cumsum), the
 ground truth comes up as uncompressed counts and becomes planes there, the intersections are popcounts of plane & plane.
 One call of `mask_batch` costs two host synchronisations and two device-to-host transfers whatever the number of images:
-the arena size, then strings + string ends + areas + boxes + intersections in one buffer.  `counters` counts them.
+the arena size, then strings + string ends + areas + boxes + intersections (+ ground-truth areas) in one buffer.  `counters`
+counts them.
 
-Ground truth must be an RLE dict (compressed or uncompressed counts); polygons are out of scope."""
+Ground truth is an RLE dict (compressed or uncompressed counts).  Polygon lists are refused unless the caller asks for them
+(`polygons=True` / `gt=`): then they are rasterised by data/polygon.py's definition, on the device by csrc/polygon.hip into
+planes next to the RLE ones, with the same number of synchronisations and transfers."""
 import ctypes
 
 import numpy as np
 import torch
 
 from .. import _hip
-from ..data import rle
+from ..data import polygon, rle
 
 counters = {"host_syncs": 0, "d2h_transfers": 0}
 
@@ -25,6 +28,13 @@ class _MaskImage(ctypes.Structure):
 
     _fields_ = [("first", ctypes.c_int), ("n", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
                 ("in_offset", ctypes.c_longlong), ("plane_offset", ctypes.c_longlong), ("col_offset", ctypes.c_longlong)]
+
+
+class _PolyMask(ctypes.Structure):
+    """Mirror of U2PolyMask (include/u2seg_hip.h)."""
+
+    _fields_ = [("H", ctypes.c_int), ("W", ctypes.c_int), ("plane_offset", ctypes.c_longlong),
+                ("first_poly", ctypes.c_int), ("num_polys", ctypes.c_int)]
 
 
 class _PairImage(ctypes.Structure):
@@ -52,6 +62,34 @@ def gt_counts(ann, height, width, image_id=None):
     if sum(counts) != height * width or any(c < 0 for c in counts):
         raise ValueError("%s: RLE counts sum to %d, mask has %d pixels" % (where, sum(counts), height * width))
     return counts
+
+
+MAX_POLYGON_COORD = 1e8  # 5 x + .5 stays an int32 on the device
+
+
+def gt_polygons(ann, image_id=None):
+    """The polygons of a ground-truth annotation as float64 arrays [2 k], checked: every polygon a flat list of k >= 1 points
+    (cocoapi rasterises what the json holds; dropping polygons of fewer than 3 points is the dataset loader's business)."""
+    where = "annotation %s of image %s" % (ann.get("id"), ann.get("image_id", image_id))
+    seg = ann.get("segmentation")
+    if not isinstance(seg, (list, tuple)):
+        raise ValueError("%s: segmentation of type %s is neither an RLE dict nor a list of polygons" % (where, type(seg).__name__))
+    out = []
+    for p in seg:
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size == 0 or p.size % 2:
+            raise ValueError("%s: a polygon of %d numbers" % (where, p.size))
+        if not (np.abs(p) <= MAX_POLYGON_COORD).all():
+            raise ValueError("%s: polygon coordinates must be finite and within +-%g" % (where, MAX_POLYGON_COORD))
+        out.append(p)
+    return out
+
+
+def gt_mask(ann, height, width, image_id=None):
+    """The host definition of a ground-truth annotation's mask, uint8 [height, width]: RLE decoded, polygons rasterised."""
+    if isinstance(ann.get("segmentation"), dict):
+        return rle.decode({"size": [height, width], "counts": gt_counts(ann, height, width, image_id)})
+    return polygon.polygons_to_bitmask(gt_polygons(ann, image_id), height, width).astype(np.uint8)
 
 
 def words_per_column(h):
@@ -99,6 +137,66 @@ def planes_from_counts(counts_per_image, sizes, device):
     return planes, descs, m
 
 
+def planes_from_annotations(anns_per_image, sizes, device):
+    """Ground-truth planes on the device from annotations whose "segmentation" is an RLE dict or a list of polygons:
+    anns_per_image[i] = the annotation dicts of image i (size sizes[i]).  RLE annotations go through
+    u2_mask_planes_from_counts, polygon annotations through u2_mask_planes_from_polygons; the launcher of the former wants an
+    image's masks contiguous, so an image's planes are ordered RLE first.  Returns (planes int64, descriptors (n = masks of the
+    image, plane_offset = its first plane), info: "order" = per image the annotation index of every plane, "m" = planes in
+    all, "area" = int64 [m] on the host with the RLE masks' areas filled in, "poly_rows" = the planes that came from polygons
+    and "poly_area" = their areas, int32 on the device).  Two uploads at most (one int64 buffer: count offsets, polygon offsets, vertices; the counts)."""
+    nimg = len(sizes)
+    descs = (_MaskImage * max(nimg, 1))()   # what the pair kernel needs: all planes of the image
+    rdescs = (_MaskImage * max(nimg, 1))()  # the RLE planes of the image, for u2_mask_planes_from_counts
+    pmasks, order, count_lists, polys, rle_area = [], [], [], [], []
+    words = m = 0
+    for i, ((h, w), anns) in enumerate(zip(sizes, anns_per_image)):
+        h, w = int(h), int(w)
+        is_rle = [isinstance(a.get("segmentation"), dict) for a in anns]
+        parsed = [gt_counts(a, h, w) if r else gt_polygons(a) for a, r in zip(anns, is_rle)]
+        idx = [k for k, r in enumerate(is_rle) if r] + [k for k, r in enumerate(is_rle) if not r]
+        order.append(idx)
+        n = len(anns) if h * w > 0 else 0
+        nr = sum(is_rle) if n else 0
+        nw = w * words_per_column(h)
+        d, r = descs[i], rdescs[i]
+        d.first, d.n, d.H, d.W, d.in_offset, d.plane_offset, d.col_offset = m, n, h, w, 0, words, 0
+        r.first, r.n, r.H, r.W, r.in_offset, r.plane_offset, r.col_offset = len(count_lists), nr, h, w, 0, words, 0
+        for j, k in enumerate(idx[:n]):
+            if is_rle[k]:
+                count_lists.append(np.asarray(parsed[k], dtype=np.int32))
+                rle_area.append((m + j, int(sum(parsed[k][1::2]))))
+            else:
+                pm = _PolyMask()
+                pm.H, pm.W, pm.plane_offset, pm.first_poly, pm.num_polys = h, w, words + j * nw, len(polys), len(parsed[k])
+                pmasks.append((m + j, pm))
+                polys += parsed[k]
+        m += n
+        words += n * nw
+    planes = torch.empty(max(words, 1), dtype=torch.int64, device=device)
+    area = np.zeros(m, dtype=np.int64)
+    for row, v in rle_area:
+        area[row] = v
+    info = {"order": order, "m": m, "area": area, "poly_rows": [row for row, _ in pmasks],
+            "poly_area": torch.zeros(len(pmasks), dtype=torch.int32, device=device)}
+    if m == 0:
+        return planes, descs, info
+    offs = np.concatenate([[0], np.cumsum([len(c) for c in count_lists])]).astype(np.int64)
+    poffs = np.concatenate([[0], np.cumsum([len(p) // 2 for p in polys])]).astype(np.int64)
+    xy = np.concatenate(polys) if polys else np.zeros(0, dtype=np.float64)
+    up = torch.from_numpy(np.concatenate([offs, poffs, xy.view(np.int64)])).to(device)
+    if count_lists:
+        cum = torch.cumsum(torch.from_numpy(np.concatenate(count_lists)).to(device), 0, dtype=torch.int64)
+        _hip.call("u2_mask_planes_from_counts", cum, up[: len(offs)], planes, rdescs, nimg)
+    if pmasks:
+        pm = (_PolyMask * len(pmasks))(*[p for _, p in pmasks])
+        need = int(_hip.call_nostream("u2_mask_polygon_scratch_words", pm, len(pmasks)))
+        scratch = torch.empty(max(need, 1), dtype=torch.int64, device=device)
+        _hip.call("u2_mask_planes_from_polygons", up[len(offs) + len(poffs) :].view(torch.float64),
+                  up[len(offs) : len(offs) + len(poffs)], pm, len(pmasks), planes, info["poly_area"], scratch, need)
+    return planes, descs, info
+
+
 def _canvas_base(masks):
     """One base address + a byte offset per image for canvases that may sit in different allocations."""
     ptrs = [m.data_ptr() for m in masks if m.numel()]
@@ -106,10 +204,13 @@ def _canvas_base(masks):
     return base, [(m.data_ptr() - base if m.numel() else 0) for m in masks]
 
 
-def mask_batch(masks_list, gt_counts_list=None, strings=True):
+def mask_batch(masks_list, gt_counts_list=None, strings=True, gt=None):
     """masks_list: per image a bool / uint8 tensor [n_i, H_i, W_i] on one GPU.  gt_counts_list: per image a list of
-    uncompressed count lists (already checked by gt_counts), or None.  Returns per image a dict with "rles" (when strings),
-    "area" int64 [n_i], "bbox" float64 [n_i, 4] (x, y, w, h) and, with ground truth, "inter" int64 [n_i, G_i]."""
+    uncompressed count lists (already checked by gt_counts), or None.  gt (instead of gt_counts_list): per image the list of
+    ground-truth annotation dicts, RLE or polygon segmentations in any mix.  Returns per image a dict with "rles" (when
+    strings), "area" int64 [n_i], "bbox" float64 [n_i, 4] (x, y, w, h) and, with ground truth, "inter" int64 [n_i, G_i]
+    (columns in annotation order); with `gt` also "area_gt" int64 [G_i], the areas of the rasterised ground truth."""
+    assert gt is None or gt_counts_list is None
     dev = masks_list[0].device
     masks = []
     for m in masks_list:
@@ -164,8 +265,13 @@ def mask_batch(masks_list, gt_counts_list=None, strings=True):
         parts += [arena[:arena_bytes], ends.view(torch.uint8)]
     parts += [area[:total].view(torch.uint8), box[: total * 4].view(torch.uint8)]
     n_inter = 0
-    if gt_counts_list is not None:
+    ginfo = None
+    if gt is not None:
+        gt_planes, gdescs, ginfo = planes_from_annotations(gt, sizes, dev)
+        gt_counts_list = gt  # below only the number of ground truths per image is read
+    elif gt_counts_list is not None:
         gt_planes, gdescs, _ = planes_from_counts(gt_counts_list, sizes, dev)
+    if gt_counts_list is not None:
         pairs = (_PairImage * max(nimg, 1))()
         for i in range(nimg):
             p, d, g = pairs[i], descs[i], gdescs[i]
@@ -176,6 +282,8 @@ def mask_batch(masks_list, gt_counts_list=None, strings=True):
         if n_inter:
             _hip.call("u2_mask_pair_counts", planes, gt_planes, box, inter, pairs, nimg)
         parts.append(inter[:n_inter].view(torch.uint8))
+    if ginfo is not None:
+        parts.append(ginfo["poly_area"].view(torch.uint8))
     host = _sync_fetch(torch.cat(parts)).numpy()
     pos = 0
 
@@ -191,6 +299,8 @@ def mask_batch(masks_list, gt_counts_list=None, strings=True):
     area_h = take(4 * total, np.int32).astype(np.int64)
     box_h = take(16 * total, np.int32).reshape(total, 4).astype(np.float64)
     inter_h = take(4 * n_inter, np.int32).astype(np.int64) if gt_counts_list is not None else None
+    if ginfo is not None:
+        ginfo["area"][ginfo["poly_rows"]] = take(4 * len(ginfo["poly_rows"]), np.int32)
     out, ipos = [], 0
     for i, ((h, w), n) in enumerate(zip(sizes, nums)):
         d = descs[i]
@@ -211,18 +321,30 @@ def mask_batch(masks_list, gt_counts_list=None, strings=True):
                 ipos += n * g
             else:
                 res["inter"] = np.zeros((n, g), dtype=np.int64)
+        if ginfo is not None:  # planes are RLE first: back to annotation order
+            gd, order = gdescs[i], ginfo["order"][i]
+            res["area_gt"] = np.zeros(len(order), dtype=np.int64)
+            if gd.n:
+                res["area_gt"][order] = ginfo["area"][gd.first : gd.first + gd.n]
+            inter = np.empty_like(res["inter"])
+            inter[:, order] = res["inter"]
+            res["inter"] = inter
         out.append(res)
     return out
 
 
-def _host_image(masks, counts, h, w, strings=True):
+def _host_image(masks, counts, h, w, strings=True, anns=None):
     m = np.asarray(masks).astype(np.uint8)
     res = {}
     if strings:
         res["rles"] = [rle.encode(x) for x in m]
     res["area"] = m.sum(axis=(1, 2), dtype=np.int64)
-    if counts is not None:
-        gm = [rle.decode({"size": [h, w], "counts": c}) for c in counts]
+    if counts is not None or anns is not None:
+        if anns is not None:
+            gm = [gt_mask(a, h, w) for a in anns]
+            res["area_gt"] = np.array([g.sum(dtype=np.int64) for g in gm], dtype=np.int64).reshape(len(gm))
+        else:
+            gm = [rle.decode({"size": [h, w], "counts": c}) for c in counts]
         inter = np.zeros((len(m), len(gm)), dtype=np.int64)
         for j, g in enumerate(gm):
             inter[:, j] = (m & g[None]).sum(axis=(1, 2), dtype=np.int64)
@@ -230,12 +352,13 @@ def _host_image(masks, counts, h, w, strings=True):
     return res
 
 
-def mask_batch_any(masks_list, gt_counts_list=None, strings=True):
-    """`mask_batch` on the device when the masks are there, the numpy definition otherwise ("rles", "area", "inter")."""
+def mask_batch_any(masks_list, gt_counts_list=None, strings=True, gt=None):
+    """`mask_batch` on the device when the masks are there, the numpy definition otherwise ("rles", "area", "inter" and, with
+    `gt`, "area_gt")."""
     if masks_list and masks_list[0].is_cuda:
-        return mask_batch(masks_list, gt_counts_list, strings)
-    return [_host_image(m.numpy(), None if gt_counts_list is None else gt_counts_list[i], int(m.shape[1]), int(m.shape[2]), strings)
-            for i, m in enumerate(masks_list)]
+        return mask_batch(masks_list, gt_counts_list, strings, gt)
+    return [_host_image(m.numpy(), None if gt_counts_list is None else gt_counts_list[i], int(m.shape[1]), int(m.shape[2]), strings,
+                        None if gt is None else gt[i]) for i, m in enumerate(masks_list)]
 
 
 def encode_masks(pred_masks):
@@ -247,13 +370,19 @@ def encode_masks(pred_masks):
     return [rle.encode(np.asarray(x, dtype=np.uint8)) for x in m]
 
 
-def mask_pair_counts(pred_masks, gt_annotations, height, width):
+def mask_pair_counts(pred_masks, gt_annotations, height, width, polygons=False):
     """inter int64 [D, G] = pixels shared by predicted mask d and ground-truth mask g, area_dt int64 [D], area_gt int64 [G].
-    pred_masks: [D, height, width] tensor or array; gt_annotations: dicts with an RLE "segmentation" of that size."""
-    counts = [gt_counts(a, height, width) for a in gt_annotations]
-    area_gt = np.array([sum(c[1::2]) for c in counts], dtype=np.int64).reshape(len(counts))
+    pred_masks: [D, height, width] tensor or array; gt_annotations: dicts with an RLE "segmentation" of that size.
+    polygons=True: a "segmentation" may also be a list of polygons, rasterised by data/polygon.py's definition (on the device
+    when the masks are there); area_gt is then the rasterised area."""
+    if not polygons:
+        counts = [gt_counts(a, height, width) for a in gt_annotations]
+        area_gt = np.array([sum(c[1::2]) for c in counts], dtype=np.int64).reshape(len(counts))
     if not isinstance(pred_masks, torch.Tensor):
         pred_masks = torch.from_numpy(np.ascontiguousarray(np.asarray(pred_masks)).astype(np.uint8))
     assert tuple(pred_masks.shape[1:]) == (height, width), (pred_masks.shape, height, width)
+    if polygons:
+        res = mask_batch_any([pred_masks], strings=False, gt=[list(gt_annotations)])[0]
+        return res["inter"], res["area"], res["area_gt"]
     res = mask_batch_any([pred_masks], [counts], strings=False)[0]
     return res["inter"], res["area"], area_gt
