@@ -326,7 +326,6 @@ int launch_stream_cfg(ConvArgs& a, int N, int tiny, int forced, int code, hipStr
   const int lds_budget = (per_cu == 2 ? 80 : 160) * 1024;
   int ring = lds_budget / STAGE;
   if (ring > 8) ring = 8;
-  if (const char* e = getenv("U2_STREAM_RING")) { const int r = atoi(e); if (r >= 2 && r < ring) ring = r; }  // measurement knob
   if (ring < 2) return 0;
   a.tiles_m = (a.M + TM - 1) / TM;
   a.tiles_n = (N + CBW * 64 - 1) / (CBW * 64);

@@ -18,7 +18,6 @@
 // work-group = WCH x WPX waves: 4x2 (256 ch x 256 px, one group per CU), 2x2 and 4x1 (two groups per CU).
 #include <stdlib.h>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 #include <algorithm>
 #include <stdio.h>
@@ -66,20 +65,7 @@ __device__ unsigned long long* g_tile_sub_dev = nullptr;
 #define U2_SUBK(K) do { } while (0)
 #endif
 
-// measurement switch: -DU2_TILE_NOPRIO compiles the s_setprio brackets around the MFMA groups out (tools/exp/tile_noprio_ab.sh)
-#ifdef U2_TILE_NOPRIO
-#define U2_TILE_SETPRIO(P) do { } while (0)
-#else
-#define U2_TILE_SETPRIO(P) __builtin_amdgcn_s_setprio(P)
-#endif
-
-#ifdef U2_TILE_DMA_BY_HALF
-template <int N> __device__ __forceinline__ void wait_vm() {   // (the issuing half has twice the loads per stage in flight)
-  if ((threadIdx.x >> 6) < (blockDim.x >> 7)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * N > 63 ? 63 : 2 * N) : "memory");
-}
-#else
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#endif
 
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
@@ -141,35 +127,17 @@ __device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
 // the chip idle for the second round).  A share that begins inside a tile (k0 > 0) holds a non-leading part of it: its
 // accumulators go, raw fp32, into the work-group's slot of a.sk_ws and its flag is raised - at the START of that work-group's
 // life.  The share that holds the tile's first half K tile is its owner: at the END of its life it waits for the flags of
-// the (consecutive) work-groups holding the rest, adds their slots and runs the ordinary epilogue.  Every work-group of the
-// launch is resident (grid <= CUs x work-groups per CU), and nobody waits before having published, so the hand-over cannot
-// deadlock; slot stores and loads are both `sc0 sc1` (coherent for any placement of the two work-groups, MI355X_MICROARCH.md
-// "Workgroup dispatch ..."), the flag is a relaxed agent-scope atomic behind s_waitcnt vmcnt(0) + barrier.
+// the (consecutive) work-groups holding the rest, adds their slots and runs the ordinary epilogue.  Nobody waits before having
+// published, but the hand-over was measured to hang beside kernels of other streams: see the comment above sk_scratch() for
+// when this form may be launched.  Slot stores and loads are both `sc0 sc1` (coherent for any placement of the two work-groups,
+// MI355X_MICROARCH.md "Workgroup dispatch ..."), the flag is a relaxed agent-scope atomic behind s_waitcnt vmcnt(0) + barrier.
 // KT = 2 (round 5): a stage of the ring is a WHOLE K tile - rows of 64 channels, 128 bytes, so that an LDS-DMA instruction moves
 // 8 rows x 128 contiguous bytes instead of 16 x 64 (tests/native/dma_bench: 64-byte pieces at a 1-4 KB pitch stream at 3.5 TB/s,
 // 128-byte pieces at 6.3).  For the HBM-streaming 1x1 layers with long rows (K >= 512).  Two half-tile MFMA sequences per stage;
 // staging, the counted wait and the barrier happen once per stage (weights at the first half, pixels behind the barrier of the
 // second).  In the text below "half K tile" then reads "K tile" wherever it means the ring's unit.
-#ifndef U2_SKB
-#define U2_SKB 16
-#endif
-#ifndef U2_TILE_READS_FIRST
-#define U2_TILE_READS_FIRST 0   // measured: not faster (profiles/r06_tile_loop_experiments.txt)
-#endif
-#ifndef U2_TILE_LATE_PIXELS
-#define U2_TILE_LATE_PIXELS 0
-#endif
-#ifndef U2_TILE_W_FIRST
-#define U2_TILE_W_FIRST 0
-#endif
 #ifndef U2_TILE_PINGPONG
 #define U2_TILE_PINGPONG 0
-#endif
-#ifndef U2_TILE_ROLES
-#define U2_TILE_ROLES 0
-#endif
-#ifndef U2_TILE_PEEL
-#define U2_TILE_PEEL 0   // measured: not faster (profiles/r06_tile_loop_experiments.txt)
 #endif
 template <int WCH, int WPX, int RING, bool ACC = false, bool SK = false, int KT = 1>
 __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const ConvArgs a) {
@@ -179,16 +147,9 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
   constexpr int ROWB = 64 * KT;      // bytes per staged row
   constexpr int CPRW = ROWB / 16;    // 16-byte chunks per row
   constexpr int RPI = 1024 / ROWB;   // rows one LDS-DMA instruction moves
-  // U2_TILE_ROLES (round 6, profiles/r06_tile_loop_experiments.txt item 8): in the eight-wave work-groups the WEIGHT operand is staged by
-  // waves 0-3 alone and the PIXEL operand by waves 4-7 alone (twice the rows per issuing thread), so that on every SIMD one wave
-  // issues a phase's four LDS-DMA instructions back to back while its partner goes on multiplying - an LDS-DMA instruction costs
-  // the issuing wave ~100+ cycles when both waves of a SIMD issue two each in the same phase.  Loads per wave and stage stay 4.
-  constexpr bool ROLES = U2_TILE_ROLES && NW == 8 && KT == 1;
-  constexpr int SNW = ROLES ? NW / 2 : NW;          // waves that stage one operand
-  constexpr int LP = TM * CPRW / (SNW * 64);        // 16-byte chunks an ISSUING thread moves per stage, pixel operand
-  constexpr int LW = TN * CPRW / (SNW * 64);        //                                                   weight operand
-  constexpr int LPT = ROLES ? LP : LP + LW;         // LDS-DMA instructions per wave and stage
-  static_assert(!ROLES || LP == LW, "the role split needs equally many pixel and weight rows per stage");
+  constexpr int LP = TM * CPRW / NT;                // 16-byte chunks a thread moves per stage, pixel operand
+  constexpr int LW = TN * CPRW / NT;                //                                          weight operand
+  constexpr int LPT = LP + LW;                      // LDS-DMA instructions per wave and stage
   constexpr int PBYTES = TM * ROWB, WBYTES = TN * ROWB, BUF = PBYTES + WBYTES;  // one stage: rows of KU bf16
   constexpr int AHEAD = RING - 1;
   static_assert(LP >= 1 && LW >= 1 && RING >= (KT == 2 ? 2 : 3) && RING <= 5 && (KT == 1 || KT == 2), "unsupported configuration");
@@ -197,8 +158,6 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int sw_ = ROLES ? (w & (SNW - 1)) : w;            // this wave's index among the waves that stage an operand
-  const bool p_issuer = !ROLES || w >= SNW, w_issuer = !ROLES || w < SNW;
 #ifdef U2_TILE_TRACE
   const bool trace_on = w == 0 && g_tile_trace_dev != nullptr;
   unsigned long long* trace_row = g_tile_trace_dev + (size_t)blockIdx.x * 64;
@@ -257,7 +216,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
     const int m0 = (tile / a.tiles_n) * TM;
 #pragma unroll
     for (int i = 0; i < LP; ++i) {
-      const int m = m0 + (i * SNW + sw_) * RPI + row_in;
+      const int m = m0 + (i * NW + w) * RPI + row_in;
       if (m < a.M) {
         if (linear) {
           p_center[i] = (unsigned)(((size_t)m * a.in_ld + cc * 8) * 2);
@@ -310,36 +269,11 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
     }
     --p_kc;
     unsigned char* base = smem + buf * BUF;
-    // measurement switches (timing only, results are wrong): abl bit 4 = the pixel operand is staged by waves 0 .. NW/2-1 only and
-    // the weights by the others (half of the LDS-DMA instructions, the two waves of a SIMD issue theirs in different phases);
-    // bit 5 = no wave stages weights (half of the instructions, every wave in the same phase); both = no staging at all
-    // (compiled in with -DU2_TILE_DMA_ABLATION only - tools/exp/dma_phase_ablation.sh: the test puts a branch around every staging
-    //  instruction of the production loop otherwise)
-#ifdef U2_TILE_DMA_ABLATION
-    const bool skip_p = ((a.abl & 48) == 16 && w >= NW / 2) || (a.abl & 48) == 48;
-#else
-    constexpr bool skip_p = false;
-#endif
-#ifdef U2_TILE_DMA_BY_HALF
-    // TIMING ONLY (wrong results): waves 0 .. NW/2-1 issue the staging instructions of the whole work-group - their own and, with
-    // their own source rows, their SIMD partner's - and the other waves issue none: does an LDS-DMA instruction cost less when one
-    // wave of a SIMD issues them back to back than when both waves issue two each?
-    if (w < NW / 2) {
-#pragma unroll
-      for (int i = 0; i < LP; ++i) {
-        glds16(p_src[i], base + (i * NW + w) * 1024);
-        glds16(p_src[i], base + (i * NW + w + NW / 2) * 1024);   // (ablation build: not combined with U2_TILE_ROLES)
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < LP; ++i) p_src[i] += (p_okmask >> i & 1u) * KU;
-#else
 #pragma unroll
     for (int i = 0; i < LP; ++i) {
-      if (!skip_p && p_issuer) glds16(p_src[i], base + (i * SNW + sw_) * 1024);
+      glds16(p_src[i], base + (i * NW + w) * 1024);
       p_src[i] += (p_okmask >> i & 1u) * KU;
     }
-#endif
   };
 
   // Weight rows: LDS row rho = blk * 16 + q of a wave's 64-channel slice holds channel
@@ -353,7 +287,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
     const int n0 = (tile % a.tiles_n) * TN;
 #pragma unroll
     for (int i = 0; i < LW; ++i) {
-      const int R = (i * SNW + sw_) * RPI + row_in;
+      const int R = (i * NW + w) * RPI + row_in;
       const int blk = (R >> 4) & 3, q = R & 15;
       const int n = n0 + (R & ~63) + (blk >> 1) * 32 + (q >> 2) * 8 + (blk & 1) * 4 + (q & 3);
       w_base[i] = n < a.N ? (unsigned)(((size_t)n * ((size_t)a.wt_taps * a.C) + cc * 8) * 2) : 0xffffffffu;
@@ -379,28 +313,11 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
     }
     --w_kc;
     unsigned char* base = smem + buf * BUF + PBYTES;
-#ifdef U2_TILE_DMA_ABLATION
-    const bool skip_w = ((a.abl & 48) == 16 && w < NW / 2) || (a.abl & 32);
-#else
-    constexpr bool skip_w = false;
-#endif
-#ifdef U2_TILE_DMA_BY_HALF
-    if (w < NW / 2) {
-#pragma unroll
-      for (int i = 0; i < LW; ++i) {
-        glds16(w_src[i], base + (i * NW + w) * 1024);
-        glds16(w_src[i], base + (i * NW + w + NW / 2) * 1024);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < LW; ++i) w_src[i] += w_base[i] != 0xffffffffu ? KU : 0;
-#else
 #pragma unroll
     for (int i = 0; i < LW; ++i) {
-      if (!skip_w && w_issuer) glds16(w_src[i], base + (i * SNW + sw_) * 1024);
+      glds16(w_src[i], base + (i * NW + w) * 1024);
       w_src[i] += w_base[i] != 0xffffffffu ? KU : 0;
     }
-#endif
   };
 
   const int wr = w / WPX;  // 64-channel slice of the tile
@@ -413,7 +330,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
   const int pfrag0 = (wc * 128 + fr) * ROWB + ((fg ^ swz<KU>(fr)) << 4);
   auto ldw = [&](int hb, int t, int half = 0) { return *reinterpret_cast<const s16x8*>(smem + hb * BUF + (wfrag0 ^ (half << 6)) + t * 16 * ROWB); };
   auto ldp = [&](int hb, int t, int half = 0) { return *reinterpret_cast<const s16x8*>(smem + hb * BUF + (pfrag0 ^ (half << 6)) + t * 16 * ROWB); };
-#if U2_TILE_READS_FIRST || U2_TILE_PINGPONG
+#if U2_TILE_PINGPONG
   // Fragment reads as inline asm with counted waits (KT = 1 only): the compiler answers a plain LDS load it must wait for with
   // s_waitcnt lgkmcnt(0) whenever LDS-DMA is in flight (it will not count across it), which forbids having a SECOND batch of reads in
   // flight while the first is consumed.  LDS returns in order, so `lgkmcnt(6)` with twelve reads outstanding releases the older six.
@@ -559,22 +476,13 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
 #pragma unroll
   for (int i = 0; i < AHEAD; ++i) { stage_pixels(i); stage_weights(i); }
   stage_pixels(AHEAD);
-  wait_vm<ROLES ? LPT * (AHEAD - 1) : LPT * (AHEAD - 1) + LP>();   // (ROLES: a weight wave has stages 0 .. AHEAD - 1 in flight, a pixel wave one more)
+  wait_vm<LPT * (AHEAD - 1) + LP>();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   U2_STAMP(1);
 #if U2_TILE_PINGPONG
   if constexpr (KT == 1 && !ACC) {
     // ping-pong form: both wave groups enter their first step "cold" (they read its fragments themselves)
-  } else
-#endif
-#if U2_TILE_READS_FIRST
-  if constexpr (KT == 1) {
-    // (asm like the reads of the loop: a compiler-visible LDS load pending at the loop header would make the wait-count pass put
-    //  s_waitcnt lgkmcnt(0) in front of the loop's first counted wait in EVERY iteration)
-    const unsigned pa = lds_base + (unsigned)pfrag0, wa = lds_base + (unsigned)wfrag0;
-    U2_T_RD(wfA[0], wa, 0); U2_T_RD(wfA[1], wa, 16 * ROWB);
-    U2_T_RD(pf[0], pa, 0); U2_T_RD(pf[1], pa, 16 * ROWB); U2_T_RD(pf[2], pa, 2 * 16 * ROWB); U2_T_RD(pf[3], pa, 3 * 16 * ROWB);
   } else
 #endif
   {
@@ -613,7 +521,8 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
       asm volatile("global_store_dword %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(a.sk_flags + blockIdx.x), "v"(one) : "memory");
     }
   };
-  constexpr int SKB = U2_SKB;   // loads in flight per thread in sk_combine: 8, 12 (no), 16
+  constexpr int SKB = 16;   // loads in flight per thread in sk_combine (four measured the same: profiles/r06_1x1_k512.txt)
+  static_assert(SKB == 16, "the counted waits of sk_combine are written for four groups of four loads");
   auto sk_combine = [&](int tile) {
     // the work-groups idx + 1, idx + 2, ... of this XCD hold the rest of the tile: all whose share begins before the tile ends
     const long long tile_end = (long long)(tile - xbase + 1) * nkh;
@@ -648,10 +557,10 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
           }
 #pragma unroll
           for (int g = 0; g < SKB / 4; ++g) {
-            if (g == SKB / 4 - 1) asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[g * 4]), "+v"(t[g * 4 + 1]), "+v"(t[g * 4 + 2]), "+v"(t[g * 4 + 3])::"memory");
-            else if (g == SKB / 4 - 2) asm volatile("s_waitcnt vmcnt(4)" : "+v"(t[g * 4]), "+v"(t[g * 4 + 1]), "+v"(t[g * 4 + 2]), "+v"(t[g * 4 + 3])::"memory");
-            else if (g == SKB / 4 - 3) asm volatile("s_waitcnt vmcnt(8)" : "+v"(t[g * 4]), "+v"(t[g * 4 + 1]), "+v"(t[g * 4 + 2]), "+v"(t[g * 4 + 3])::"memory");
-            else asm volatile("s_waitcnt vmcnt(12)" : "+v"(t[g * 4]), "+v"(t[g * 4 + 1]), "+v"(t[g * 4 + 2]), "+v"(t[g * 4 + 3])::"memory");
+            if (g == 0) asm volatile("s_waitcnt vmcnt(12)" : "+v"(t[g * 4]), "+v"(t[g * 4 + 1]), "+v"(t[g * 4 + 2]), "+v"(t[g * 4 + 3])::"memory");
+            else if (g == 1) asm volatile("s_waitcnt vmcnt(8)" : "+v"(t[g * 4]), "+v"(t[g * 4 + 1]), "+v"(t[g * 4 + 2]), "+v"(t[g * 4 + 3])::"memory");
+            else if (g == 2) asm volatile("s_waitcnt vmcnt(4)" : "+v"(t[g * 4]), "+v"(t[g * 4 + 1]), "+v"(t[g * 4 + 2]), "+v"(t[g * 4 + 3])::"memory");
+            else asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[g * 4]), "+v"(t[g * 4 + 1]), "+v"(t[g * 4 + 2]), "+v"(t[g * 4 + 3])::"memory");
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
               const int blk = q * SKB + g * 4 + jj;   // accumulator block i * 8 + j in slot order
@@ -670,111 +579,63 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int h_begin = (SK && ti == 0) ? sk_k0 : 0, h_end = (SK && ti == my_tiles - 1) ? sk_k1 : nkh;
-    // One half K tile (the sequence documented above).  FAST: the step lies in the interior of the work-group's life
-    // (gh + AHEAD + 1 < H), where every staging / read-ahead condition holds and the counted wait is the steady-state one - the
-    // interior steps run without the five compare-and-branch pairs and the wait ladder of the general form (round 6: the waves of
-    // a SIMD sit in the same phase behind the step's barrier, so every cycle of this bookkeeping is a cycle the matrix pipe idles:
-    // profiles/r06_1x1_k512.txt).  MEASURED NOT FASTER (26 instructions and 7 branches fewer per step, 0 ... 4 % slower on the 256 x 256
-    // configurations: profiles/r06_tile_loop_experiments.txt), so the default is the single general loop; -DU2_TILE_PEEL=1 selects this form.
-    auto step = [&](auto fast_tag) {
-      constexpr bool FAST = decltype(fast_tag)::value;
+    // One half K tile (the sequence documented above).  A form with the interior steps peeled off, free of the staging conditions
+    // and the wait ladder, measured not faster: profiles/r06_tile_loop_experiments.txt.
+    auto step = [&]() {
       const int nb = (hb + 1 == RING) ? 0 : hb + 1;
       const int sb = (hb == 0) ? RING - 1 : hb - 1;  // buffer of stage gh + AHEAD (= gh - 1 mod RING)
       if constexpr (KT == 2) {
         // ---- first half of the stage: no staging of pixels, no wait, no barrier; the second half's fragments are in the same buffer
-        U2_TILE_SETPRIO(1);
+        __builtin_amdgcn_s_setprio(1);
         U2_T_MFMA(0, wfA[0], 0); U2_T_MFMA(1, wfA[1], 0); U2_T_MFMA(0, wfA[0], 1); U2_T_MFMA(1, wfA[1], 1);
-        U2_TILE_SETPRIO(0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         pf[4] = ldp(hb, 4); pf[5] = ldp(hb, 5); pf[6] = ldp(hb, 6); pf[7] = ldp(hb, 7);
         wfB[0] = ldw(hb, 2); wfB[1] = ldw(hb, 3);
-        if (FAST || gh + AHEAD < H) stage_weights(sb);   // the buffer of stage gh - 1: every wave left it at the last barrier
+        if (gh + AHEAD < H) stage_weights(sb);   // the buffer of stage gh - 1: every wave left it at the last barrier
         __builtin_amdgcn_sched_barrier(0);
-        U2_TILE_SETPRIO(1);
+        __builtin_amdgcn_s_setprio(1);
         U2_T_MFMA(0, wfA[0], 2); U2_T_MFMA(1, wfA[1], 2); U2_T_MFMA(0, wfA[0], 3); U2_T_MFMA(1, wfA[1], 3);
 #pragma unroll
         for (int j = 4; j < 8; ++j) { U2_T_MFMA(0, wfA[0], j); U2_T_MFMA(1, wfA[1], j); }
 #pragma unroll
         for (int j = 0; j < 4; ++j) { U2_T_MFMA(2, wfB[0], j); U2_T_MFMA(3, wfB[1], j); }
-        U2_TILE_SETPRIO(0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         wfA[0] = ldw(hb, 0, 1); wfA[1] = ldw(hb, 1, 1);
         pf[0] = ldp(hb, 0, 1); pf[1] = ldp(hb, 1, 1); pf[2] = ldp(hb, 2, 1); pf[3] = ldp(hb, 3, 1);
         __builtin_amdgcn_sched_barrier(0);
-        U2_TILE_SETPRIO(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int j = 4; j < 8; ++j) { U2_T_MFMA(2, wfB[0], j); U2_T_MFMA(3, wfB[1], j); }
-        U2_TILE_SETPRIO(0);
+        __builtin_amdgcn_s_setprio(0);
       }
       constexpr int LH = KT - 1;   // the half of the stage the sequence below multiplies (its fragments 0-3 / first weight pair are in registers)
       // phase A
-#if U2_TILE_READS_FIRST
-      // round 6 experiment (MEASURED NOT FASTER, default off): the fragments the second half of phase A needs are requested at its very start (their registers are
-      // free: the last MFMAs of the previous step read them), so that eight MFMAs and the weight staging cover their LDS round trip
-      // instead of four MFMAs - all eight waves request 6 KB each at the same moment, ~190 cycles of LDS bandwidth alone
-      if constexpr (KT == 1) {
-        {
-          const unsigned pa = lds_base + (unsigned)(hb * BUF + pfrag0), wa = lds_base + (unsigned)(hb * BUF + wfrag0);
-          U2_T_RD(pf[4], pa, 4 * 16 * ROWB); U2_T_RD(pf[5], pa, 5 * 16 * ROWB); U2_T_RD(pf[6], pa, 6 * 16 * ROWB);
-          U2_T_RD(pf[7], pa, 7 * 16 * ROWB); U2_T_RD(wfB[0], wa, 2 * 16 * ROWB); U2_T_RD(wfB[1], wa, 3 * 16 * ROWB);
-        }
-        // the six reads of the previous step's phase B (or the prologue's) have returned once at most six are outstanding
-        U2_T_WAIT6(6, wfA[0], wfA[1], pf[0], pf[1], pf[2], pf[3]);
-        __builtin_amdgcn_sched_barrier(0);
-        U2_TILE_SETPRIO(1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { U2_T_MFMA(0, wfA[0], j); U2_T_MFMA(1, wfA[1], j); }
-        U2_TILE_SETPRIO(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (FAST || gh + AHEAD < H) stage_weights(sb);
-        U2_T_WAIT6(0, pf[4], pf[5], pf[6], pf[7], wfB[0], wfB[1]);
-        __builtin_amdgcn_sched_barrier(0);
-        U2_TILE_SETPRIO(1);
-#pragma unroll
-        for (int j = 4; j < 8; ++j) { U2_T_MFMA(0, wfA[0], j); U2_T_MFMA(1, wfA[1], j); }
-        U2_TILE_SETPRIO(0);
-      } else
-#endif
-      {
-      U2_TILE_SETPRIO(1);
+      __builtin_amdgcn_s_setprio(1);
       U2_T_MFMA(0, wfA[0], 0); U2_T_MFMA(1, wfA[1], 0); U2_T_MFMA(0, wfA[0], 1); U2_T_MFMA(1, wfA[1], 1);
-      U2_TILE_SETPRIO(0);
+      __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       U2_SUBK(3);
-#if U2_TILE_W_FIRST
-      // round 6 experiment: the weight staging in FRONT of phase A's fragment reads (an LDS-DMA instruction issued behind six
-      // outstanding ds_read_b128 is the expensive case of MI355X_MICROARCH.md's price list)
-      if constexpr (KT == 1) {
-        if (FAST || gh + AHEAD < H) stage_weights(sb);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#endif
       pf[4] = ldp(hb, 4, LH); pf[5] = ldp(hb, 5, LH); pf[6] = ldp(hb, 6, LH); pf[7] = ldp(hb, 7, LH);
       wfB[0] = ldw(hb, 2, LH); wfB[1] = ldw(hb, 3, LH);
-#if !U2_TILE_W_FIRST
       if constexpr (KT == 1) {
-        if (FAST || gh + AHEAD < H) stage_weights(sb);
+        if (gh + AHEAD < H) stage_weights(sb);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
       U2_SUBK(4);
-      U2_TILE_SETPRIO(1);
+      __builtin_amdgcn_s_setprio(1);
       U2_T_MFMA(0, wfA[0], 2); U2_T_MFMA(1, wfA[1], 2); U2_T_MFMA(0, wfA[0], 3); U2_T_MFMA(1, wfA[1], 3);
 #pragma unroll
       for (int j = 4; j < 8; ++j) { U2_T_MFMA(0, wfA[0], j); U2_T_MFMA(1, wfA[1], j); }
-      U2_TILE_SETPRIO(0);
+      __builtin_amdgcn_s_setprio(0);
       U2_SUBK(5);
-      }
       // phase B
-      if constexpr (FAST) {
-        wait_vm<LPT * (AHEAD - 1)>();
-      } else {
-        const int rem = H - 2 - gh;  // stages staged behind gh + 1
-        if (rem >= AHEAD - 1) wait_vm<LPT * (AHEAD - 1)>();
-        else if (AHEAD > 3 && rem == 2) wait_vm<LPT * 2>();
-        else if (rem == 1) wait_vm<LPT>();
-        else wait_vm<0>();
-      }
+      const int rem = H - 2 - gh;  // stages staged behind gh + 1
+      if (rem >= AHEAD - 1) wait_vm<LPT * (AHEAD - 1)>();
+      else if (AHEAD > 3 && rem == 2) wait_vm<LPT * 2>();
+      else if (rem == 1) wait_vm<LPT>();
+      else wait_vm<0>();
       U2_SUBK(6);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -783,41 +644,23 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
       if (gh < 44) U2_STAMP(2 + gh);
       U2_SUB(0);
 #endif
-      // U2_TILE_LATE_PIXELS (round 6 experiment): the pixel staging of the step behind the first eight MFMAs of phase B instead of in
-      // front of them - all eight waves leave the barrier together and queue on the CU's one vector-memory path (16 instructions
-      // of 16 cycles each) before any of them issues an MFMA; the order of the VMEM operations of a wave is unchanged
-#if !U2_TILE_LATE_PIXELS
-      if (FAST || gh + AHEAD + 1 < H) stage_pixels(hb);
-#endif
+      if (gh + AHEAD + 1 < H) stage_pixels(hb);
       __builtin_amdgcn_sched_barrier(0);
-      U2_TILE_SETPRIO(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int j = 0; j < 4; ++j) { U2_T_MFMA(2, wfB[0], j); U2_T_MFMA(3, wfB[1], j); }
-      U2_TILE_SETPRIO(0);
+      __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       U2_SUBK(1);
-#if U2_TILE_LATE_PIXELS
-      if (FAST || gh + AHEAD + 1 < H) stage_pixels(hb);
-      __builtin_amdgcn_sched_barrier(0);
-#endif
-      if (FAST || gh + 1 < H) {
-#if U2_TILE_READS_FIRST
-        if constexpr (KT == 1) {
-          const unsigned pa = lds_base + (unsigned)(nb * BUF + pfrag0), wa = lds_base + (unsigned)(nb * BUF + wfrag0);
-          U2_T_RD(wfA[0], wa, 0); U2_T_RD(wfA[1], wa, 16 * ROWB);
-          U2_T_RD(pf[0], pa, 0); U2_T_RD(pf[1], pa, 16 * ROWB); U2_T_RD(pf[2], pa, 2 * 16 * ROWB); U2_T_RD(pf[3], pa, 3 * 16 * ROWB);
-        } else
-#endif
-        {
+      if (gh + 1 < H) {
         wfA[0] = ldw(nb, 0); wfA[1] = ldw(nb, 1);
         pf[0] = ldp(nb, 0); pf[1] = ldp(nb, 1); pf[2] = ldp(nb, 2); pf[3] = ldp(nb, 3);
-        }
       }
       __builtin_amdgcn_sched_barrier(0);
-      U2_TILE_SETPRIO(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int j = 4; j < 8; ++j) { U2_T_MFMA(2, wfB[0], j); U2_T_MFMA(3, wfB[1], j); }
-      U2_TILE_SETPRIO(0);
+      __builtin_amdgcn_s_setprio(0);
       U2_SUBK(2);
       ++gh;
       hb = nb;
@@ -833,7 +676,6 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
     // across a tile boundary (the first step of a tile is "cold" for both groups): no fragment register is live in the epilogue.
     // Same products into the same accumulators in the same K order as the lock-step form: bit-identical results.
     auto step_pp = [&](bool first_of_tile, bool last_of_tile) {
-      constexpr bool FAST = false;
       const int nb = (hb + 1 == RING) ? 0 : hb + 1;
       const int sb = (hb == 0) ? RING - 1 : hb - 1;
       const bool grp_x = w < NW / 2;
@@ -843,13 +685,13 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wfA[0]), "+v"(wfA[1]), "+v"(pf[0]), "+v"(pf[1]), "+v"(pf[2]), "+v"(pf[3])::"memory");  \
       asm volatile("" : "+v"(pf[4]), "+v"(pf[5]), "+v"(pf[6]), "+v"(pf[7])::"memory")
 #define U2_PP_MA()                                                                                                               \
-      U2_TILE_SETPRIO(1);                                                                                                        \
+      __builtin_amdgcn_s_setprio(1);                                                                                                        \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) { U2_T_MFMA(0, wfA[0], j); U2_T_MFMA(1, wfA[1], j); }                        \
-      U2_TILE_SETPRIO(0)
+      __builtin_amdgcn_s_setprio(0)
 #define U2_PP_MB()                                                                                                               \
-      U2_TILE_SETPRIO(1);                                                                                                        \
+      __builtin_amdgcn_s_setprio(1);                                                                                                        \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) { U2_T_MFMA(2, wfB[0], j); U2_T_MFMA(3, wfB[1], j); }                        \
-      U2_TILE_SETPRIO(0)
+      __builtin_amdgcn_s_setprio(0)
       // ---------------- half A  (ONE copy of every MFMA group: the group-dependent pieces around them are reads and staging only)
       if (cold) {
         U2_T_RD(wfA[0], wa, 0); U2_T_RD(wfA[1], wa, 16 * ROWB);
@@ -922,15 +764,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
     } else
 #endif
     {
-#if U2_TILE_PEEL
-    while (h < h_end) {
-      int nfast = min(h_end - h, H - (AHEAD + 1) - gh);
-      for (; nfast > 0; --nfast, ++h) step(std::true_type{});
-      if (h < h_end) { step(std::false_type{}); ++h; }
-    }
-#else
-    for (; h < h_end; ++h) step(std::false_type{});
-#endif
+    for (; h < h_end; ++h) step();
     }
     if constexpr (SK) {
       if (h_begin > 0) { U2_STAMP(48); sk_publish(); U2_STAMP(49); continue; }   // a non-leading part: handed to the tile's owner
@@ -969,7 +803,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
 // every persistent-kernel hand-over does); it does NOT rely on co-residency of the whole grid.
 //
 // Round 6: MEASURED OTHERWISE.  With the semantic / mask head's kernels on their own streams beside it, the driver's bench command hung
-// in 4 of 23 runs (tools/exp/hang_hunt.sh: the chip never finishes a step), in 0 of 24 with this form forbidden (variant bit 28), in 0
+// in 4 of 23 runs (profiles/r06_hang_hunt.txt: the chip never finishes a step), in 0 of 24 with this form forbidden (variant bit 28), in 0
 // of 40 with those streams off, and still in 3 of 30 with the stream-K launches of different streams ordered behind each other by
 // events - one launch of this form beside kernels of another stream is enough.  What the argument above misses is not understood.
 // The product path (layers/functional.py:streamk_region) asks for this form only where no branch stream has work in flight and

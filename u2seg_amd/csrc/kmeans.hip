@@ -214,9 +214,6 @@ constexpr int KS_NB = 20;                    // 16-centroid blocks: 320 centroid
 constexpr int KS_KMAX = KS_NB * 16;
 constexpr int KS_STAGE = 2 * KS_KMAX * 64;   // [hi | lo][320 rows][32 bf16]
 constexpr int KS_RING = 3;
-#ifndef U2_KM_X3
-#define U2_KM_X3 1
-#endif
 constexpr int KS_DMA = KS_STAGE / 1024 / 8;  // LDS-DMA instructions per wave per step (5)
 
 // chl [2][320][D] bf16 (hi plane, lo plane; rows >= K zero), cn[j] = |c_j|^2 in fp32, *cmax2 = max_j cn[j]
@@ -467,20 +464,19 @@ __global__ __launch_bounds__(512) void kmeans_screen_kernel(const float* __restr
   // in flight lives in a register the compiler could move.  NP = 1 stages only the hi plane of the centroids (3 instead of 5
   // LDS-DMA instructions per wave and step: rows 320-383 of the stage are filler from the lo plane), ring of 3 as before; NP = 3
   // with XR keeps both planes in a ring of 2 (centroids(s + 1) requested at the start of step s, 144 KB in all).
-  // Round 6, X3 (coarse pass only, -DU2_KM_X3=0 restores the round-5 form): THREE x slots.  The coarse pass is bound by how many bytes of x
+  // Round 6, X3 (coarse pass only; the two-slot form it replaced: profiles/r06_km_x3.txt): THREE x slots.  The coarse pass is bound by how many bytes of x
   // a CU has in flight (3.8 TB/s with two steps = 64 KB); a third slot needs (i) the centroid stage without its filler rows - 320 rows
   // x 64 B = 20 KB, twenty LDS-DMA instructions: waves 0-5 issue three, wave 6 two, wave 7 none - so that 3 x 20 + 3 x 32 KB = 156 KB
   // fit, and (ii) the centroids of a step requested BEFORE the step's x: vmcnt retires in order, so with x(s + 2) queued in front of
   // centroids(s + 1) the wait for the centroids waited for that x as well and a third slot bought nothing (round 5's note).  Issue
   // order now: ... c(s + 1) x(s + 2) | c(s + 2) x(s + 3) | ...; the wait that closes step s leaves x(s + 2), c(s + 2), x(s + 3) in flight.
   constexpr bool XR = NP == 1 || XR3;
-  constexpr bool X3 = NP == 1 && U2_KM_X3;
+  constexpr bool X3 = NP == 1;
   constexpr int CDMA = NP == 1 ? 3 : KS_DMA;           // centroid LDS-DMA instructions per wave and step (X3: at most)
   constexpr int CSTAGE = X3 ? KS_KMAX * 64 : CDMA * 8 * 1024;   // bytes of a centroid stage
   constexpr int CRING = (NP == 3 && XR) ? 2 : KS_RING; // centroid stages
   constexpr int XDMA = 4;                              // x: 32 rows x 128 bytes per wave and step
   constexpr int XSLOT = KS_PTS * 128;                  // bytes of an x slot of the work-group
-  constexpr int XSLOTS = X3 ? 3 : 2;
   unsigned char* const xring = ks_smem + CRING * CSTAGE;
 
   // x: lane (fr, fg) owns row m * 16 + fr of both 16-point blocks and, per 32-dimension step, dimensions fg * 4 .. + 3 and
@@ -578,16 +574,6 @@ __global__ __launch_bounds__(512) void kmeans_screen_kernel(const float* __restr
     if (nsteps > 2) U2_KS_WAIT_VM(2);            // x(1), c(1), x(2) may be in flight
     else if (nsteps > 1) U2_KS_WAIT_VM(1);       // x(1), c(1)
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else if constexpr (XR && CRING == 3) {
-    stage_x(0);
-    stage_c(0);
-    if (nsteps > 1) {
-      stage_x(1);
-      stage_c(1);
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XDMA + CDMA) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
   } else if constexpr (XR) {   // ring of 2: in flight when step s begins: x(s + 1) only
     stage_c(0);
     stage_x(0);
@@ -627,10 +613,8 @@ __global__ __launch_bounds__(512) void kmeans_screen_kernel(const float* __restr
       if constexpr (X3) {           // (LOAD: centroids(s + 2) exist, STAGE: x(s + 3) exists) centroids first, see the head comment
         if (LOAD) stage_c((s + 2) % 3);
         if (STAGE) stage_x(xsl);
-      } else {
-        if constexpr (CRING == 2) {   // centroids(s + 1) go first: the wait that closes the step leaves only x(s + 2) in flight
-          if (LOAD) stage_c((s + 1) & 1);
-        }
+      } else {                      // ring of 2, centroids(s + 1) go first: the wait that closes the step leaves only x(s + 2) in flight
+        if (LOAD) stage_c((s + 1) & 1);
         if (STAGE) stage_x(s & 1);
       }
     }
@@ -653,7 +637,7 @@ __global__ __launch_bounds__(512) void kmeans_screen_kernel(const float* __restr
     if constexpr (!XR) {
       if (LOAD) load_x();
     }
-    if constexpr (CRING == 3 && !X3) {
+    if constexpr (!XR) {
       if (STAGE) stage_c((s + 2) % KS_RING);
     }
     // Two centroid blocks at a time, piece by piece: consecutive MFMAs go to four different accumulators, so the three products
@@ -724,7 +708,7 @@ __global__ __launch_bounds__(512) void kmeans_screen_kernel(const float* __restr
       else if (LOAD) U2_KS_WAIT_VM(1);                        // s = nsteps - 3: x(s + 2), c(s + 2)
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
-    if (STAGE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(!XR ? CDMA : CRING == 3 ? XDMA + CDMA : XDMA) : "memory");
+    if (STAGE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(!XR ? CDMA : XDMA) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     if constexpr (!XR) asm volatile("" : "+v"(raw[0][0]), "+v"(raw[0][1]), "+v"(raw[1][0]), "+v"(raw[1][1])::"memory");
@@ -853,11 +837,6 @@ __device__ unsigned long long km_trace[8192 * 16];   // [work-group][role][8]
 #else
 #define U2_KM_STAMP(I)
 #endif
-// timing-only ablations of the loop (results are wrong): 1 no MFMAs, 2 no centroid-fragment reads behind the first group, 4 no LDS-DMA
-// requests in the loop, 8 no barrier
-#ifndef U2_KC_ABL
-#define U2_KC_ABL 0
-#endif
 constexpr int KC_SLOTS = 6;
 constexpr int KC_SLOT = KS_PTS * 64;           // 16 groups x 1 KB
 constexpr int KC_STAGE = KS_KMAX * 64;         // hi plane: 320 rows x 64 B
@@ -974,14 +953,13 @@ __global__ __launch_bounds__(512) void kmeans_coarse_kernel(const unsigned char*
     const int pmine = ((int)blockIdx.x + it * (int)gridDim.x) * KS_PTS + w * 32 + ((fr >> 2) & 1) * 16 + fg * 4 + (fr & 3);
     float xn, xlo, xno;       // |y|, |y - bf16(y)| for y = x_p - mu, and |x_p|
     for (int s = 0; s < nsteps; ++s, ++g) {
-      if (!(U2_KC_ABL & 8)) __builtin_amdgcn_s_barrier();   // stage / slot g are complete for every wave, and every wave is done with step g - 1
+      __builtin_amdgcn_s_barrier();   // stage / slot g are complete for every wave, and every wave is done with step g - 1
       asm volatile("" ::: "memory");
       s16x8 ah[2];
       const unsigned xs = xoff + (unsigned)(xslot * KC_SLOT);
       asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024" : "=&v"(ah[0]), "=&v"(ah[1]) : "v"(xs) : "memory");
       // this step's requests go to the stage / slot that every wave read in step g - 1 (the barrier above has seen that)
-      if (U2_KC_ABL & 4) {
-      } else if (!xrole) {
+      if (!xrole) {
         if (g + 2 < T) stage_c(cbuf == 0 ? 2 : cbuf - 1);
       } else {
         if (g + KC_SLOTS - 1 < T) stage_x(xslot == 0 ? KC_SLOTS - 1 : xslot - 1);
@@ -991,7 +969,6 @@ __global__ __launch_bounds__(512) void kmeans_coarse_kernel(const unsigned char*
       s16x8 bq[2][4];
       const unsigned sba = lds0 + (unsigned)(cbuf * KC_STAGE) + boff;
 #define U2_KC_LDQ(SET, NB)                                                                                                    \
-      if (!(U2_KC_ABL & 2) || (NB) < 8)                                                                                        \
       asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\t"       \
                    "ds_read_b128 %3, %4 offset:%8"                                                                             \
                    : "=&v"(bq[SET][0]), "=&v"(bq[SET][1]), "=&v"(bq[SET][2]), "=&v"(bq[SET][3])                               \
@@ -999,7 +976,7 @@ __global__ __launch_bounds__(512) void kmeans_coarse_kernel(const unsigned char*
 #define U2_KC_WAIT(SET, CNT)                                                                                                  \
       asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(bq[SET][0]), "+v"(bq[SET][1]), "+v"(bq[SET][2]), "+v"(bq[SET][3]) : "n"(CNT) : "memory")
 #define U2_KC_QUAD(SET, NB)                                                                                                   \
-      if (!(U2_KC_ABL & 1)) {                                                                                                  \
+      {                                                                                                                        \
         const s16x8 b0 = bq[SET][0], b1 = bq[SET][1], b2 = bq[SET][2], b3 = bq[SET][3];                                        \
         acc[0][NB] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ks_h16x8, ah[0]), __builtin_bit_cast(ks_h16x8, b0), acc[0][NB], 0, 0, 0);                                  \
         acc[1][NB] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ks_h16x8, ah[1]), __builtin_bit_cast(ks_h16x8, b0), acc[1][NB], 0, 0, 0);                                  \
@@ -1507,8 +1484,7 @@ extern "C" int u2_kmeans_assign_shadow(const float* x, const float* shadow, cons
   }
   const dim3 grid((N + KS_PTS - 1) / KS_PTS), block(512);
   const size_t lds = KS_RING * KS_STAGE;                               // fine pass: both centroid planes, x through registers
-  const size_t lds1 = U2_KM_X3 ? (size_t)KS_RING * KS_KMAX * 64 + 3 * KS_PTS * 128     // coarse pass: hi plane (20 KB stages) + three x slots
-                               : (size_t)KS_RING * 3 * 8 * 1024 + 2 * KS_PTS * 128;   // round 5: 24 KB stages with filler rows + two x slots
+  const size_t lds1 = (size_t)KS_RING * KS_KMAX * 64 + 3 * KS_PTS * 128;   // coarse pass: hi plane (20 KB stages) + three x slots
   const size_t lds3 = 2 * KS_STAGE + 2 * KS_PTS * 128;                // fine pass with the x ring: two centroid stages + two x slots
   static const int xring3 = getenv("U2_KM_XRING3") ? atoi(getenv("U2_KM_XRING3")) : 1;   // measurement knob: 0 = x through registers
   const int* gate = reinterpret_cast<const int*>(state + 1);

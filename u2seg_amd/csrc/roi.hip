@@ -151,15 +151,7 @@ constexpr int FS_MAXP = 14, FS_MAXR = 16;
 // times the number of threads resident (71-75 % of the wave cycles parked, 3.4 TB/s through the L1s): at 92 registers five
 // waves fit a SIMD, at <= 64 eight - measured 1.48 -> 1.23 ms for 32 000 ROIs of 7 x 7, 0.44 -> 0.37 for 3 200 of 14 x 14
 // (profiles/r05_pmc_roi.txt; the handful of spilled registers sit in the sample-by-sample fall-back)
-#ifndef FS_OCC
-#define FS_OCC 8
-#endif
-#ifndef FS_PAIR
-#define FS_PAIR 1
-#endif
-#ifndef FS_QUAD
-#define FS_QUAD 1
-#endif
+constexpr int FS_OCC = 8;
 
 // One work item = (bin row ph, 8-channel chunk) sweeping ALL bin columns of the row (round 5).  Neighbouring bins overlap by one or
 // two pixel columns (bin pw ends at floor(last sample) + 1, bin pw + 1 starts at floor(its first sample) >= floor(that last sample)),
@@ -328,7 +320,6 @@ __global__ __launch_bounds__(256, FS_OCC) void roi_align_fwd_sep_kernel(const Ro
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
     const int ny = cnt[0][ph], nx = cnt[1][pw], y0 = lo[0][ph], x0 = lo[1][pw];
-#if FS_QUAD
     // round 6: two pixel rows x two pixel columns of the bin in flight per thread (four independent 16-byte loads per round trip
     // instead of two: the pass is bound by the latency of its dependent loads times the threads resident).  A missing second row /
     // column re-reads the first one with weight 0; the sum's terms are the same, their order within a 2 x 2 block is not.
@@ -366,41 +357,6 @@ __global__ __launch_bounds__(256, FS_OCC) void roi_align_fwd_sep_kernel(const Ro
         }
       }
     }
-#else
-    for (int ky = 0; ky < ny; ++ky) {
-      const float a = wtab[0][ph][ky];
-      if (a == 0.f) continue;
-      const bf16_t* rowp = f + (plane + (size_t)(y0 + ky) * W + x0) * C + cc * 8;
-      int kx = 0;
-#if FS_PAIR
-      // two pixels of the row in flight per thread (the pass is latency-bound: profiles/r05_pmc_roi.txt); both loads are issued
-      // whatever their weights (every tabulated pixel lies inside the map), the terms are still added in kx order and a zero
-      // weight still adds nothing, so the result keeps its bits
-      for (; kx + 1 < nx; kx += 2) {
-        const float w0 = a * wtab[1][pw][kx], w1 = a * wtab[1][pw][kx + 1];
-        bf16_t v0[8], v1[8];
-        *reinterpret_cast<uint4*>(v0) = *reinterpret_cast<const uint4*>(rowp + (size_t)kx * C);
-        *reinterpret_cast<uint4*>(v1) = *reinterpret_cast<const uint4*>(rowp + (size_t)(kx + 1) * C);
-        if (w0 != 0.f) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[e] += w0 * bf2f(v0[e]);
-        }
-        if (w1 != 0.f) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[e] += w1 * bf2f(v1[e]);
-        }
-      }
-#endif
-      for (; kx < nx; ++kx) {
-        const float wgt = a * wtab[1][pw][kx];
-        if (wgt == 0.f) continue;
-        bf16_t v[8];
-        *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(rowp + (size_t)kx * C);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += wgt * bf2f(v[e]);
-      }
-    }
-#endif
     bf16_t o[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = f2bf(acc[e] * inv_cnt);
@@ -417,10 +373,7 @@ __global__ __launch_bounds__(256, FS_OCC) void roi_align_fwd_sep_kernel(const Ro
 struct RoiSetDev { const float* rois; const int* order; const int* seg; const bf16_t* dout; int P; float gscale; };
 struct RoiSetsDev { RoiSetDev s[4]; int n; };
 
-#ifndef GS_MAXL_V
-#define GS_MAXL_V 256
-#endif
-constexpr int GS_TS = 8, GS_MAXL = GS_MAXL_V, GS_KB = 4, GS_MAXP = 14;
+constexpr int GS_TS = 8, GS_MAXL = 256, GS_KB = 4, GS_MAXP = 14;
 constexpr int GS_STAGE_BYTES = 24576;  // 48 bins of 256 channels
 typedef float gs_f2 __attribute__((ext_vector_type(2)));
 
@@ -429,9 +382,7 @@ typedef float gs_f2 __attribute__((ext_vector_type(2)));
 // the 1.47 ms of the stride-4 level; 17 TB/s of 16-byte loads).  The bin rows a batch of ROIs has in common with the tile are
 // therefore staged in LDS once (coalesced 512-byte rows) and the quads read them from there; a ROI whose bins do not fit
 // the stage (a 14 x 14 mask ROI on a coarse level) keeps reading from L2.
-#ifndef GS_OCC
-#define GS_OCC 4
-#endif
+constexpr int GS_OCC = 4;
 #ifdef GS_TRACE
 // debug build (-DGS_TRACE, tools/exp/roi_gather_trace.sh): shader-clock ticks of thread 0 per phase, summed over the work-groups
 // (one slot per work-group, plain adds: stamps through same-address atomics slowed the kernel six-fold)
@@ -1280,10 +1231,8 @@ extern "C" int u2_roi_align_bwd_gather_sum(void* const* gfeats, const int* Hs, c
     sets.s[i].rois = (const float*)rois[i]; sets.s[i].order = (const int*)order[i]; sets.s[i].seg = (const int*)seg[i];
     sets.s[i].dout = (const bf16_t*)dout[i]; sets.s[i].P = P[i]; sets.s[i].gscale = gscale[i];
   }
-  const char* e_lv = getenv("U2_ROI_LEVEL");  // experiments: launch one level only
-  const int only = e_lv ? atoi(e_lv) : -1;
   for (int l = 0; l < nlevels; ++l) {
-    if ((only >= 0 && l != only) || !((level_mask >> l) & 1) || !gfeats[l]) continue;
+    if (!((level_mask >> l) & 1) || !gfeats[l]) continue;
     const dim3 grid((Ws[l] + 7) / 8, (Hs[l] + 7) / 8, B);
     hipLaunchKernelGGL(roi_align_bwd_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, sets, (bf16_t*)gfeats[l], l,
                        nlevels, Hs[l], Ws[l], C, scales[l], add0 ? (const bf16_t*)add0[l] : nullptr,

@@ -399,7 +399,6 @@ int launch_ws(WsArgs& a, int per_cu, int tiny, int code, hipStream_t s) {
   const int lds_budget = (per_cu == 2 ? 80 : 160) * 1024;
   int ring = lds_budget / STAGE;
   if (ring > 8) ring = 8;
-  if (const char* e = getenv("U2_WSTREAM_RING")) { const int r = atoi(e); if (r >= 2 && r < ring) ring = r; }  // measurement knob
   if (ring < 2) return 0;
   a.ring = ring;
   // pixel ranges: one or two work-groups per CU in total, a multiple of 8 ranges (the tiles of a range share an XCD); never

@@ -204,7 +204,7 @@ def join_aux_stream(device, index=0):
 
 
 # ---- where the stream-K form of the tile kernel may be used (round 6) ----
-# Found with tools/exp/hang_hunt.sh: the driver's bench command hung in 4 of 23 runs (the chip never finished; the host sat in the
+# Recorded in profiles/r06_hang_hunt.txt: the driver's bench command hung in 4 of 23 runs (the chip never finished; the host sat in the
 # step's first synchronisation), in 0 of 24 with the stream-K form forbidden, in 0 of 40 with the branch streams (semantic head, mask
 # head) switched off, and still in 3 of 30 with the stream-K launches of different streams ordered behind each other by events.  So
 # ONE stream-K launch - whose owners spin for peers that the dispatcher has yet to place on a CU, conv_tile.hip - can stall for good
