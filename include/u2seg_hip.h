@@ -503,6 +503,67 @@ typedef struct U2PanopticPairImage {
 int u2_panoptic_pair_counts(const U2PanopticPairImage* images, int n_images, int* out_of_range, void* stream);
 int u2_panoptic_pair_lds_ints(void);
 
+/* ---- COCO AP matching and accumulation (cocoeval.hip): evaluation/cocoeval_ops.py, DESIGN.md section 15 -------------------------
+ * The two stages of COCOeval the reference runs in C++ (layers/csrc/cocoeval/cocoeval.cpp), value for value what
+ * evaluation/cocoeval.py's _match_image and accumulate compute.  Work is organised by cell = an (image, category) pair with at
+ * least one ground truth or one detection; cells are ordered by (category, image position), so that the detections of a
+ * category are one contiguous run of the flat detection arrays.  All pointers of the problem are device pointers.
+ *   cell_dt_off / cell_gt_off / cell_iou_off [n_cells + 1]: first detection / ground truth / IoU entry of every cell; a
+ *     cell's detections are in descending score order (stable), cut to the largest budget; its IoU table is [D'][G].
+ *   dt_area: what the area ranges test (box area, or mask area in the mask form); dt_box / gt_box: xywh float64.
+ *   mask form: IoU of (d, g) from inter[dt_row[d] + gt_col[g]], dt_marea[d], gt_marea[g] (int64 pixel counts).
+ *   gt_crowd: a crowd region (ignored; its union is the detection's area; it can be matched repeatedly).
+ *   perm [n_dt]: position in the flat detection arrays of every entry of the categories' lists, each list in descending score
+ *     order (stable: image position, then rank); cat_dt_off [K + 1] delimits the lists.
+ *   area_rng [A][2], iou_thrs [T], rec_thrs [R], max_dets [M]: the parameters, as the host holds them.
+ * A * T <= 40, A <= 8, R <= 256, max_rank (largest D' of any cell) < 2^23.
+ * u2_cocoeval_match: IoU tables, per-area ground-truth order and the greedy matching, one wave per cell; a cell with more
+ * than u2_cocoeval_lds_iou_entries() IoU entries or more than u2_cocoeval_lds_max_gt() ground truth keeps its table and its
+ * taken-flags in global memory.  rec_match / rec_ignore (both or neither; [n_dt][A * T]): matched column of the cell's
+ * ground truth + 1 (0: none) and the detection-ignored flag.  u2_cocoeval_accumulate (after it, same workspace): precision and
+ * scores [T][R][K][A][M], recall [T][K][A][M], every entry written; integer scans in chunks of u2_cocoeval_scan_chunk().
+ * workspace: u2_cocoeval_workspace_bytes() bytes, 16-byte aligned, no initialisation; u2_cocoeval_workspace_layout also gives
+ * the byte offsets of its parts: [0] IoU tables float64, [1] per-detection flag words, [2] the same in list order, [3] scores
+ * in list order, [4] ground-truth order int32 [cell][A][G], [5] ground-truth ignored uint8 [cell][A][G] in that order,
+ * [6] not-ignored ground truth per (category, area) int32, [7] taken-flags, [8] not-ignored ground truth per (cell, area)
+ * int32, [9] path of every cell uint8 (0 = LDS, 1 = global memory).  It does not grow with T * A * M. */
+typedef struct U2CocoEvalProblem {
+  const long long* cell_dt_off;
+  const long long* cell_gt_off;
+  const long long* cell_iou_off;
+  const int* cell_cat;
+  const double* dt_area;
+  const double* dt_score;
+  const double* dt_box;
+  const long long* dt_row;
+  const long long* dt_marea;
+  const double* gt_area;
+  const double* gt_box;
+  const unsigned char* gt_crowd;
+  const long long* gt_col;
+  const long long* gt_marea;
+  const long long* inter;
+  const int* perm;
+  const long long* cat_dt_off;
+  const double* area_rng;
+  const double* iou_thrs;
+  const double* rec_thrs;
+  const int* max_dets;
+  long long n_cells, n_dt, n_gt, iou_entries;
+  int K, A, T, R, M, mask_form, max_rank, pad_;
+} U2CocoEvalProblem;
+long long u2_cocoeval_workspace_bytes(long long n_dt, long long n_gt, long long iou_entries, long long n_cells, int K, int A,
+                                      int T);
+long long u2_cocoeval_workspace_layout(long long n_dt, long long n_gt, long long iou_entries, long long n_cells, int K, int A,
+                                       int T, long long* offsets /* host [10] */);
+int u2_cocoeval_match(const U2CocoEvalProblem* problem, void* workspace, long long workspace_bytes, int* rec_match,
+                      unsigned char* rec_ignore, void* stream);
+int u2_cocoeval_accumulate(const U2CocoEvalProblem* problem, void* workspace, long long workspace_bytes, double* precision,
+                           double* scores, double* recall, void* stream);
+int u2_cocoeval_lds_iou_entries(void);
+int u2_cocoeval_lds_max_gt(void);
+int u2_cocoeval_scan_chunk(void);
+
 /* ---- optimizer (optim.hip): solver/build.py:36-37,63-73,119-139 ------------------------------- */
 int u2_sgd_clip_step(float* params, const float* grads, float* momentum_buf, const int* chunk_tensor,
                      const long long* chunk_begin, const int* chunk_len, int n_chunks, float* partial /*[n_chunks]*/,

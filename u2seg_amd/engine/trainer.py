@@ -112,6 +112,8 @@ def default_argument_parser():
     p.add_argument("--eval-tasks", default="bbox", help="what the instance evaluator scores: bbox or bbox,segm (mask AP)")
     p.add_argument("--panoptic-pq", default="files", choices=("files", "counts"),
                    help="PQ from the written pngs (files) or from segment-pair counts made on the device (counts)")
+    p.add_argument("--coco-eval", default="host", choices=("host", "device"),
+                   help="AP matching and accumulation in numpy (host) or by the HIP kernels on the GPU (device), same numbers")
     p.add_argument("--eval-gt-polygons", default="refuse", choices=("refuse", "rasterize"),
                    help="polygon ground truth in the segm task: refuse it, or rasterize it as cocoapi does (COCO val2017)")
     p.add_argument("--num-gpus", type=int, default=1)

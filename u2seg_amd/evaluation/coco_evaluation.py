@@ -11,7 +11,8 @@ that task, :352-354, but carries the code for it, :672-679): process() collects,
 (evaluation/mask_ops.py, on the device when the predictions are there), evaluate() turns them into IoU tables.  Ground truth
 stored as polygons (COCO's instances_val2017.json: every non-crowd instance) is refused by default and, with
 gt_polygons="rasterize", rasterised by data/polygon.py's restatement of cocoapi's conversion - on the device next to the
-predictions' planes (csrc/polygon.hip), by the definition itself on a CPU-only evaluator."""
+predictions' planes (csrc/polygon.hip), by the definition itself on a CPU-only evaluator.  coco_eval="device"
+runs cocoeval.py's matching and accumulation stages on the GPU (csrc/cocoeval.hip) with the same results."""
 import itertools
 import json
 import os
@@ -54,12 +55,20 @@ def instances_to_coco_json(instances, img_id, rles=None):
 
 class COCOEvaluator(DatasetEvaluator):
     def __init__(self, dataset_name, output_dir=None, *, mode="hungarian_matching",
-                 mapping_path="./hungarian_matching/instance_mapping.json", tasks=("bbox",), gt_polygons="refuse"):
+                 mapping_path="./hungarian_matching/instance_mapping.json", tasks=("bbox",), gt_polygons="refuse",
+                 coco_eval="host"):
         self._metadata = MetadataCatalog.get(dataset_name)
         self._tasks = tuple(tasks)
         if gt_polygons not in ("refuse", "rasterize"):
             raise ValueError('gt_polygons must be "refuse" or "rasterize", got %r' % (gt_polygons,))
         self._gt_polygons = gt_polygons
+        if coco_eval not in ("host", "device"):
+            raise ValueError('coco_eval must be "host" or "device", got %r' % (coco_eval,))
+        if coco_eval == "device":  # matching and accumulation by csrc/cocoeval.hip: no GPU is an error
+            from . import cocoeval_ops
+
+            cocoeval_ops.require_gpu()
+        self._coco_eval = coco_eval
         if "bbox" not in self._tasks or set(self._tasks) - {"bbox", "segm"}:
             raise ValueError('tasks must be ("bbox",) or ("bbox", "segm"), got %r' % (tasks,))
         self._output_dir = output_dir
@@ -186,14 +195,15 @@ class COCOEvaluator(DatasetEvaluator):
                 pair_counts[p["image_id"]] = {"gt_ids": sp["gt_ids"], "inter": np.asarray(sp["inter"])[rows],
                                               "area_dt": np.asarray(sp["area_dt"])[rows], "area_gt": sp["area_gt"]}
         polygons = self._gt_polygons == "rasterize"
-        return self._metrics(coco_results, lambda ds, rs: cocoeval.evaluate_segm(ds, rs, pair_counts=pair_counts, polygons=polygons))
+        return self._metrics(coco_results, lambda ds, rs: cocoeval.evaluate_segm(ds, rs, pair_counts=pair_counts, polygons=polygons,
+                                                                                 engine=self._coco_eval))
 
     def _box_metrics(self, coco_results):
         """AP, AP50, AP75, APs, APm, APl (x 100, NaN where undefined) and the per-category APs, as _derive_coco_results
         reports them (:473-540; the reference skips the "segm" task, :346-347), from evaluation/cocoeval.py."""
         from . import cocoeval
 
-        return self._metrics(coco_results, cocoeval.evaluate_bbox)
+        return self._metrics(coco_results, lambda ds, rs: cocoeval.evaluate_bbox(ds, rs, engine=self._coco_eval))
 
     def _metrics(self, coco_results, evaluate):
         names = ("AP", "AP50", "AP75", "APs", "APm", "APl")

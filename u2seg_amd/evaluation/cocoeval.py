@@ -185,15 +185,36 @@ def summarize(acc, params):
 STAT_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
 
 
-def evaluate_bbox(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100)):
+ENGINES = ("host", "device")
+
+
+def _checked_engine(engine):
+    """"host": this module's numpy, the definition.  "device": matching and accumulation by csrc/cocoeval.hip through
+    evaluation/cocoeval_ops.py, the same values; without a GPU that is an error, not a fallback."""
+    if engine not in ENGINES:
+        raise ValueError('engine must be "host" or "device", got %r' % (engine,))
+    if engine == "device":
+        from . import cocoeval_ops
+
+        cocoeval_ops.require_gpu()
+    return engine
+
+
+def evaluate_bbox(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100), engine="host"):
     """gt_dataset: the COCO json dict (images, annotations, categories); results: COCO result dicts with xywh boxes.
-    Returns {"stats": {name: value in [0, 1] or -1}, "precision", "recall", "params"}."""
+    engine: see `_checked_engine`.  Returns {"stats": {name: value in [0, 1] or -1}, "precision", "recall", "params"}."""
+    engine = _checked_engine(engine)
     imgs = sorted(im["id"] for im in gt_dataset["images"]) if img_ids is None else sorted(set(img_ids))
     cats = sorted(c["id"] for c in gt_dataset["categories"])
     params = Params(imgs, cats, max_dets)
     gts, dts = prepare(gt_dataset["annotations"], results, params)
-    ious = compute_ious(gts, dts, params)
-    acc = accumulate(evaluate_images(gts, dts, ious, params), params)
+    if engine == "device":
+        from . import cocoeval_ops
+
+        acc = cocoeval_ops.evaluate(gts, dts, params)
+    else:
+        ious = compute_ious(gts, dts, params)
+        acc = accumulate(evaluate_images(gts, dts, ious, params), params)
     return {"stats": dict(zip(STAT_NAMES, summarize(acc, params))), "precision": acc["precision"], "recall": acc["recall"],
             "scores": acc["scores"], "params": params}
 
@@ -239,13 +260,14 @@ def host_pair_counts(gt_dataset, results, img_ids, polygons=False):
     return out
 
 
-def evaluate_segm(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100), pair_counts=None, polygons=False):
+def evaluate_segm(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100), pair_counts=None, polygons=False, engine="host"):
     """Mask AP / AR: `evaluate_bbox` with two differences (the reference's _evaluate_predictions_on_coco with iou_type "segm",
     coco_evaluation.py:672-679, drops "bbox" from the results for the first): a detection's area is its mask area (the
     ground truth keeps ann["area"]), and the IoU tables come from masks.  results: COCO result dicts with an RLE
     "segmentation".  pair_counts: what `host_pair_counts` returns, collected elsewhere (the evaluator does it per batch on the
-    device); None: computed here, with `polygons` as in `host_pair_counts`.  Returns evaluate_bbox's dict plus "ious"
-    {(image, category): [D', G]}."""
+    device); None: computed here, with `polygons` as in `host_pair_counts`.  engine: as in `evaluate_bbox`.  Returns
+    evaluate_bbox's dict plus "ious" {(image, category): [D', G]}."""
+    engine = _checked_engine(engine)
     imgs = sorted(im["id"] for im in gt_dataset["images"]) if img_ids is None else sorted(set(img_ids))
     cats = sorted(c["id"] for c in gt_dataset["categories"])
     params = Params(imgs, cats, max_dets)
@@ -259,6 +281,15 @@ def evaluate_segm(gt_dataset, results, img_ids=None, max_dets=(1, 10, 100), pair
         pc = pair_counts.get(res["image_id"])
         dt_areas.append(int(pc["area_dt"][k]) if pc is not None else 0)
     gts, dts = prepare(gt_dataset["annotations"], results, params, dt_areas)
+    if engine == "device":
+        from . import cocoeval_ops
+
+        acc = cocoeval_ops.evaluate(gts, dts, params, pair_counts, row, ious=True)
+        packed, ious = acc["packed"], {(img, cat): [] for img in params.imgIds for cat in params.catIds}
+        for c in range(packed.n_cells):
+            ious[packed.cell_key(c)] = cocoeval_ops.cell_ious(packed, acc["records"], c)
+        return {"stats": dict(zip(STAT_NAMES, summarize(acc, params))), "precision": acc["precision"], "recall": acc["recall"],
+                "scores": acc["scores"], "params": params, "ious": ious}
     ious = {}
     for img in params.imgIds:
         pc = pair_counts.get(img)
