@@ -1,4 +1,5 @@
-// Argument block and staging helpers shared by the implicit-GEMM convolution kernels (conv_igemm.hip, conv_tile.hip).
+// Argument block, staging and LDS-layout helpers shared by the convolution kernels (conv_igemm.hip, conv_tile.hip, conv_halo.hip,
+// conv_stream.hip, wgrad_halo.hip, wgrad_stream.hip).
 #pragma once
 #include "common.h"
 
@@ -45,6 +46,28 @@ __device__ __forceinline__ void glds16(const bf16_t* src, void* lds_dst_wave_bas
   __builtin_amdgcn_global_load_lds(U2_GLB_PTR(src), U2_LDS_PTR(lds_dst_wave_base), 16, 0, 0);
 }
 
+// XOR applied to the 16-byte chunk index of pixel row `pix` of a step image with rows of RB bytes.  A half-wave of
+// ds_read_b64_tr_b16 reads 32 bytes (one chunk pair) of each of the pixels {P .. P+3, P+8 .. P+11}; the eight pieces must cover
+// the 64 banks once.  RB >= 256: every row starts a bank row, eight different pairs (bits 1-3); RB = 128: two rows per bank
+// row, the four rows of equal parity need four different pairs for every start P (the taps of wgrad_halo.hip shift P by 0..2):
+// bits 1 and 3 of the pixel index do that; RB = 64: four rows per bank row, rows P + k and P + 8 + k need different pairs.
+template <int RB> __device__ __forceinline__ int tr_swz(int pix) {
+  if constexpr (RB >= 256) return ((pix & 3) << 1) | (pix & 8);
+  else if constexpr (RB == 128) return (((pix >> 1) & 1) | (((pix >> 3) & 1) << 1)) << 1;
+  else return ((pix >> 3) & 1) << 1;
+}
+
+// The transposing read as inline asm (through the builtin the compiler assumes that an LDS read may alias the LDS-DMA writes
+// in flight and drains them), and the two reads that make one MFMA operand.
+template <int IMM = 0> __device__ __forceinline__ unsigned long long tr_read(unsigned addr) {
+  unsigned long long r;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(IMM) : "memory");
+  return r;
+}
+union Frag {
+  unsigned long long u[2];
+  s16x8 v;
+};
 
 // Which kernel the most recent u2_conv_igemm / u2_conv_wgrad launch selected (u2_conv_last_kernel, a test / debugging aid):
 //   conv_tile_kernel configuration k -> 100 + k;  conv_igemm256_kernel -> 256 (+ 1024 staggered);

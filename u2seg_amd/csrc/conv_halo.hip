@@ -30,50 +30,6 @@
 namespace u2conv {
 namespace {
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-// see conv_tile.hip: transposing reduction over the 16 lanes of a DPP row; lane fr leaves with the row total of v[fr]
-__device__ __forceinline__ float row16_transpose_sum(float (&v)[16], int fr) {
-  {
-    const bool up = fr & 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float keep = up ? v[k + 8] : v[k], send = up ? v[k] : v[k + 8];
-      v[k] = keep + dpp_mov<0x128>(send);
-    }
-  }
-  {
-    const bool up = fr & 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float keep = up ? v[k + 4] : v[k], send = up ? v[k] : v[k + 4];
-      v[k] = keep + dpp_mov<0x141>(send);
-    }
-  }
-  {
-    const bool up = fr & 2;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float keep = up ? v[k + 2] : v[k], send = up ? v[k] : v[k + 2];
-      v[k] = keep + dpp_mov<0x4E>(send);
-    }
-  }
-  const bool up = fr & 1;
-  const float keep = up ? v[1] : v[0], send = up ? v[0] : v[1];
-  return keep + dpp_mov<0xB1>(send);
-}
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-  const f32x2_t v = {lo, hi};
-  const bf16x2_t r = __builtin_convertvector(v, bf16x2_t);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
-
 // output patch of a work-group: PH rows x PWD columns = 512 pixels, 16 x 32 (template default) or 8 x 64 (maps whose height
 // fills 16-row patches badly); halo row pitch PWD + 4 pixels (a multiple of 4; PH + 2 rows x PWD + 2 columns used)
 constexpr int HBUF = 49152;              // one halo buffer: 768 rows of 64 B (648 / 680 used)

@@ -694,10 +694,7 @@ struct WgradArgs {
 
 constexpr int WP = 32;  // pixels per reduction step
 
-// XOR swizzle of the 16-byte chunk index of the wgrad LDS image [32 px][16 chunks].  A half-wave of a
-// ds_read_b64_tr_b16 touches pixels {4h..4h+3, 8+4h..8+4h+3} x one 32-byte chunk pair; mapping those 8 pixels to 8
-// different chunk pairs (bits 1-3) makes the 8 x 32 B of a half-wave cover one 256-byte bank row exactly.
-__device__ __forceinline__ int wg_swz(int pix) { return ((pix & 3) << 1) | (pix & 8); }
+// The wgrad LDS image is [32 px][16 chunks of 16 bytes], chunk index XOR-swizzled by tr_swz<256>(pix) (conv_args.h).
 
 template <bool GLDS, bool TR, int RING = 2>
 __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const WgradArgs a) {
@@ -752,7 +749,7 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const WgradArgs a) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int pix = (i * 4 + w) * 4 + pix_in_instr;
-      const int cc = slot ^ wg_swz(pix);
+      const int cc = slot ^ tr_swz<256>(pix);
       const int m = cm[i];
       const bool mok = m < mend;
       const bf16_t* ysrc = (mok && n0 + cc * 8 < a.N) ? a.dy + (size_t)m * a.dy_ld + n0 + cc * 8 : a.zero;
@@ -810,7 +807,7 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const WgradArgs a) {
   const int fr = lane & 15, fg = lane >> 4;
 
   // Fragment for a 16-channel block starting at ch0: lane gets, for channel ch0+fr, the 8 pixels 8*fg .. 8*fg+7 of the
-  // step.  LDS image: [pix][128 ch] bf16, 16-byte chunks XOR-swizzled by wg_swz(pix).  All byte offsets are loop
+  // step.  LDS image: [pix][128 ch] bf16, 16-byte chunks XOR-swizzled by tr_swz<256>(pix).  All byte offsets are loop
   // invariant and computed once.
   // The 16-channel block index q only occupies bits 1-2 of the 16-byte chunk number (disjoint from the bits set by
   // wr and the lane), so offset(q) = offset(0) ^ (q << 5): two base offsets per operand instead of a table.
@@ -823,8 +820,8 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const WgradArgs a) {
     const int pix = TR ? fg * 8 + e * 4 + (fr >> 2) : fg * 8 + e;
     const int chl = TR ? (fr & 3) * 4 : fr;
     const int chy = wr * 64 + chl, chx = wc * 64 + chl;
-    yoff0[e] = pix * 256 + (((chy >> 3) ^ wg_swz(pix)) << 4) + (chy & 7) * 2;
-    xoff0[e] = pix * 256 + (((chx >> 3) ^ wg_swz(pix)) << 4) + (chx & 7) * 2;
+    yoff0[e] = pix * 256 + (((chy >> 3) ^ tr_swz<256>(pix)) << 4) + (chy & 7) * 2;
+    xoff0[e] = pix * 256 + (((chx >> 3) ^ tr_swz<256>(pix)) << 4) + (chx & 7) * 2;
   }
   // GLDS + TR: the transposing reads are inline asm.  Through the builtin the compiler assumes every LDS read may alias
   // the LDS-DMA writes in flight and drains them (vmcnt(0)) right after they are issued, i.e. the next step's loads
@@ -835,12 +832,9 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const WgradArgs a) {
   auto load_frag = [&](const unsigned char* base, const int* off0, int q) -> s16x8 {
     s16x8 r;
     if constexpr (ASM_TR) {
-      union { unsigned long long u[2]; s16x8 v; } rr;
+      Frag rr;
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const unsigned addr = lds0 + (unsigned)(base - smem) + (unsigned)(off0[h] ^ (q << 5));
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(rr.u[h]) : "v"(addr) : "memory");
-      }
+      for (int h = 0; h < 2; ++h) rr.u[h] = tr_read(lds0 + (unsigned)(base - smem) + (unsigned)(off0[h] ^ (q << 5)));
       r = rr.v;
     } else if constexpr (TR) {
 #pragma unroll
@@ -992,7 +986,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad256_kernel(const WgradArgs a
 
   // staging: wave w moves pixels 4w .. 4w+3 of the step (16 chunks each) of all four images
   const int pix = w * 4 + (lane >> 4);
-  const int cc = (lane & 15) ^ wg_swz(pix);
+  const int cc = (lane & 15) ^ tr_swz<256>(pix);
   int cm = mbeg + pix, cimg, coy, cox;
   {
     cimg = cm / hw;
@@ -1052,11 +1046,11 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad256_kernel(const WgradArgs a
     const int px = fg * 8 + e * 4 + (fr >> 2);
     const int chl = (fr & 3) * 4;
     const int chy = (wr & 1) * 64 + chl;
-    yoff0[e] = (wr >> 1) * WG256_IMG + px * 256 + (((chy >> 3) ^ wg_swz(px)) << 4) + (chy & 7) * 2;
+    yoff0[e] = (wr >> 1) * WG256_IMG + px * 256 + (((chy >> 3) ^ tr_swz<256>(px)) << 4) + (chy & 7) * 2;
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
       const int chx = hh * 64 + chl;
-      xoff0[hh][e] = (2 + wc) * WG256_IMG + px * 256 + (((chx >> 3) ^ wg_swz(px)) << 4) + (chx & 7) * 2;
+      xoff0[hh][e] = (2 + wc) * WG256_IMG + px * 256 + (((chx >> 3) ^ tr_swz<256>(px)) << 4) + (chx & 7) * 2;
     }
   }
   // The transposing reads are issued as inline asm: for the builtin the compiler assumes that an LDS read may alias the
@@ -1064,12 +1058,9 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad256_kernel(const WgradArgs a
   // synchronous load.  Ordering is explicit instead: counted vmcnt + barrier before the reads, lgkmcnt(0) after them.
   const unsigned lds0 = (unsigned)(size_t)U2_LDS_PTR(smem);
   auto load_frag = [&](unsigned base, const int* off0, int q) -> s16x8 {
-    union { unsigned long long u[2]; s16x8 v; } r;
+    Frag r;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const unsigned addr = base + (unsigned)(off0[h] ^ (q << 5));
-      asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r.u[h]) : "v"(addr) : "memory");
-    }
+    for (int h = 0; h < 2; ++h) r.u[h] = tr_read(base + (unsigned)(off0[h] ^ (q << 5)));
     return r.v;
   };
   auto compute = [&](int buf) {

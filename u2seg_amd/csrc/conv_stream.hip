@@ -25,53 +25,11 @@
 namespace u2conv {
 namespace {
 
-template <int CTRL> __device__ __forceinline__ float dpp_mov_s(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-// conv_tile.hip: transposing reduction over the 16 lanes of a DPP row; lane fr leaves with the row total of v[fr]
-__device__ __forceinline__ float row16_transpose_sum_s(float (&v)[16], int fr) {
-  {
-    const bool up = fr & 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float keep = up ? v[k + 8] : v[k], send = up ? v[k] : v[k + 8];
-      v[k] = keep + dpp_mov_s<0x128>(send);
-    }
-  }
-  {
-    const bool up = fr & 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float keep = up ? v[k + 4] : v[k], send = up ? v[k] : v[k + 4];
-      v[k] = keep + dpp_mov_s<0x141>(send);
-    }
-  }
-  {
-    const bool up = fr & 2;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float keep = up ? v[k + 2] : v[k], send = up ? v[k] : v[k + 2];
-      v[k] = keep + dpp_mov_s<0x4E>(send);
-    }
-  }
-  const bool up = fr & 1;
-  const float keep = up ? v[1] : v[0], send = up ? v[0] : v[1];
-  return keep + dpp_mov_s<0xB1>(send);
-}
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_s;
-typedef __attribute__((ext_vector_type(2))) float f32x2_s;
-__device__ __forceinline__ uint32_t pack_bf16_s(float lo, float hi) {
-  const f32x2_s v = {lo, hi};
-  const bf16x2_s r = __builtin_convertvector(v, bf16x2_s);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
-
 // XOR applied to the 16-byte chunk index of LDS row `row` (rows of RB bytes): conflict-free ds_read_b128 fragment reads
 // (16 rows x 4 chunks per instruction) - checked by brute force over the four lane groups of MI355X_MICROARCH.md's LDS table
 template <int RB> __device__ __forceinline__ int row_swz(int row) {
-  if constexpr (RB == 64) return (-(row >> 2)) & 3;
-  else if constexpr (RB == 128) return (row >> 1) & 7;
+  if constexpr (RB == 64) return swz<32>(row);  // 32 channels = 64 bytes: the tile kernels' layout
+  else if constexpr (RB == 128) return (row >> 1) & 7;  // not swz<64> (row & 7): another layout for the same row length
   else return row & 15;
 }
 
@@ -91,8 +49,6 @@ template <int CNT, int NF> __device__ __forceinline__ void lds_wait_frags(s16x8 
 #pragma unroll
   for (int j = 0; j < NF; ++j) asm volatile("" : "+v"(pf[j])::"memory");
 }
-
-template <int N> __device__ __forceinline__ void wait_vm_s() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // KS: 32-channel slabs of the reduction (C = 32 KS); TM: pixels per tile; PSW: waves along the pixels (NWV / PSW along the
 // channels, 64 each); NWV: waves per work-group (4: two groups per CU, 8: one); KSS: slabs per ring step - a tile arrives in
@@ -204,9 +160,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
   // makes the wait-count pass drain the LDS-DMA queue in front of the next fragment read)
   auto epilogue = [&](int ti) {
     const int m0 = (first_tile + ti * nwalk) * TM + psw * WPX;
-    f32x2_s s2[8], ss2[8];
+    f32x2_t s2[8], ss2[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s2[e] = f32x2_s{0.f, 0.f}; ss2[e] = f32x2_s{0.f, 0.f}; }
+    for (int e = 0; e < 8; ++e) { s2[e] = f32x2_t{0.f, 0.f}; ss2[e] = f32x2_t{0.f, 0.f}; }
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
       const int m = m0 + j * 16 + fr;
@@ -217,13 +173,13 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
         float v0 = acc[i][j][0] + bia[i][0], v1 = acc[i][j][1] + bia[i][1];
         float v2 = acc[i][j][2] + bia[i][2], v3 = acc[i][j][3] + bia[i][3];
         if (a.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-        pk[2 * i] = pack_bf16_s(v0, v1);
-        pk[2 * i + 1] = pack_bf16_s(v2, v3);
+        pk[2 * i] = pack_bf16(v0, v1);
+        pk[2 * i + 1] = pack_bf16(v2, v3);
       }
       if (do_stats && row_ok) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const f32x2_s v = {__uint_as_float(pk[e] << 16), __uint_as_float(pk[e] & 0xffff0000u)};
+          const f32x2_t v = {__uint_as_float(pk[e] << 16), __uint_as_float(pk[e] & 0xffff0000u)};
           s2[e] += v;
           ss2[e] = __builtin_elementwise_fma(v, v, ss2[e]);
         }
@@ -239,8 +195,8 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
       float s[16], ss[16];
 #pragma unroll
       for (int e = 0; e < 8; ++e) { s[2 * e] = s2[e][0]; s[2 * e + 1] = s2[e][1]; ss[2 * e] = ss2[e][0]; ss[2 * e + 1] = ss2[e][1]; }
-      st_s += row16_transpose_sum_s(s, fr);
-      st_ss += row16_transpose_sum_s(ss, fr);
+      st_s += row16_transpose_sum(s, fr);
+      st_ss += row16_transpose_sum(ss, fr);
     }
   };
 
@@ -260,13 +216,13 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
       int nd = G - 1 - g;
       if (nd > ring - 2) nd = ring - 2;
       switch (nd) {
-        case 0: wait_vm_s<0>(); break;
-        case 1: wait_vm_s<PPW>(); break;
-        case 2: wait_vm_s<2 * PPW>(); break;
-        case 3: wait_vm_s<3 * PPW>(); break;
-        case 4: wait_vm_s<4 * PPW>(); break;
-        case 5: wait_vm_s<5 * PPW>(); break;
-        default: wait_vm_s<6 * PPW>(); break;
+        case 0: wait_vm<0>(); break;
+        case 1: wait_vm<PPW>(); break;
+        case 2: wait_vm<2 * PPW>(); break;
+        case 3: wait_vm<3 * PPW>(); break;
+        case 4: wait_vm<4 * PPW>(); break;
+        case 5: wait_vm<5 * PPW>(); break;
+        default: wait_vm<6 * PPW>(); break;
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -65,60 +65,12 @@ __device__ unsigned long long* g_tile_sub_dev = nullptr;
 #define U2_SUBK(K) do { } while (0)
 #endif
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-// Transposing reduction over the 16 lanes of a DPP row (lanes sharing lane >> 4): every lane enters with 16 partial sums
-// v[0..15]; lane fr leaves with the row total of v[fr].  Four exchange steps, each halving the values a lane carries
-// (the lane keeps the half selected by one bit of fr and adds its partner's copy of that half): 15 adds instead of the 64
-// of an all-reduce, and the totals end up one per lane, which is what a full-wave atomic wants.
-__device__ __forceinline__ float row16_transpose_sum(float (&v)[16], int fr) {
-  {
-    const bool up = fr & 8;  // partner fr ^ 8 (row_ror:8)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float keep = up ? v[k + 8] : v[k], send = up ? v[k] : v[k + 8];
-      v[k] = keep + dpp_mov<0x128>(send);
-    }
-  }
-  {
-    const bool up = fr & 4;  // partner fr ^ 7 (row_half_mirror): same bit 3, opposite bit 2
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float keep = up ? v[k + 4] : v[k], send = up ? v[k] : v[k + 4];
-      v[k] = keep + dpp_mov<0x141>(send);
-    }
-  }
-  {
-    const bool up = fr & 2;  // partner fr ^ 2 (quad_perm [2,3,0,1])
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float keep = up ? v[k + 2] : v[k], send = up ? v[k] : v[k + 2];
-      v[k] = keep + dpp_mov<0x4E>(send);
-    }
-  }
-  const bool up = fr & 1;    // partner fr ^ 1 (quad_perm [1,0,3,2])
-  const float keep = up ? v[1] : v[0], send = up ? v[0] : v[1];
-  return keep + dpp_mov<0xB1>(send);
-}
-
 // m / d and m % d for 0 <= m < 2^24 through one float multiply (inv = 1.0f / d) and a +-1 correction
 __device__ __forceinline__ void divmod_f(int m, int d, float inv, int& q, int& r) {
   q = (int)((float)m * inv);
   r = m - q * d;
   if (r < 0) { --q; r += d; }
   if (r >= d) { ++q; r -= d; }
-}
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-// two floats -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-  const f32x2_t v = {lo, hi};
-  const bf16x2_t r = __builtin_convertvector(v, bf16x2_t);
-  return *reinterpret_cast<const uint32_t*>(&r);
 }
 
 // ACC: out = act(bf16(conv + bias) + out) - the epilogue reads what it overwrites (a residual block's tail at inference)

@@ -301,14 +301,7 @@ __global__ __launch_bounds__(256) void csplit_kernel(const float* __restrict__ c
   }
 }
 
-typedef __attribute__((ext_vector_type(2))) __bf16 ks_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float ks_f32x2;
-__device__ __forceinline__ uint32_t ks_pack(float lo, float hi) {  // v_cvt_pk_bf16_f32, round to nearest even
-  const ks_f32x2 v = {lo, hi};
-  const ks_bf16x2 r = __builtin_convertvector(v, ks_bf16x2);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
-__device__ __forceinline__ int ks_swz(int row) { return (-(row >> 2)) & 3; }  // 64-byte rows: conflict-free ds_read_b128
+__device__ __forceinline__ int ks_swz(int row) { return (-(row >> 2)) & 3; }  // 64-byte rows: conflict-free ds_read_b128 (conv_args.h's swz<32>)
 // v_min_f32 / v_max_f32 as they are: fminf / fmaxf on a value that went through integer instructions get a canonicalising v_max_f32 v, v, v
 // in front (a fifth of the arg-min's instructions); a signalling NaN cannot come out of an fma, and every NaN case goes by the margin
 __device__ __forceinline__ float kc_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
@@ -627,8 +620,8 @@ __global__ __launch_bounds__(512) void kmeans_screen_kernel(const float* __restr
       for (int e = 0; e < 4; ++e) {
         const float v0 = raw[m][e >> 1][(e & 1) * 2], v1 = raw[m][e >> 1][(e & 1) * 2 + 1];
         n2[m] += v0 * v0 + v1 * v1;
-        h[e] = ks_pack(v0, v1);
-        if constexpr (NP == 3) l[e] = ks_pack(v0 - __uint_as_float(h[e] << 16), v1 - __uint_as_float(h[e] & 0xffff0000u));
+        h[e] = pack_bf16(v0, v1);
+        if constexpr (NP == 3) l[e] = pack_bf16(v0 - __uint_as_float(h[e] << 16), v1 - __uint_as_float(h[e] & 0xffff0000u));
         else l[e] = 0u;
       }
       ah[m] = *reinterpret_cast<const s16x8*>(h);

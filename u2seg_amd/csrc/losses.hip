@@ -234,12 +234,6 @@ __global__ __launch_bounds__(256) void scale_to_bf16_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------------
 constexpr int SC_ROWS = 0, SC_ACC = 1, SC_FG = 2, SC_FG_ACC = 3, SC_FN = 4;
 
-__device__ __forceinline__ int wave_min_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 struct CeCounts {
   int n[5] = {0, 0, 0, 0, 0};
   // best: the lowest column holding the row's maximum (INT_MAX when no column compared equal: a row of -inf, argmax 0)
@@ -314,7 +308,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const bf16_t* __restric
           const int c = (it * 64 + lane) * 8 + e;
           if (c < NC && v[it][e] == mx) best = c;  // (walked downwards: the lane's lowest such column stays)
         }
-      best = wave_min_int(best);
+      best = wave_imin(best);
     }
     float se = 0.f;
 #pragma unroll
@@ -358,7 +352,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const bf16_t* __restric
   if constexpr (STATS) {
     for (int c = lane; c < NC && best == 0x7fffffff; c += 64)
       if (bf2f(zr[c]) == mx) best = c;
-    best = wave_min_int(best);
+    best = wave_imin(best);
   }
   float se = 0.f;
   for (int c = lane; c < NC; c += 64) se += __expf(bf2f(zr[c]) - mx);

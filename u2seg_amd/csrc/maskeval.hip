@@ -14,22 +14,6 @@ constexpr int ME_MAXIMG = 64;
 struct MaskBatch { U2MaskImage im[ME_MAXIMG]; };
 struct PairBatch { U2PairImage im[ME_MAXIMG]; };
 
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_imin(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_imax(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // ---- canvases -> planes ------------------------------------------------------------------------------------------------
 // One work-group per (strip of 256 columns, mask); it walks the mask's 64-row bands.  A band's rows are fetched as aligned
 // 16-byte pieces (a row starts at any byte: W is arbitrary) and stored in LDS at the same alignment, so row r sits shifted by

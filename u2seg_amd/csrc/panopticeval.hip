@@ -20,12 +20,6 @@ constexpr int PQ_LDS_TABLE = 1024;               // ground-truth ids searched in
 constexpr int PQ_LDS_COUNTS = 15 * 1024;         // table entries accumulated in LDS: 60 KB + 4 KB of ids = 64 KB, two work-groups per CU
 struct PairCountBatch { U2PanopticPairImage im[PQ_MAXIMG]; };
 
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // row of a ground-truth id: 0 = void, 1 + its index in the ascending table, G + 1 = not listed
 template <class T>
 __device__ __forceinline__ int pq_row(T tab, int G, int id) {

@@ -113,15 +113,6 @@ __device__ __forceinline__ void mp_load_coef(const float* __restrict__ a, int c,
 #pragma unroll
   for (int e = 0; e < 8; ++e) v[e] = a[c + e];
 }
-// two floats -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32: one instruction where f2bf is seven; these passes
-// are VALU-bound - the first form of the forward pass spent 1 200 instructions per 16-byte item and ran at 1.8 TB/s)
-typedef __attribute__((ext_vector_type(2))) __bf16 mp_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float mp_f32x2;
-__device__ __forceinline__ uint32_t mp_pack(float lo, float hi) {
-  const mp_f32x2 v = {lo, hi};
-  const mp_bf16x2 r = __builtin_convertvector(v, mp_bf16x2);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
 
 // Forward.  The activation of a tap is >= 0 (ReLU), so its bf16 pattern orders like an unsigned integer: the running maximum and
 // its slot are ONE v_max_u32 on key = pattern << 4 | (8 - slot) - among equal values the lowest slot wins, max_pool2d's rule and
@@ -162,7 +153,7 @@ __global__ __launch_bounds__(256) void affine_relu_maxpool_fwd_kernel(const bf16
       for (int e2 = 0; e2 < 4; ++e2) {
         const float f0 = fmaxf(__uint_as_float(v[e2] << 16) * sc[2 * e2] + sh[2 * e2], 0.f);
         const float f1 = fmaxf(__uint_as_float(v[e2] & 0xffff0000u) * sc[2 * e2 + 1] + sh[2 * e2 + 1], 0.f);
-        const uint32_t pk = mp_pack(f0, f1) & 0x7fff7fffu;   // the activation as affine_act stores it
+        const uint32_t pk = pack_bf16(f0, f1) & 0x7fff7fffu;   // the activation as affine_act stores it
         key[2 * e2] = max(key[2 * e2], ((pk << 4) & 0xffff0u) | code);
         key[2 * e2 + 1] = max(key[2 * e2 + 1], ((pk >> 12) & 0xffff0u) | code);
       }
@@ -267,7 +258,7 @@ __global__ __launch_bounds__(256) void affine_relu_maxpool_bwd_kernel(const bf16
       uint32_t o[4];
 #pragma unroll
       for (int e2 = 0; e2 < 4; ++e2) {
-        const uint32_t gp = mp_pack(g[2 * e2], g[2 * e2 + 1]);   // the gradient map as maxpool_bwd_kernel stores it
+        const uint32_t gp = pack_bf16(g[2 * e2], g[2 * e2 + 1]);   // the gradient map as maxpool_bwd_kernel stores it
         float dz[2] = {__uint_as_float(gp << 16), __uint_as_float(gp & 0xffff0000u)};
         const float xf[2] = {__uint_as_float(xv[e2] << 16), __uint_as_float(xv[e2] & 0xffff0000u)};
         float r[2];
@@ -282,7 +273,7 @@ __global__ __launch_bounds__(256) void affine_relu_maxpool_bwd_kernel(const bf16
             s1[e] += dz[h] * (xf[h] - a1[e]) * a2[e];
           }
         }
-        if (APPLY) o[e2] = mp_pack(r[0], r[1]);
+        if (APPLY) o[e2] = pack_bf16(r[0], r[1]);
       }
       if (APPLY) {
         const int iy = 2 * a + (p >> 1), ix = 2 * c + (p & 1);

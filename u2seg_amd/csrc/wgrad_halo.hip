@@ -50,26 +50,9 @@ constexpr int STAGE = YB + 16 * 1024;   // 3 runs = 15 wave-wide loads + 1 idle 
 constexpr int RING = 4;
 constexpr int LOADS = 3;                // LDS-DMA instructions per wave per step
 
-// 16-byte chunk swizzles.  dY image (256-byte rows): a half-wave of ds_read_b64_tr_b16 touches pixels {P..P+3, P+8..P+11} x
-// one 32-byte chunk pair; XOR-ing the chunk index with this makes the eight 32-byte pieces cover all 64 banks once.
-__device__ __forceinline__ int y_swz(int pix) { return ((pix & 3) << 1) | (pix & 8); }
-// input runs (128-byte rows, two pixels per bank row): pixels of equal parity must get four different chunk pairs, for
-// every start P (the taps shift P by 0..2): bits 1 and 3 of the pixel index do that.
-__device__ __forceinline__ int x_swz(int p) { return (((p >> 1) & 1) | (((p >> 3) & 1) << 1)) << 1; }
-
-template <int IMM>
-__device__ __forceinline__ unsigned long long tr_read(unsigned addr) {
-  unsigned long long r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(IMM) : "memory");
-  return r;
-}
-
-union Frag {
-  unsigned long long u[2];
-  s16x8 v;
-};
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+using u2conv::Frag;
+using u2conv::tr_read;
+using u2conv::tr_swz;  // dY image: 256-byte rows, input runs: 128-byte rows (two pixels per bank row)
 
 // 512 threads: 8 waves of 64(n) x 16(c) x 9 taps (144 accumulator registers), two waves per SIMD
 __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const WgradHaloArgs a) {
@@ -103,7 +86,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const WgradHaloArg
   bool d_on;
   {
     const int pix = w * 4 + (lane >> 4);
-    const int cc = (lane & 15) ^ y_swz(pix);
+    const int cc = (lane & 15) ^ tr_swz<256>(pix);
     const int q = qbeg + pix;
     const int gy = q / Wp;
     d_x = q - gy * Wp;
@@ -121,7 +104,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const WgradHaloArg
     const int k = w + 8 * jj;
     const int g = k % 5, dy = k / 5 - 1;
     const int p = g * 8 + (lane >> 3);
-    const int cc = (lane & 7) ^ x_swz(p);
+    const int cc = (lane & 7) ^ tr_swz<128>(p);
     x_on[jj] = k < 15 && p < 34 && c0 + cc * 8 < a.C;
     const int t = qbeg - 1 + p + Wp;  // >= 0; one row added so that the division never sees a negative number
     const int gy = t / Wp - 1;        // global row img * H + y of the dy = 0 position (-1 for the position before q = 0)
@@ -179,13 +162,13 @@ __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const WgradHaloArg
     const int pix = fg * 8 + h * 4 + (fr >> 2);
     {
       const int ch = wr * 64 + (fr & 3) * 4;
-      yoff[h] = pix * 256 + (((ch >> 3) ^ y_swz(pix)) << 4) + (ch & 7) * 2;
+      yoff[h] = pix * 256 + (((ch >> 3) ^ tr_swz<256>(pix)) << 4) + (ch & 7) * 2;
     }
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
       const int p = pix + dx;  // run position of tap column dx (offset dx - 1) for output pixel `pix`: pix + 1 + (dx - 1)
       const int ch = wc * 16 + (fr & 3) * 4;
-      xoff[dx][h] = lds0 + YB + p * 128 + (((ch >> 3) ^ x_swz(p)) << 4) + (ch & 7) * 2;
+      xoff[dx][h] = lds0 + YB + p * 128 + (((ch >> 3) ^ tr_swz<128>(p)) << 4) + (ch & 7) * 2;
     }
   }
 

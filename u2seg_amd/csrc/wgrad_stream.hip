@@ -50,34 +50,12 @@ struct WsArgs {
 // the expression of norm.hip's apply kernels, spelled the same way (same contraction by the compiler)
 __device__ __forceinline__ float ws_apply(float a1, float dz, float a2, float xf, float a3) { return a1 * dz + a2 * xf + a3; }
 
-// XOR applied to the 16-byte chunk index of pixel row `pix` of a step image with rows of RB bytes.  A half-wave of
-// ds_read_b64_tr_b16 reads 32 bytes (one chunk pair) of each of the pixels {P .. P+3, P+8 .. P+11}; the eight pieces must cover
-// the 64 banks once.  RB >= 256: every row starts a bank row, eight different pairs (wgrad_halo.hip y_swz); RB = 128: two rows
-// per bank row, the four rows of equal parity need four different pairs (x_swz); RB = 64: four rows per bank row, rows P + k and
-// P + 8 + k need different pairs.
-template <int RB> __device__ __forceinline__ int ws_swz(int pix) {
-  if constexpr (RB >= 256) return ((pix & 3) << 1) | (pix & 8);
-  else if constexpr (RB == 128) return (((pix >> 1) & 1) | (((pix >> 3) & 1) << 1)) << 1;
-  else return ((pix >> 3) & 1) << 1;
-}
-
-__device__ __forceinline__ unsigned long long ws_tr_read(unsigned addr) {
-  unsigned long long r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-  return r;
-}
-union WsFrag {
-  unsigned long long u[2];
-  s16x8 v;
-};
-template <int N> __device__ __forceinline__ void ws_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // The MFMAs of column j (FN of them: every dY fragment against X fragment j) behind a counted wait: the X fragments were
 // requested in order after the dY fragments and LDS returns in order, so column j only needs the 2 (FC - 1 - j) youngest reads to
 // be outstanding still - the reads of the later columns land while the earlier columns multiply.
 // EXTRA: LDS reads issued BEHIND the X fragments that may stay outstanding throughout (the fused data gradient's first fragments).
 template <int FN, int FC, int EXTRA = 0, int J = 0>
-__device__ __forceinline__ void ws_mfma_columns(f32x4 (&acc)[FN][FC], WsFrag (&yf)[FN], WsFrag (&xf)[FC]) {
+__device__ __forceinline__ void ws_mfma_columns(f32x4 (&acc)[FN][FC], Frag (&yf)[FN], Frag (&xf)[FC]) {
   if constexpr (J < FC) {
     static_assert(2 * (FC - 1) + EXTRA <= 15, "lgkmcnt is a 4-bit counter");
     asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * (FC - 1 - J) + EXTRA) : "memory");
@@ -144,7 +122,7 @@ __global__ __launch_bounds__(WN * WC * 64, (WN * WC == 4 ? 2 : 1)) void wgrad_st
     const int piece = is_y ? (p < PY ? p : p - PY) : p - PYS;
     const int row = piece * (1024 / rb) + lane / cpr;
     const int pos = lane % cpr;
-    const int chunk = is_y ? (pos ^ ws_swz<RBY>(row)) : (pos ^ ws_swz<RBX>(row));
+    const int chunk = is_y ? (pos ^ tr_swz<RBY>(row)) : (pos ^ tr_swz<RBX>(row));
     const int ch = (is_y ? n0 : c0) + chunk * 8;
     const bool ok = p < PT && ch < (is_y ? a.N : a.C);
     d_row[q] = (row & 255) | (ok ? 0 : 256);
@@ -177,8 +155,8 @@ __global__ __launch_bounds__(WN * WC * 64, (WN * WC == 4 ? 2 : 1)) void wgrad_st
   for (int h = 0; h < 2; ++h) {
     const int pix = fg * 8 + h * 4 + (fr >> 2);
     const int chy = wn * FN * 16 + (fr & 3) * 4, chx = wc * FC * 16 + (fr & 3) * 4;
-    yoff[h] = (unsigned)(pix * RBY + (((chy >> 3) ^ ws_swz<RBY>(pix)) << 4) + (chy & 7) * 2);
-    xoff[h] = (unsigned)(PYS * 1024 + pix * RBX + (((chx >> 3) ^ ws_swz<RBX>(pix)) << 4) + (chx & 7) * 2);
+    yoff[h] = (unsigned)(pix * RBY + (((chy >> 3) ^ tr_swz<RBY>(pix)) << 4) + (chy & 7) * 2);
+    xoff[h] = (unsigned)(PYS * 1024 + pix * RBX + (((chx >> 3) ^ tr_swz<RBX>(pix)) << 4) + (chx & 7) * 2);
   }
 
   f32x4 acc[FN][FC];
@@ -218,7 +196,7 @@ __global__ __launch_bounds__(WN * WC * 64, (WN * WC == 4 ? 2 : 1)) void wgrad_st
 #pragma unroll
     for (int j = 0; j < APR; ++j) {
       const int row = tid / CPR + j * (NWV * 64 / CPR);
-      aoff[j] = (unsigned)(row * RBY + ((acg ^ ws_swz<RBY>(row)) << 4));
+      aoff[j] = (unsigned)(row * RBY + ((acg ^ tr_swz<RBY>(row)) << 4));
     }
   }
   if constexpr (DG) {
@@ -241,7 +219,7 @@ __global__ __launch_bounds__(WN * WC * 64, (WN * WC == 4 ? 2 : 1)) void wgrad_st
 #pragma unroll
     for (int p = 0; p < DPX; ++p) {
       const int pix = (dpb0 + p) * 16 + fr;
-      dyoff[p] = (unsigned)(pix * RBY + ((fg ^ ws_swz<RBY>(pix)) << 4));   // reduction step ks: ^ (ks << 6)
+      dyoff[p] = (unsigned)(pix * RBY + ((fg ^ tr_swz<RBY>(pix)) << 4));   // reduction step ks: ^ (ks << 6)
       pend_m[p] = -1;
       pend[p][0] = pend[p][1] = 0u;
     }
@@ -269,13 +247,13 @@ __global__ __launch_bounds__(WN * WC * 64, (WN * WC == 4 ? 2 : 1)) void wgrad_st
     int nd = G - 1 - g;
     if (nd > ring - 2) nd = ring - 2;
     switch (nd) {
-      case 0: ws_wait_vm<0>(); break;
-      case 1: ws_wait_vm<PPW>(); break;
-      case 2: ws_wait_vm<2 * PPW>(); break;
-      case 3: ws_wait_vm<3 * PPW>(); break;
-      case 4: ws_wait_vm<4 * PPW>(); break;
-      case 5: ws_wait_vm<5 * PPW>(); break;
-      default: ws_wait_vm<6 * PPW>(); break;
+      case 0: wait_vm<0>(); break;
+      case 1: wait_vm<PPW>(); break;
+      case 2: wait_vm<2 * PPW>(); break;
+      case 3: wait_vm<3 * PPW>(); break;
+      case 4: wait_vm<4 * PPW>(); break;
+      case 5: wait_vm<5 * PPW>(); break;
+      default: wait_vm<6 * PPW>(); break;
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -325,15 +303,15 @@ __global__ __launch_bounds__(WN * WC * 64, (WN * WC == 4 ? 2 : 1)) void wgrad_st
     // gradient's MFMAs - measured the same, 0.182 vs 0.189 ms on res2 64 -> 256, and needed two code paths)
     if constexpr (DG) dg_read(0, 0);
     if (wave_active) {
-      WsFrag yf[FN], xf[FC];
+      Frag yf[FN], xf[FC];
 #pragma unroll
       for (int i = 0; i < FN; ++i)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) yf[i].u[h] = ws_tr_read(sb + (yoff[h] ^ (unsigned)(i << 5)));
+        for (int h = 0; h < 2; ++h) yf[i].u[h] = tr_read(sb + (yoff[h] ^ (unsigned)(i << 5)));
 #pragma unroll
       for (int j = 0; j < FC; ++j)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) xf[j].u[h] = ws_tr_read(sb + (xoff[h] ^ (unsigned)(j << 5)));
+        for (int h = 0; h < 2; ++h) xf[j].u[h] = tr_read(sb + (xoff[h] ^ (unsigned)(j << 5)));
       ws_mfma_columns<FN, FC>(acc, yf, xf);
     }
     if constexpr (DG) {
