@@ -1,4 +1,4 @@
-"""Float64 reference helpers of tests/test_gpu_optim_resample_float64.py, in a plain module so that the CPU tests of
+"""Float64 reference helpers of tests/test_gpu_optim_resample_float64.py and tests/test_gpu_conv_float64.py, in a plain module so that the CPU tests of
 tests/test_float64_refs_host.py check exactly what the GPU tests use.  Plain torch ops only; nothing here touches the HIP
 library.  Every function works on whatever device its inputs live on."""
 import torch
@@ -152,3 +152,180 @@ def stem_canvas(images, mean, std, hpad, wpad):
         canvas[i, :, :h, :w] = (im.to(F64) - mean) / std
         inside[i, :, :h, :w] = 1
     return canvas, inside
+
+
+# ---- convolution family (tests/test_gpu_conv_float64.py) ----
+TWO24 = float(1 << 24)   # every integer below it is an fp32 value: sums of integer terms with sum |term| < 2^24 are exact in any order
+U24 = 2.0 ** -24         # fp32 unit roundoff
+
+
+def rne_bf16(x):
+    """float64 -> the nearest bf16 value, ties to even, as float64.  Integer arithmetic on the float64 bit pattern (45 of the
+    52 fraction bits go), so the same on every device; bf16's exponent range is not modelled: |x| is 0 or in [2^-126, 2^127)."""
+    x = x.to(F64).contiguous()
+    ax = x.abs()
+    assert bool(((ax == 0) | ((ax >= 2.0 ** -126) & (ax < 2.0 ** 127))).all())
+    bits = x.view(torch.int64)
+    bits = bits + ((1 << 44) - 1) + ((bits >> 45) & 1)
+    return (bits & ~((1 << 45) - 1)).view(F64)
+
+
+def conv_out_size(h, w, kh, kw, stride, ph, pw):
+    return (h + 2 * ph - kh) // stride + 1, (w + 2 * pw - kw) // stride + 1
+
+
+def _cols(x, kh, kw, stride, ph, pw):
+    return TF.unfold(x, (kh, kw), padding=(ph, pw), stride=stride)   # [B, C * KH * KW, Ho * Wo], K ordered (c, kh, kw)
+
+
+def conv_fwd_ref(x, w, stride, ph, pw, bias=None):
+    """Convolution from unfold + matmul in float64 with its magnitude sum: (y, A), both [B, N, Ho, Wo];
+    y = sum of terms x w (+ bias), A = sum of |term| (+ |bias|).  x [B, C, H, W], w [N, C, KH, KW]."""
+    b, _, h, wd = x.shape
+    n, _, kh, kw = w.shape
+    ho, wo = conv_out_size(h, wd, kh, kw, stride, ph, pw)
+    cols = _cols(x.to(F64), kh, kw, stride, ph, pw)
+    wm = w.to(F64).reshape(n, -1)
+    y, a = wm @ cols, wm.abs() @ cols.abs()
+    if bias is not None:
+        y, a = y + bias.to(F64).view(1, n, 1), a + bias.to(F64).abs().view(1, n, 1)
+    return y.view(b, n, ho, wo), a.view(b, n, ho, wo)
+
+
+def conv_dgrad_ref(dy, w, in_hw, stride, ph, pw):
+    """Data gradient built the same way: the columns' gradient w^T dy folded back onto the input, and its magnitude sum.
+    dy [B, N, Ho, Wo] -> (dx, A) [B, C, H, W]."""
+    b, n = dy.shape[:2]
+    _, c, kh, kw = w.shape
+    wm = w.to(F64).reshape(n, -1)
+    d = dy.to(F64).reshape(b, n, -1)
+    fold = lambda t: TF.fold(t, in_hw, (kh, kw), padding=(ph, pw), stride=stride)
+    return fold(wm.t() @ d), fold(wm.abs().t() @ d.abs())
+
+
+def conv_wgrad_ref(x, dy, kh, kw, stride, ph, pw):
+    """Weight gradient dw[n][c][kh][kw] = sum over images and output pixels of dy x(source pixel), and its magnitude sum."""
+    b, c = x.shape[:2]
+    n = dy.shape[1]
+    cols = _cols(x.to(F64), kh, kw, stride, ph, pw)
+    d = dy.to(F64).reshape(b, n, -1)
+    dw = torch.einsum("bnl,bkl->nk", d, cols)
+    a = torch.einsum("bnl,bkl->nk", d.abs(), cols.abs())
+    return dw.view(n, c, kh, kw), a.view(n, c, kh, kw)
+
+
+def fp32_sum_bound(length, a):
+    """E = (L + 2) 2^-24 A: an fp32 sum of L terms in any order errs by at most (L - 1) u A to first order (each of the L - 1
+    additions rounds a partial sum that is at most A in magnitude); the products of two bf16 values are exact in fp32; the 2 pays
+    for the bias add and the epilogue, and the slack of 1 covers the second-order terms (L u << 1 at every L used here)."""
+    return (length + 2) * U24 * a
+
+
+def bf16_interval(ref, e, relu=False, old=None):
+    """[lo, hi] of the stored bf16 value for an fp32 result within e of ref: RNE_bf16 of both ends (rounding is monotone), then -
+    both monotone too - the accumulating epilogue's second rounding RNE_bf16(. + old) and the ReLU."""
+    lo, hi = rne_bf16(ref - e), rne_bf16(ref + e)
+    if old is not None:
+        lo, hi = rne_bf16(lo + old.to(F64)), rne_bf16(hi + old.to(F64))
+    if relu:
+        lo, hi = lo.clamp(min=0), hi.clamp(min=0)
+    return lo, hi
+
+
+def exact_amp(length, other=None):
+    """Amplitude a of the exact-input generator: integers uniform in {-a .. a} have variance a (a + 1) / 3, so a sum of
+    `length` products with a factor of amplitude `other` (default: a itself) has the standard deviation
+    sqrt(length a (a + 1) / 3 other (other + 1) / 3) - the smallest a in 2 .. 16 that puts it at 512 or more (a good share of the
+    sums then lies past 256, where bf16 no longer holds every integer); 16 for short sums."""
+    for a in range(2, 17):
+        o = a if other is None else other
+        if (length * a * (a + 1) * o * (o + 1)) ** 0.5 / 3 >= 512:
+            return a
+    return 16
+
+
+def ints(shape, amp, g):
+    return torch.randint(-amp, amp + 1, tuple(shape), generator=g).to(F64)
+
+
+def bf16_round(t):
+    return t.float().bfloat16().to(F64)
+
+
+def conv_operands(geom, mode, amp=None):
+    """Operands of one convolution case as float64 tensors whose values are bf16 numbers: x [B, Cin, H, W], w [N, Cin, KH, KW],
+    bias [N], gy [B, N, Ho, Wo], old [B, N, Ho, Wo] (the accumulating epilogue's stored values).
+    geom = (B, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w).
+    mode "exact": small integers (amplitudes by exact_amp of the forward and data-gradient sum lengths - the taps that fall
+      inside the map, not those in the padding - or `amp` for all).
+    mode "real": x = relu(N(mu_c, 1)), mu_c drawn from {0, 1, 4}, channel 0 all zero, channel 1 with a few values of 2^6;
+      w = N(0, 1 / K) + a per-filter offset U(-1, 1) / K; gy = N(0, 1) 2^-10."""
+    b, h, wd, cin, cout, kh, kw, stride, ph, pw = geom
+    g = torch.Generator().manual_seed(sum((i + 1) * 7919 * v for i, v in enumerate(geom)) % (2 ** 31) + (mode == "real"))
+    ho, wo = conv_out_size(h, wd, kh, kw, stride, ph, pw)
+    k = kh * kw * cin
+    if mode == "exact":
+        # the terms an output really has: taps inside the map (a one-pixel map under a 7x7 filter meets one tap), on average
+        inside = float(_cols(torch.ones((1, 1, h, wd), dtype=F64), kh, kw, stride, ph, pw).sum(1).mean())
+        a_f = amp or exact_amp(max(1, round(cin * inside)))
+        x, w = ints((b, cin, h, wd), a_f, g), ints((cout, cin, kh, kw), a_f, g)
+        bias, old = ints((cout,), 16 * a_f, g), ints((b, cout, ho, wo), 16 * a_f, g)
+        # data gradient: taps * Cout terms, of which a stride-s layer meets one in s^2
+        a_g = amp or exact_amp(max(1, round(cout * inside * ho * wo / (h * wd))), a_f)   # every term of y is one of dx too
+        gy = ints((b, cout, ho, wo), a_g, g)
+        return x, w, bias, gy, old
+    assert mode == "real"
+    mu = torch.tensor([0.0, 1.0, 4.0], dtype=F64)[torch.randint(0, 3, (cin,), generator=g)]
+    x = torch.relu(torch.randn((b, cin, h, wd), generator=g, dtype=F64) + mu.view(1, cin, 1, 1))
+    x[:, 0] = 0
+    if cin > 1:
+        flat = x[:, 1].reshape(-1).clone()
+        flat[torch.randint(0, flat.numel(), (min(3, flat.numel()),), generator=g)] = 64.0
+        x[:, 1] = flat.view(b, h, wd)
+    w = torch.randn((cout, cin, kh, kw), generator=g, dtype=F64) / k ** 0.5 \
+        + (torch.rand((cout, 1, 1, 1), generator=g, dtype=F64) * 2 - 1) / k
+    bias = torch.randn((cout,), generator=g, dtype=F64) * 0.1
+    gy = torch.randn((b, cout, ho, wo), generator=g, dtype=F64) * 2.0 ** -10
+    old = torch.relu(torch.randn((b, cout, ho, wo), generator=g, dtype=F64) + 1)
+    return tuple(bf16_round(t) for t in (x, w, bias, gy, old))
+
+
+def g3(b, h, w, cin, cout, k=3, stride=1, pad=None):
+    """geom of a square filter with symmetric padding (default: 'same' for odd k)."""
+    pad = k // 2 if pad is None else pad
+    return (b, h, w, cin, cout, k, k, stride, pad, pad)
+
+
+# The cases of tests/test_gpu_conv_float64.py, here so that the CPU twin checks the generator's preconditions on every one.
+VARIANT_SHAPES = [g3(2, 36, 32, 64, 256), g3(2, 35, 31, 64, 256)]
+GENERIC_LAYERS = [(32, 8, 1, 1, 0), (64, 40, 3, 1, 1), (128, 96, 3, 2, 1), (256, 40, 1, 2, 0), (32, 28, 5, 1, 2), (32, 64, 7, 2, 3)]
+GENERIC_MAPS = [(1, 1, 1), (1, 1, 9), (1, 9, 1), (2, 19, 23), (1, 8, 8)]
+GENERIC_GEOMS = [g3(b, h, w, cin, cout, k, s, p) for (cin, cout, k, s, p) in GENERIC_LAYERS for (b, h, w) in GENERIC_MAPS]
+ASYM_GEOM = (2, 9, 11, 32, 40, 1, 3, 1, 0, 1)   # KH != KW, pad_h != pad_w (C ABI only)
+STRIDE2_MAPS = [(1, 1), (1, 2), (2, 1), (7, 9), (8, 10)]
+STRIDE2_GEOMS = [g3(2, h, w, 64, 64, k, 2, p) for (k, p) in ((1, 0), (3, 1)) for (h, w) in STRIDE2_MAPS]
+HALO_MAPS = [(1, 5, 7), (2, 16, 32), (2, 17, 33), (1, 33, 65)]
+HALO_CHANNELS = [(64, 64), (96, 40), (256, 64), (32, 8)]
+HALO_GEOMS = [g3(b, h, w, cin, cout) for (cin, cout) in HALO_CHANNELS for (b, h, w) in HALO_MAPS]
+# conv_stream.hip: pixels one work-group's LDS ring holds (ring stages x pixel tile) by input channels; with the 8-work-group
+# grid of the tests (bit 16) a channel block's eight walkers pass their ring's end at 8 x that many pixels
+STREAM_RING_PIXELS = {32: 8 * 128, 64: 5 * 128, 128: 5 * 64, 256: 5 * 64}
+STREAM_CIN, STREAM_COUT = [32, 64, 128, 256], [40, 104, 264, 520]
+
+
+def stream_pixel_counts(cin):
+    full = 8 * STREAM_RING_PIXELS[cin]
+    return [1, 63, full - 1, full + 1]
+
+
+STREAM_GEOMS = [g3(1, 1, m, cin, cout, 1) for cin in STREAM_CIN for cout in STREAM_COUT for m in stream_pixel_counts(cin)]
+ACC_GEOMS = [g3(2, 37, 41, 64, 256, 1), g3(3, 20, 24, 256, 1024, 1), g3(1, 1, 1, 64, 256, 1)]
+LONGK_GEOMS = [g3(2, 5, 7, 2048, 512, 1), g3(1, 65, 1, 768, 2304, 1), g3(1, 65, 1, 3072, 768, 1)]
+FC_GEOM = g3(37, 7, 7, 256, 1024, 7, 1, 0)
+WGRAD_TAP_GEOMS = [g3(2, 21, 27, 128, 136), g3(2, 21, 27, 256, 264, 1)]
+WGRAD_HALO_GEOMS = [g3(*s) for s in ((1, 5, 7, 32, 32), (2, 14, 14, 64, 64), (1, 13, 17, 128, 136), (1, 1, 1, 32, 32), (1, 1, 9, 64, 40))]
+WGRAD_STREAM_GEOMS = [g3(1, 1, 1, 64, 256, 1), g3(1, 19, 17, 264, 520, 1), g3(2, 33, 21, 256, 40, 1), g3(1, 37, 29, 64, 256, 1)]
+FUSED_GEOMS = [g3(1, 1, 1, 64, 256, 1), g3(2, 37, 41, 64, 256, 1), g3(2, 37, 41, 40, 200, 1), g3(1, 1, 1, 128, 512, 1),
+               g3(2, 37, 41, 128, 512, 1), g3(2, 37, 41, 72, 264, 1)]
+ALL_CONV_GEOMS = (VARIANT_SHAPES + GENERIC_GEOMS + [ASYM_GEOM] + STRIDE2_GEOMS + HALO_GEOMS + STREAM_GEOMS + ACC_GEOMS + LONGK_GEOMS
+                  + [FC_GEOM] + WGRAD_TAP_GEOMS + WGRAD_HALO_GEOMS + WGRAD_STREAM_GEOMS + FUSED_GEOMS)

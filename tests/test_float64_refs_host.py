@@ -1,5 +1,5 @@
-"""CPU checks of tests/float64_refs.py, the float64 references tests/test_gpu_optim_resample_float64.py compares the HIP
-kernels with: each reference is held against an independent formulation in torch, so that a GPU test cannot pass or fail
+"""CPU checks of tests/float64_refs.py, the float64 references tests/test_gpu_optim_resample_float64.py and
+tests/test_gpu_conv_float64.py compare the HIP kernels with: each reference is held against an independent formulation in torch, so that a GPU test cannot pass or fail
 because of a mistake in its own yardstick."""
 import pytest
 import torch
@@ -88,3 +88,92 @@ def test_stem_unfold_ref_reproduces_conv2d():
     # image 2 is one pixel: only the windows that contain canvas pixel (0, 0) see it, at tap (3 - 2 oy, 3 - 2 ox)
     one = cols[2].view(32, 48, 7, 7, 3)
     assert int((one != 0).any(-1).sum()) == 4 and bool((one[1, 1, 1, 1] == canvas[2, :, 0, 0]).all())
+
+
+# ---- the convolution references of tests/test_gpu_conv_float64.py ----
+def test_rne_bf16_on_hand_made_ties():
+    """bf16 keeps 8 significant bits: in [1, 2) the step is 2^-7, in [256, 512) it is 2.  Exact ties go to the even neighbour, a
+    hair above or below a tie goes to the nearer one, bf16 values come back unchanged, the sign is symmetric."""
+    s = 2.0 ** -7
+    cases = [(1 + s / 2, 1.0), (1 + 3 * s / 2, 1 + 2 * s), (1 + s / 2 + 2.0 ** -40, 1 + s), (1 + 3 * s / 2 - 2.0 ** -40, 1 + s),
+             (257.0, 256.0), (259.0, 260.0), (258.0, 258.0), (261.0, 260.0), (263.0, 264.0), (255.5, 256.0), (254.5, 254.0),
+             (511.0, 512.0), (513.0, 512.0), (515.0, 516.0), (2.0 - s / 2, 2.0), (0.0, 0.0), (2.0 ** -10 * (1 + s / 2), 2.0 ** -10),
+             (3.0 * 2.0 ** 20, 3.0 * 2.0 ** 20), (65.0 + 0.25, 65.0), (65.0 + 0.75, 66.0)]
+    x = torch.tensor([c[0] for c in cases], dtype=F64)
+    want = torch.tensor([c[1] for c in cases], dtype=F64)
+    assert torch.equal(R.rne_bf16(x), want)
+    assert torch.equal(R.rne_bf16(-x), -want)
+    # float64 -> bf16 in one rounding is what torch does from fp32 for fp32 values; random fp32 values agree with torch's cast
+    r = torch.randn(100000, generator=torch.Generator().manual_seed(1)).to(F64) * 300
+    assert torch.equal(R.rne_bf16(r), r.float().bfloat16().to(F64))
+    lo, hi = R.bf16_interval(torch.tensor([257.0, -3.0, 1.0], dtype=F64), torch.tensor([0.5, 0.5, 0.0], dtype=F64), relu=True)
+    assert lo.tolist() == [256.0, 0.0, 1.0] and hi.tolist() == [258.0, 0.0, 1.0]
+    lo, hi = R.bf16_interval(torch.tensor([257.0], dtype=F64), torch.tensor([0.0], dtype=F64), old=torch.tensor([3.0], dtype=F64))
+    assert lo.tolist() == [260.0] and hi.tolist() == [260.0]   # bf16(257) = 256, bf16(259) = 260 (tie to even)
+
+
+@pytest.mark.parametrize("geom", R.GENERIC_GEOMS + [R.ASYM_GEOM] + R.STRIDE2_GEOMS + R.HALO_GEOMS[:4])
+def test_conv_refs_equal_torch_conv2d_and_autograd(geom):
+    """unfold + matmul (forward), its transpose + fold (data gradient) and dy cols^T (weight gradient) against
+    torch.nn.functional.conv2d in float64 and its autograd: strides 1 and 2, asymmetric filter and padding, one-pixel / one-row /
+    one-column maps.  The magnitude sums are the same operations on |operands|: positive operands give A == |value|."""
+    b, h, w, cin, cout, kh, kw, stride, ph, pw = geom
+    x, wt, bias, gy, _ = R.conv_operands(geom, "real")
+    xr, wr, br = x.clone().requires_grad_(True), wt.clone().requires_grad_(True), bias.clone().requires_grad_(True)
+    want = TF.conv2d(xr, wr, br, stride, (ph, pw))
+    want.backward(gy)
+    want = want.detach()
+    tol = lambda t: 1e-12 * float(t.abs().max()) + 1e-300
+    y, a = R.conv_fwd_ref(x, wt, stride, ph, pw, bias)
+    assert y.shape == want.shape == gy.shape
+    assert float((y - want).abs().max()) <= tol(want)
+    dx, adx = R.conv_dgrad_ref(gy, wt, (h, w), stride, ph, pw)
+    assert dx.shape == x.shape and float((dx - xr.grad).abs().max()) <= tol(xr.grad)
+    dw, adw = R.conv_wgrad_ref(x, gy, kh, kw, stride, ph, pw)
+    assert dw.shape == wt.shape and float((dw - wr.grad).abs().max()) <= tol(wr.grad)
+    assert float((gy.sum((0, 2, 3)) - br.grad).abs().max()) <= tol(br.grad)
+    # magnitude sums: >= |value| everywhere, and the value itself on |operands|
+    assert bool((a >= y.abs() - tol(y)).all()) and bool((adx >= dx.abs() - tol(dx)).all()) and bool((adw >= dw.abs() - tol(dw)).all())
+    ya, _ = R.conv_fwd_ref(x.abs(), wt.abs(), stride, ph, pw, bias.abs())
+    assert float((ya - a).abs().max()) <= tol(a)
+    dxa, _ = R.conv_dgrad_ref(gy.abs(), wt.abs(), (h, w), stride, ph, pw)
+    assert float((dxa - adx).abs().max()) <= tol(adx)
+    dwa, _ = R.conv_wgrad_ref(x.abs(), gy.abs(), kh, kw, stride, ph, pw)
+    assert float((dwa - adw).abs().max()) <= tol(adw)
+
+
+@pytest.mark.parametrize("geom", sorted(set(R.ALL_CONV_GEOMS)))
+def test_exact_generator_preconditions(geom):
+    """Every shape of the GPU module: the exact-input operands are integers that bf16 holds (|v| <= 256), and the magnitude sums
+    of the forward (+ bias), the data gradient, the weight gradient and the column sums of the outputs stay below 2^24 - any
+    order of fp32 additions is then exact.  The low-amplitude form also keeps the sums of squares there."""
+    b, h, w, cin, cout, kh, kw, stride, ph, pw = geom
+    x, wt, bias, gy, old = R.conv_operands(geom, "exact")
+    for t in (x, wt, gy):
+        assert torch.equal(t, t.round()) and float(t.abs().max()) <= 256
+    for t in (bias, old):
+        assert torch.equal(R.rne_bf16(t), t)
+    y, a = R.conv_fwd_ref(x, wt, stride, ph, pw, bias)
+    assert float(a.max()) < R.TWO24
+    yy = R.rne_bf16(y)
+    assert float(yy.abs().sum((0, 2, 3)).max()) < R.TWO24
+    assert float(R.conv_dgrad_ref(gy, wt, (h, w), stride, ph, pw)[1].max()) < R.TWO24
+    assert float(R.conv_wgrad_ref(x, gy, kh, kw, stride, ph, pw)[1].max()) + 256 < R.TWO24
+    assert float(gy.abs().sum((0, 2, 3)).max()) < R.TWO24
+    if geom in R.VARIANT_SHAPES + R.HALO_GEOMS:
+        x1, w1, _, _, _ = R.conv_operands(geom, "exact", amp=1)
+        y1 = R.conv_fwd_ref(x1, w1, stride, ph, pw)[0]
+        assert torch.equal(R.rne_bf16(y1) ** 2, y1 ** 2) and float((y1 * y1).sum((0, 2, 3)).max()) < R.TWO24
+
+
+def test_activation_like_operands():
+    """The realistic generator: bf16 values, non-negative activations with one all-zero channel and a channel holding 2^6,
+    per-channel means apart, gradients at 2^-10."""
+    x, wt, bias, gy, old = R.conv_operands(R.VARIANT_SHAPES[0], "real")
+    for t in (x, wt, bias, gy, old):
+        assert torch.equal(R.bf16_round(t), t)
+    assert float(x.min()) >= 0 and float(x[:, 0].abs().max()) == 0 and int((x[:, 1] == 64).sum()) >= 1
+    means = x.mean((0, 2, 3))
+    assert float(means.max()) > 3.5 and float(means[2:].min()) < 0.6
+    assert 2.0 ** -11 < float(gy.std()) < 2.0 ** -9
+    assert float(wt.mean((1, 2, 3)).abs().max()) > 0.2 / (64 * 9)
