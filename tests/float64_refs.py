@@ -1,4 +1,5 @@
-"""Float64 reference helpers of tests/test_gpu_optim_resample_float64.py and tests/test_gpu_conv_float64.py, in a plain module so that the CPU tests of
+"""Float64 reference helpers of tests/test_gpu_optim_resample_float64.py, tests/test_gpu_conv_float64.py and
+tests/test_gpu_inference_tails_float64.py, in a plain module so that the CPU tests of
 tests/test_float64_refs_host.py check exactly what the GPU tests use.  Plain torch ops only; nothing here touches the HIP
 library.  Every function works on whatever device its inputs live on."""
 import torch
@@ -329,3 +330,202 @@ FUSED_GEOMS = [g3(1, 1, 1, 64, 256, 1), g3(2, 37, 41, 64, 256, 1), g3(2, 37, 41,
                g3(2, 37, 41, 128, 512, 1), g3(2, 37, 41, 72, 264, 1)]
 ALL_CONV_GEOMS = (VARIANT_SHAPES + GENERIC_GEOMS + [ASYM_GEOM] + STRIDE2_GEOMS + HALO_GEOMS + STREAM_GEOMS + ACC_GEOMS + LONGK_GEOMS
                   + [FC_GEOM] + WGRAD_TAP_GEOMS + WGRAD_HALO_GEOMS + WGRAD_STREAM_GEOMS + FUSED_GEOMS)
+
+
+# ---- inference tails (tests/test_gpu_inference_tails_float64.py) ----
+def _paste_axis(n_pix, lo, hi, p):
+    """Source coordinate of every pixel centre along one axis, [n_masks, n_pix]: the normalised grid value of
+    layers/mask_ops.py (pixel centre mapped so that the box spans [-1, 1]) and grid_sample's unnormalisation with
+    align_corners=False, ((g + 1) P - 1) / 2."""
+    pix = torch.arange(n_pix, dtype=F64) + 0.5
+    g = (pix[None] - lo[:, None]) / (hi - lo)[:, None] * 2 - 1
+    return ((g + 1) * p - 1) / 2
+
+
+def _paste_taps(coord, p):
+    """[n, L] source coordinates -> [n, L, p] bilinear weights of the p texels; a tap outside the map has no column: zeros padding."""
+    i0 = torch.floor(coord)
+    w1 = coord - i0
+    j = torch.arange(p, dtype=F64)
+    return (1 - w1)[..., None] * (j == i0[..., None]).to(F64) + w1[..., None] * (j == i0[..., None] + 1).to(F64)
+
+
+def paste_ref(probs, boxes, h, w):
+    """layers/mask_ops.py:17-147 before the threshold, in float64: the P x P maps probs [n, P, P] sampled over boxes [n, 4]
+    (x0, y0, x1, y1) by grid_sample(bilinear, align_corners=False, zeros padding) at the centres of an h x w canvas.
+    Returns (v [n, h, w] float64, inside [n, h, w] bool); `inside`: the sample point lies less than one texel outside the map on
+    both axes (-1 < coordinate < P) - everywhere else all four taps are padding and the value is an exact 0."""
+    probs, boxes = probs.to(F64).cpu(), boxes.to(F64).cpu()
+    p = probs.shape[-1]
+    ix = _paste_axis(w, boxes[:, 0], boxes[:, 2], p)
+    iy = _paste_axis(h, boxes[:, 1], boxes[:, 3], p)
+    v = torch.einsum("nyi,nij,nxj->nyx", _paste_taps(iy, p), probs, _paste_taps(ix, p))
+    inside = ((iy > -1) & (iy < p))[:, :, None] & ((ix > -1) & (ix < p))[:, None, :]
+    return v, inside
+
+
+def paste_fp32(probs, boxes, h, w):
+    """The reference's own fp32 form of the same (mask_ops.py's grid + F.grid_sample on the CPU), before the threshold:
+    what the margins of the random-input paste test are measured with."""
+    probs, boxes = probs.float().cpu(), boxes.float().cpu()
+    n = probs.shape[0]
+    x0, y0, x1, y1 = torch.split(boxes, 1, dim=1)
+    img_y = (torch.arange(0, h, dtype=torch.float32) + 0.5 - y0) / (y1 - y0) * 2 - 1
+    img_x = (torch.arange(0, w, dtype=torch.float32) + 0.5 - x0) / (x1 - x0) * 2 - 1
+    grid = torch.stack([img_x[:, None, :].expand(n, h, w), img_y[:, :, None].expand(n, h, w)], dim=3)
+    return TF.grid_sample(probs[:, None], grid, align_corners=False)[:, 0]
+
+
+PASTE_P = [1, 2, 7, 14, 28]
+PASTE_CANVASES = [(45, 53), (5, 3), (1, 1), (9, 8), (16, 64)]
+PASTE_HALF, PASTE_BELOW = 6, 7   # maps of paste_exact_case that are constant 0.5 / constant 0.5 - 1/256
+
+
+def paste_exact_case(p, h, w):
+    """Exact inputs of the paste on an h x w canvas: 13 boxes (x0, y0, x1, y1) whose sides are powers of two (1/4 .. 32) and whose
+    corners are multiples of 1/4, and maps whose values are multiples of 1/256.  Every source coordinate is then a multiple of
+    2^-7, every bilinear weight product one of 2^-14 and every term one of 2^-22 below 1: the sampled value is an fp32 number
+    in whatever order it is formed (the tests assert it).  13 masks: 13 h w is no multiple of 16 unless h w is.
+    Map PASTE_HALF is constant 0.5 (interior pixels sit exactly on the 0.5 threshold), map PASTE_BELOW constant 0.5 - 1/256."""
+    g = torch.Generator().manual_seed(1000 * p + 10 * h + w)
+    q = lambda v: float(int(v * 4)) / 4    # noqa: E731
+    xywh = [
+        (-40.25, 0.0, 32, 8),                 # 0 wholly left of the canvas (with P = 1 its reach still comes back in)
+        (w + 8.5, 1.0, 16, 4),                # 1 wholly right
+        (0.0, -20.75, 8, 16),                 # 2 wholly above
+        (2.0, h + 4.25, 4, 2),                # 3 wholly below
+        (-3.25, -2.5, 8, 4),                  # 4 partly off, top left
+        (w - 2.75, h - 1.5, 4, 8),            # 5 partly off, bottom right
+        (q((w - 32) / 2), q((h - 32) / 2), 32, 32),   # 6 covers the canvas (or its middle): constant 0.5
+        (q((w - 16) / 2) + 0.25, q((h - 8) / 2) - 0.25, 16, 8),   # 7 constant 0.5 - 1/256
+        (q(w / 2) + 0.25, q(h / 2) + 0.25, 0.5, 0.25),   # 8 smaller than a pixel, covers no pixel centre
+        (q(w / 3) + 0.25, q(h / 3) + 0.25, 1, 1),        # 9 one pixel wide, across four pixels
+        (4.25, 1.0, 32, 1),                   # 10 32 wide, 1 high: the widest reach past the box with P = 1, 2
+        (0.0, 0.0, 1, 32),                    # 11 1 wide, 32 high, at the origin
+        (w - 32.0, h - 32.0, 32, 32),         # 12 ends exactly at the canvas corner
+    ]
+    boxes = torch.tensor([[x, y, x + bw, y + bh] for x, y, bw, bh in xywh], dtype=torch.float32)
+    n = boxes.shape[0]
+    probs = torch.randint(0, 257, (n, p, p), generator=g).float() / 256
+    probs[PASTE_HALF] = 0.5
+    probs[PASTE_BELOW] = 0.5 - 1.0 / 256
+    probs[12] = (torch.randint(0, 2, (p, p), generator=g) * 256).float() / 256   # 0 / 1 checker noise
+    return probs, boxes
+
+
+def paste_random_case(p, h, w, n, seed):
+    """Random fp32 inputs of the paste: n smooth maps (a sigmoid blob each) and n salt-and-pepper maps (uniform noise), boxes
+    with arbitrary fp32 corners, some reaching past the canvas."""
+    g = torch.Generator().manual_seed(seed)
+    lin = torch.linspace(-1, 1, p) if p > 1 else torch.zeros(1)
+    yy, xx = torch.meshgrid(lin, lin, indexing="ij")
+    cx, cy = torch.rand(n, generator=g) - 0.5, torch.rand(n, generator=g) - 0.5
+    rad = 0.4 + 0.5 * torch.rand(n, generator=g)
+    smooth = torch.sigmoid(6 * (rad[:, None, None] - ((xx[None] - cx[:, None, None]) ** 2 + (yy[None] - cy[:, None, None]) ** 2).sqrt()))
+    probs = torch.cat([smooth, torch.rand((n, p, p), generator=g)]).float()
+    x0 = torch.rand(2 * n, generator=g) * (w + 6) - 6
+    y0 = torch.rand(2 * n, generator=g) * (h + 6) - 6
+    bw = 0.3 + torch.rand(2 * n, generator=g) * 1.2 * w
+    bh = 0.3 + torch.rand(2 * n, generator=g) * 1.2 * h
+    return probs, torch.stack([x0, y0, x0 + bw, y0 + bh], dim=1).float()
+
+
+def _source_index(n_out, n_in, scale):
+    """ATen's area_pixel_compute_source_index (align_corners=False) and guard_index_and_lambda along one axis:
+    src = max(scale (dst + 0.5) - 0.5, 0); i0 = min(floor(src), n_in - 1); i1 = i0 + (i0 < n_in - 1); lambda = src - i0 in [0, 1]."""
+    src = (float(scale) * (torch.arange(n_out, dtype=F64) + 0.5) - 0.5).clamp(min=0)
+    i0 = torch.floor(src).clamp(max=n_in - 1)
+    lam = (src - i0).clamp(0, 1)
+    i0 = i0.long()
+    return i0, i0 + (i0 < n_in - 1).long(), lam
+
+
+def _bilinear(x, ys, xs):
+    """x [..., H, W] float64; value = h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11), ATen's upsample_bilinear2d."""
+    (y0, y1, ly), (x0, x1, lx) = ys, xs
+    row = lambda r: (1 - lx) * r[..., x0] + lx * r[..., x1]   # noqa: E731
+    return (1 - ly)[:, None] * row(x[..., y0, :]) + ly[:, None] * row(x[..., y1, :])
+
+
+def upsample_ref(x, k, s):
+    """F.interpolate(logits, scale_factor=s, mode="bilinear", align_corners=False) of the first k channels of an NHWC map
+    x [B, H, W, Cp] in float64 (scale = 1 / s): [B, k, H s, W s]."""
+    x = x[..., :k].to(F64).cpu().permute(0, 3, 1, 2)
+    h, w = x.shape[2], x.shape[3]
+    return _bilinear(x, _source_index(h * s, h, 1.0 / s), _source_index(w * s, w, 1.0 / s))
+
+
+def resize_ref(x, hout, wout):
+    """F.interpolate(x, size=(hout, wout), mode="bilinear", align_corners=False) of x [C, Hin, Win]: the scale as ATen forms it
+    for fp32 maps - the fp32 quotient in / out - everything after it in float64."""
+    x = x.to(F64).cpu()
+    hin, win = x.shape[1], x.shape[2]
+    sc = lambda a, b: float(torch.tensor(float(a), dtype=torch.float32) / torch.tensor(float(b), dtype=torch.float32))   # noqa: E731
+    return _bilinear(x, _source_index(hout, hin, sc(hin, hout)), _source_index(wout, win, sc(win, wout)))
+
+
+def first_argmax(v, dim=1):
+    """Index of the first maximum along dim, written as a count: the number of entries before the first one equal to the maximum."""
+    is_max = v == v.max(dim=dim, keepdim=True).values
+    return (is_max.long().cumsum(dim) == 0).long().sum(dim)
+
+
+SEM_EXACT_CASES = [(1, 8), (7, 8), (8, 8), (9, 32), (28, 32), (54, 64), (64, 64), (7, 32), (1, 64)]   # (K, Cp)
+SEM_MAPS = [(1, 1), (1, 5), (7, 1), (3, 5)]
+
+
+def upsample_exact_case(b, h, w, cp, k, pad):
+    """Exact inputs of the semantic upsample: bf16 multiples of 1/4 with |v| <= 32 in channels [0, k); with s in {2, 4} the
+    interpolation weights are multiples of 1/8, every product and sum a multiple of 2^-8 below 64: fp32 numbers, in any order.
+    Built-in ties: the last channel copies channel k // 2 and both are raised by 16 on every other pixel of all images but the
+    last (two identical, mostly maximal channels: the lower index must win); all channels of the first image's top-left 2 x 2 pixels are equal (index 0 must win);
+    the last image is negative everywhere.  Pad channels [k, cp) hold `pad` (1e30 or NaN): they must influence nothing.
+    Returns NHWC float64 holding bf16 values (pad channels included)."""
+    g = torch.Generator().manual_seed(b * 100000 + h * 10000 + w * 1000 + cp * 10 + k)
+    x = torch.randint(-64, 65, (b, h, w, cp), generator=g).to(F64) / 4     # |v| <= 16
+    x[b - 1] = -x[b - 1].abs() - 0.25                                        # the last image: every value negative
+    if k > 1:
+        lo = k // 2 if k > 2 else 0
+        checker = ((torch.arange(h)[:, None] + torch.arange(w)[None]) % 2 == 0).to(F64)
+        x[: b - 1, :, :, lo] += 16 * checker                                 # (not in the negative image)
+        x[..., k - 1] = x[..., lo]
+    x[0, :2, :2, :k] = x[0, 0, 0, 0].item()
+    x[..., k:] = pad
+    return x
+
+
+def mask_prob_ref(x, w, b, cls):
+    """mask_rcnn_inference (roi_heads/mask_head.py:115-158) on the predicted class's channel only: the exact dot product of the
+    bf16-rounded operands in float64, the logit rounded to bf16 as the predictor conv's output is, float64 sigmoid.
+    x [N, S, S, C] (bf16 values), w [K, C] or [K, C, 1, 1], b [K], cls [N] -> (prob [N, 1, S, S], rounded logit z [N, 1, S, S])."""
+    x = x.to(F64).cpu()
+    wq = bf16_round(w.detach().cpu().reshape(w.shape[0], -1))[cls.cpu().long()]   # [N, C]
+    bq = bf16_round(b.detach().cpu())[cls.cpu().long()]
+    z = rne_bf16(torch.einsum("nyxc,nc->nyx", x, wq) + bq.view(-1, 1, 1))[:, None]
+    return torch.sigmoid(z), z
+
+
+MASK_PROB_Q = 2.0 ** -8   # quantum of the exact mask-predictor case: weights and bias are integers times this
+
+
+def mask_prob_case(n, side, c, k, seed=0):
+    """Exact inputs of the folded mask predictor: x integers in [-ax, ax] (bf16 values), weights and bias integers (|.| <= 255, so
+    bf16 values) times 2^-8.  Every product and partial sum is an integer times 2^-8 of magnitude at most
+    (c ax aw + 255) 2^-8 < 2^24 2^-8 - an fp32 number in any order - so the fp32 logit is the exact sum and its bf16 rounding is
+    unique (ties to even on exact halves).  Amplitudes put the logits' standard deviation near 2.5: most |z| lie in [1, 8], where
+    bf16 has fewer than 8 fractional bits - z in [1, 2) odd multiples of 2^-8 are exact halves, [2, 8) rounds properly.
+    Selected classes: the first and the last of the k, the rest random.  Returns (x [n, side, side, c] float64, w [k, c] fp32,
+    b [k] fp32, cls [n] int64, ax, aw)."""
+    g = torch.Generator().manual_seed(seed + 7919 * n + 104729 * side + 31 * c + k)
+    for ax in (8, 2):
+        aw = round((6.25 * 65536 * 9 / (c * ax * (ax + 1))) ** 0.5)
+        if aw <= 255:
+            break
+    aw = max(1, min(aw, 255))
+    x = ints((n, side, side, c), ax, g)
+    w = (ints((k, c), aw, g) * MASK_PROB_Q).float()
+    b = (ints((k,), 255, g) * MASK_PROB_Q).float()
+    cls = torch.randint(0, k, (n,), generator=g)
+    cls[0] = 0
+    cls[-1] = k - 1
+    return x, w, b, cls, ax, aw

@@ -177,3 +177,126 @@ def test_activation_like_operands():
     assert float(means.max()) > 3.5 and float(means[2:].min()) < 0.6
     assert 2.0 ** -11 < float(gy.std()) < 2.0 ** -9
     assert float(wt.mean((1, 2, 3)).abs().max()) > 0.2 / (64 * 9)
+
+
+# ---- inference tails (tests/test_gpu_inference_tails_float64.py) ----
+@pytest.mark.parametrize("p", R.PASTE_P)
+def test_paste_ref_equals_oracle_on_exact_inputs(p):
+    """paste_ref against OracleModel.paste_masks (grid_sample in fp32, then >= 0.5) on the exact inputs of the GPU test, every
+    canvas: the sampled value is an fp32 number (so the fp32 oracle computes it without error) and not one pixel differs.  The
+    constant-0.5 map has pixels exactly on the threshold, all on; the map one step below it is all off."""
+    from oracle.model import OracleModel
+
+    on_thr = 0
+    for h, w in R.PASTE_CANVASES:
+        probs, boxes = R.paste_exact_case(p, h, w)
+        side = torch.cat([boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]])
+        assert bool((torch.log2(side) == torch.log2(side).round()).all()) and float(side.max()) <= 32
+        assert torch.equal(boxes * 4, (boxes * 4).round()) and torch.equal(probs * 256, (probs * 256).round())
+        assert (boxes.shape[0] * h * w) % 16 != 0 or (h * w) % 16 == 0
+        v, inside = R.paste_ref(probs, boxes, h, w)
+        assert torch.equal(v, v.float().to(F64)), (p, h, w)
+        assert not bool(v[~inside].any())
+        want = inside & (v >= 0.5)
+        assert torch.equal(want, OracleModel.paste_masks(probs, boxes, (h, w))), (p, h, w)
+        assert torch.equal(v, R.paste_fp32(probs, boxes, h, w).to(F64)), (p, h, w)
+        on_thr += int((v[R.PASTE_HALF] == 0.5).sum())
+        assert not bool(want[R.PASTE_BELOW].any()) and bool(inside[R.PASTE_BELOW].any()) == bool(inside[R.PASTE_HALF].any())
+        assert bool(want[R.PASTE_HALF][v[R.PASTE_HALF] == 0.5].all())
+        assert not bool(inside[1].any()) and not bool(inside[3].any())      # boxes wholly right of / below the canvas
+    assert on_thr >= 3, on_thr
+
+
+@pytest.mark.parametrize("p", [1, 7, 28])
+def test_paste_ref_equals_grid_sample_float64(p):
+    """paste_ref against torch's grid_sample in float64 on random fp32 inputs (values to 1e-13), and the `inside` predicate
+    against where a map of ones samples to something positive."""
+    h, w = 45, 53
+    probs, boxes = R.paste_random_case(p, h, w, 6, 3)
+    v, inside = R.paste_ref(probs, boxes, h, w)
+    b = boxes.to(F64)
+    gy = (torch.arange(h, dtype=F64) + 0.5 - b[:, 1:2]) / (b[:, 3:4] - b[:, 1:2]) * 2 - 1
+    gx = (torch.arange(w, dtype=F64) + 0.5 - b[:, 0:1]) / (b[:, 2:3] - b[:, 0:1]) * 2 - 1
+    grid = torch.stack([gx[:, None, :].expand(-1, h, w), gy[:, :, None].expand(-1, h, w)], dim=3)
+    ref = TF.grid_sample(probs[:, None].to(F64), grid, align_corners=False)[:, 0]
+    assert float((v - ref).abs().max()) <= 1e-13
+    ones = TF.grid_sample(torch.ones_like(probs[:, None], dtype=F64), grid, align_corners=False)[:, 0]
+    assert torch.equal(inside, ones > 0)
+    assert 0.05 < float(inside.double().mean()) < 0.95
+
+
+@pytest.mark.parametrize("s", [1, 2, 3, 4])
+@pytest.mark.parametrize("hw", R.SEM_MAPS + [(9, 11)])
+def test_upsample_ref_equals_interpolate_float64(hw, s):
+    g = torch.Generator().manual_seed(s)
+    x = torch.randn((2, hw[0], hw[1], 16), generator=g).bfloat16()
+    ref = TF.interpolate(x[..., :9].to(F64).permute(0, 3, 1, 2), scale_factor=s, mode="bilinear", align_corners=False)
+    got = R.upsample_ref(x, 9, s)
+    assert got.shape == ref.shape and float((got - ref).abs().max()) <= 1e-14 * 8
+
+
+@pytest.mark.parametrize("k,cp", R.SEM_EXACT_CASES)
+def test_upsample_exact_case_is_exact_and_holds_its_ties(k, cp):
+    """The exact-input generator: bf16 values, |v| <= 32, multiples of 1/4; the float64 upsampling is an fp32 number everywhere;
+    the ties it promises are there (so first-index-wins is really exercised) and first_argmax == torch.argmax."""
+    for h, w in R.SEM_MAPS:
+        for s in (2, 4):
+            x = R.upsample_exact_case(2, h, w, cp, k, 1e30)
+            xk = x[..., :k]
+            assert torch.equal(xk, xk.bfloat16().to(F64)) and float(xk.abs().max()) <= 32 and torch.equal(xk * 4, (xk * 4).round())
+            assert bool((x[1, ..., :k] < 0).all())
+            ref = R.upsample_ref(x, k, s)
+            assert torch.equal(ref, ref.float().to(F64))
+            am = R.first_argmax(ref)
+            assert torch.equal(am, ref.argmax(1))
+            assert int(am[0, 0, 0]) == 0 and bool((ref[0, :, 0, 0] == ref[0, 0, 0, 0]).all())
+            if k > 1:
+                n_max = (ref == ref.max(1, keepdim=True).values).sum(1)
+                assert bool((n_max > 1).any()) and bool((am != k - 1).all())   # the copy never wins over the channel it copies
+                assert h * w == 1 or bool((am > 0).any())
+
+
+def _resize_cases():
+    return [((150, 200), (225, 300)), ((33, 47), (160, 224)), ((160, 224), (97, 133)), ((1, 47), (8, 100)), ((33, 1), (50, 7)),
+            ((33, 47), (1, 1)), ((12, 20), (24, 40)), ((12, 20), (6, 10)), ((21, 13), (21, 13))]
+
+
+@pytest.mark.parametrize("src,dst", _resize_cases())
+def test_resize_ref_equals_interpolate_float64(src, dst):
+    """resize_ref forms the scale in fp32 like ATen's fp32 kernel; ATen's float64 kernel forms it in float64.  The two source
+    coordinates differ by at most 2^-24 scale (dst + 0.5) <= 2^-24 Hin (Win) per axis, bilinear interpolation is continuous and
+    piecewise linear, so the values differ by at most 2^-24 (Hin + Win) times the largest step between neighbouring inputs.
+    Power-of-two scales are the same number in both formats: equal to float64 round-off there."""
+    g = torch.Generator().manual_seed(src[0] * 7 + dst[1])
+    x = torch.randn((3,) + src, generator=g)
+    ref = TF.interpolate(x.to(F64)[None], size=dst, mode="bilinear", align_corners=False)[0]
+    got = R.resize_ref(x, *dst)
+    step = max(float((x[:, 1:] - x[:, :-1]).abs().max()) if src[0] > 1 else 0.0,
+               float((x[:, :, 1:] - x[:, :, :-1]).abs().max()) if src[1] > 1 else 0.0)
+    exact_scale = all(float(torch.tensor(float(a)) / torch.tensor(float(b))) == a / b for a, b in zip(src, dst))
+    bound = 1e-14 if exact_scale else 2.0 ** -24 * (src[0] + src[1]) * step
+    assert got.shape == ref.shape and float((got - ref).abs().max()) <= bound, (float((got - ref).abs().max()), bound)
+
+
+@pytest.mark.parametrize("n,side,c,k", [(37, 7, 264, 800), (1, 1, 8, 1), (3, 14, 1024, 5), (2, 28, 64, 9)])
+def test_mask_prob_ref_equals_conv2d_float64_and_channel_pick(n, side, c, k):
+    """mask_prob_ref against the reference's order of operations - the K-channel 1x1 conv in float64 on the bf16-rounded operands,
+    the predicted class's channel, bf16 rounding, sigmoid - on the exact-input generator (equal: every sum is exact) and on
+    random weights (the float64 sums may differ in the last bit, so the rounded logits may differ on a rounding boundary: none
+    does at these sizes).  The generator's claims: integer multiples of 2^-8 below 2^24 of them, some exact halves."""
+    x, w, b, cls, ax, aw = R.mask_prob_case(n, side, c, k)
+    assert torch.equal(x, x.bfloat16().to(F64)) and torch.equal(w, w.bfloat16().float()) and torch.equal(b, b.bfloat16().float())
+    assert c * ax * aw + 255 < 1 << 24 and int(cls[0]) == 0 and int(cls[-1]) == k - 1
+    g = torch.Generator().manual_seed(5)
+    for wt, bs in ((w, b), (torch.randn((k, c), generator=g) / c ** 0.5, torch.randn(k, generator=g) * 0.1)):
+        prob, z = R.mask_prob_ref(x, wt, bs, cls)
+        conv = TF.conv2d(x.permute(0, 3, 1, 2), R.bf16_round(wt).view(k, c, 1, 1), R.bf16_round(bs))   # [n, k, side, side]
+        sel = torch.gather(conv, 1, cls.view(n, 1, 1, 1).expand(n, 1, side, side))
+        assert torch.equal(z, R.rne_bf16(sel)) and torch.equal(prob, torch.sigmoid(R.rne_bf16(sel)))
+        assert torch.equal(z, sel.float().bfloat16().to(F64))   # torch's own fp32 -> bf16 rounding of the (here exact) sums
+    if n * side * side >= 500:
+        exact = torch.einsum("nyxc,nc->nyx", x, w.to(F64)[cls]) + b.to(F64)[cls].view(-1, 1, 1)
+        a = exact.abs()
+        ulp = 2.0 ** (torch.floor(torch.log2(a.clamp(min=2.0 ** -20))) - 7)
+        half = (a >= 1) & (torch.remainder(a / ulp, 1.0) == 0.5)
+        assert int(half.sum()) >= 3 and float(((a >= 1) & (a <= 8)).double().mean()) > 0.3
