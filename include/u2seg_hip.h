@@ -564,6 +564,23 @@ int u2_cocoeval_lds_iou_entries(void);
 int u2_cocoeval_lds_max_gt(void);
 int u2_cocoeval_scan_chunk(void);
 
+/* ---- boundary IoU of the semantic evaluation (semeval.hip): evaluation/semseg_ops.py, DESIGN.md section 16 ---------------------
+ * The reference's _mask_to_boundary (evaluation/sem_seg_evaluation.py:396-407) and the two bincounts of its process():
+ * erode(m)[y][x] = minimum of m over the (2 d + 1) x (2 d + 1) window centred on (y, x), everything outside the image counted
+ * as 0 (the zero ring and d passes of a 3 x 3 minimum); boundary(m) = m - erode(m) in uint8, a difference of label values.
+ * pred, gt: [h][w] uint8 device maps, any alignment; lut: 256 uint8 entries applied to pred BEFORE the erosion, or NULL for
+ * identity; d >= 1 is computed by the caller (max(1, round(0.02 * sqrt(h^2 + w^2))), half to even).  n <= 32 is the side of
+ * the matrices; a pixel whose mapped prediction or ground truth is >= n is counted in neither.
+ *   bconf[n * boundary(lut[pred]) + boundary(gt)] += 1 for every pixel, and, when conf is not NULL, from the same read
+ *   conf[n * lut[pred] + gt] += 1.  Both are int64 [n][n] on the device, added to with integer atomics, never cleared: exact.
+ * d <= u2_semseg_boundary_fused_cap(): one fused kernel (64 x 64 tile + halo in LDS), no scratch.  A larger d takes a row
+ * pass and a column pass through scratch, u2_semseg_boundary_scratch_bytes(h, w, d) bytes owned by the caller (0 in the
+ * fused range).  h * w < 2^31.  Returns -1 for n outside 1..32, d < 1, h or w < 1, a NULL map or bconf, or too little scratch. */
+int u2_semseg_boundary_confusion(const void* pred, const void* gt, const void* lut, int h, int w, int d, int n,
+                                 long long* conf, long long* bconf, void* scratch, long long scratch_bytes, void* stream);
+int u2_semseg_boundary_fused_cap(void);
+long long u2_semseg_boundary_scratch_bytes(int h, int w, int d);
+
 /* ---- optimizer (optim.hip): solver/build.py:36-37,63-73,119-139 ------------------------------- */
 int u2_sgd_clip_step(float* params, const float* grads, float* momentum_buf, const int* chunk_tensor,
                      const long long* chunk_begin, const int* chunk_len, int n_chunks, float* partial /*[n_chunks]*/,

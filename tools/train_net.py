@@ -75,7 +75,7 @@ def precise_bn_batches(cfg, device, per_gpu, rank, world):
 
 
 def evaluate_on_disk_datasets(cfg, model, eval_mode, device, tasks=("bbox",), panoptic_pq="files", gt_polygons="refuse",
-                              coco_eval="host"):
+                              coco_eval="host", sem_seg_boundary_iou=False):
     """The reference's Trainer.test (engine/defaults.py:591-640) for the DATASETS.TEST entries that are on disk: first run
     with --eval-mode hungarian_matching (writes ./hungarian_matching/*.json), then with --eval-mode eval.  None when no
     test dataset is available."""
@@ -92,7 +92,8 @@ def evaluate_on_disk_datasets(cfg, model, eval_mode, device, tasks=("bbox",), pa
         stream = DevicePrefetcher(loader, device) if str(device).startswith("cuda") else loader
         results[name] = inference_on_dataset(model, stream, build_evaluator(cfg, name, eval_mode=eval_mode, tasks=tasks,
                                                                                   panoptic_pq=panoptic_pq, gt_polygons=gt_polygons,
-                                                                                  coco_eval=coco_eval))
+                                                                                  coco_eval=coco_eval,
+                                                                                  sem_seg_boundary_iou=sem_seg_boundary_iou))
     return results or None
 
 
@@ -117,7 +118,7 @@ def main(args):
             DetectionCheckpointer(model, cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
         tasks = tuple(t for t in args.eval_tasks.split(",") if t)
         results = evaluate_on_disk_datasets(cfg, model, args.eval_mode, c.MODEL.DEVICE, tasks, args.panoptic_pq,
-                                            args.eval_gt_polygons, args.coco_eval)
+                                            args.eval_gt_polygons, args.coco_eval, args.sem_seg_boundary_iou)
         if results is not None:
             if rank == 0:
                 print(results)

@@ -116,6 +116,8 @@ def default_argument_parser():
                    help="AP matching and accumulation in numpy (host) or by the HIP kernels on the GPU (device), same numbers")
     p.add_argument("--eval-gt-polygons", default="refuse", choices=("refuse", "rasterize"),
                    help="polygon ground truth in the segm task: refuse it, or rasterize it as cocoapi does (COCO val2017)")
+    p.add_argument("--sem-seg-boundary-iou", action="store_true",
+                   help="the semantic evaluator also reports BoundaryIoU and min(IoU, B-Iou) per class (eval mode)")
     p.add_argument("--num-gpus", type=int, default=1)
     p.add_argument("--num-machines", type=int, default=1)
     p.add_argument("--machine-rank", type=int, default=0)

@@ -6,7 +6,11 @@ IoU > 0.15 is a vote; evaluate() writes the majority mapping to ./hungarian_matc
 mode "eval": predictions are mapped (unmapped classes become the extra "ignore" label 16), a 17 x 17 confusion matrix is
 accumulated with one bincount per image on the device the predictions live on, and mIoU / fwIoU / mACC / pACC plus the
 per-class numbers come out of it.
-Boundary IoU needs OpenCV, which this image does not have; the reference switches it off in that case too (:103-109)."""
+boundary_iou=True (eval mode, off by default): the reference's Boundary IoU (:269-276, 344-360, 396-407).  Its cv2 erosion is
+a (2 d + 1)-square minimum with zeros outside the image, so no OpenCV is needed: evaluation/semseg_ops.py computes the second
+17 x 17 matrix of boundary-value pairs, for predictions on a GPU with one HIP launch per image that accumulates both matrices
+(csrc/semeval.hip), and evaluate() adds "BoundaryIoU-<name>" and "min(IoU, B-Iou)-<name>" behind every
+"IoU-<name>".  Off, the evaluator does and reports exactly what it did without the option."""
 from collections import OrderedDict
 
 import numpy as np
@@ -14,7 +18,7 @@ import torch
 from PIL import Image
 
 from ..data.catalog import DatasetCatalog, MetadataCatalog
-from . import hungarian
+from . import hungarian, semseg_ops
 from .evaluator import DatasetEvaluator, gather_to_rank0
 
 SUPERCATEGORIES = ("textile", "building", "raw-material", "furniture-stuff", "floor", "plant", "food-stuff", "ground",
@@ -41,7 +45,8 @@ def to_supercategories(gt):
 
 class SemSegEvaluator(DatasetEvaluator):
     def __init__(self, dataset_name, output_dir=None, *, mode="hungarian_matching",
-                 mapping_path="./hungarian_matching/semantic_mapping.json", sem_seg_loading_fn=load_image_into_numpy_array):
+                 mapping_path="./hungarian_matching/semantic_mapping.json", sem_seg_loading_fn=load_image_into_numpy_array,
+                 boundary_iou=False):
         self._dataset_name, self._output_dir = dataset_name, output_dir
         self.input_file_to_gt_file = {r["file_name"]: r["sem_seg_file_name"] for r in DatasetCatalog.get(dataset_name)}
         meta = MetadataCatalog.get(dataset_name)
@@ -50,13 +55,15 @@ class SemSegEvaluator(DatasetEvaluator):
         self._num_classes = 16
         self.sem_seg_loading_fn = sem_seg_loading_fn
         self.mode = mode
+        self._boundary_iou = bool(boundary_iou)
         self.hungarain_matching_save_path = mapping_path
         self.pseudo_gt_cate, self.pred_det_cate = [], []
-        self._lut = None
+        self._lut = self._lut8 = None
         self.reset()
 
     def reset(self):
         self._conf_matrix = torch.zeros((self._num_classes + 1, self._num_classes + 1), dtype=torch.int64)
+        self._b_conf_matrix = torch.zeros_like(self._conf_matrix)
 
     def _collect_votes(self, pred, gt):
         """One joint histogram of (predicted class, ground-truth supercategory) gives every pairwise intersection; with the
@@ -81,7 +88,8 @@ class SemSegEvaluator(DatasetEvaluator):
             pred = out["sem_seg"].argmax(dim=0)  # stays on the model's device
             gt_np = to_supercategories(self.sem_seg_loading_fn(self.input_file_to_gt_file[inp["file_name"]], dtype=int))
             gt_np[gt_np == self._ignore_label] = self._num_classes
-            gt = torch.from_numpy(gt_np).to(pred.device)
+            boundary = self._boundary_iou and self.mode != "hungarian_matching"
+            gt = torch.from_numpy(gt_np.astype(np.uint8) if boundary else gt_np).to(pred.device)
             if self.mode == "hungarian_matching":
                 self._collect_votes(pred, gt)
                 continue
@@ -96,6 +104,14 @@ class SemSegEvaluator(DatasetEvaluator):
             lut = self._lut.to(pred.device)
             if self._conf_matrix.device != pred.device:
                 self._conf_matrix = self._conf_matrix.to(pred.device)
+                self._b_conf_matrix = self._b_conf_matrix.to(pred.device)
+            if boundary:
+                # one pass over the two maps for both matrices; the mapping goes in as a table, applied before the erosion
+                if self._lut8 is None or self._lut8.device != pred.device:
+                    self._lut8 = lut.to(torch.uint8)
+                semseg_ops.boundary_confusion(pred.to(torch.uint8), gt, self._lut8, semseg_ops.boundary_dilation(*pred.shape), n,
+                                              self._conf_matrix, self._b_conf_matrix)
+                continue
             self._conf_matrix += torch.bincount(n * lut[pred].reshape(-1) + gt.reshape(-1), minlength=n * n).view(n, n)
 
     def cluster_mapping(self):
@@ -113,10 +129,14 @@ class SemSegEvaluator(DatasetEvaluator):
             mapping = self.cluster_mapping()
             hungarian.save_mapping(mapping, self.hungarain_matching_save_path)
             return OrderedDict({"sem_seg": None, "semantic_mapping": mapping})
-        mats = gather_to_rank0(self._conf_matrix.cpu().numpy())
+        if self._boundary_iou:
+            mats = gather_to_rank0(np.stack([self._conf_matrix.cpu().numpy(), self._b_conf_matrix.cpu().numpy()]))
+        else:
+            mats = gather_to_rank0(self._conf_matrix.cpu().numpy())
         if mats is None:
             return None
-        cm = self._conf_matrix = sum(mats[1:], mats[0].copy())
+        total = sum(mats[1:], mats[0].copy())
+        cm = self._conf_matrix = total[0] if self._boundary_iou else total
         acc = np.full(self._num_classes, np.nan, dtype=float)
         iou = np.full(self._num_classes, np.nan, dtype=float)
         tp = cm.diagonal()[:-1].astype(float)
@@ -130,8 +150,20 @@ class SemSegEvaluator(DatasetEvaluator):
         iou[iou_valid] = tp[iou_valid] / union[iou_valid]
         res = {"mIoU": 100 * np.sum(iou[iou_valid]) / np.sum(iou_valid),
                "fwIoU": 100 * np.sum(iou[iou_valid] * class_weights[iou_valid])}
+        if self._boundary_iou:
+            bcm = self._b_conf_matrix = total[1]
+            b_iou = np.full(self._num_classes, np.nan, dtype=float)
+            b_tp = bcm.diagonal()[:-1].astype(float)
+            b_pos_gt = np.sum(bcm[:-1, :-1], axis=0).astype(float)
+            b_pos_pred = np.sum(bcm[:-1, :-1], axis=1).astype(float)
+            b_union = b_pos_gt + b_pos_pred - b_tp
+            b_iou_valid = b_union > 0  # no acc_valid here, unlike iou: as the reference has it
+            b_iou[b_iou_valid] = b_tp[b_iou_valid] / b_union[b_iou_valid]
         for i, name in enumerate(self._class_names):
             res["IoU-" + name] = 100 * iou[i]
+            if self._boundary_iou:
+                res["BoundaryIoU-" + name] = 100 * b_iou[i]
+                res["min(IoU, B-Iou)-" + name] = 100 * min(iou[i], b_iou[i])  # with a NaN the order of the arguments decides
         res["mACC"] = 100 * np.sum(acc[acc_valid]) / np.sum(acc_valid)
         res["pACC"] = 100 * np.sum(tp) / np.sum(pos_gt)
         for i, name in enumerate(self._class_names):
