@@ -581,6 +581,51 @@ int u2_semseg_boundary_confusion(const void* pred, const void* gt, const void* l
 int u2_semseg_boundary_fused_cap(void);
 long long u2_semseg_boundary_scratch_bytes(int h, int w, int d);
 
+/* ---- training augmentation on the device (augment.hip): data/device_mapper.py, DESIGN.md section 17 --------------------------
+ * What the host mapper does with PIL and numpy after loading a sample - bilinear resize of the image, nearest resize of the
+ * label map, RLE decode + nearest resize of the masks, flips - from tables the worker built on the host.  Everything is
+ * integer arithmetic: exact.  One call per stage serves a whole per-GPU batch: `images` is a HOST array of descriptors.
+ *
+ * `block` is one device allocation of block_bytes bytes that holds every input of the batch, `tables_host` a host copy of the
+ * same bytes (the pinned staging block it was copied from); the launchers read the tables and run ends of the host copy to
+ * check the contract before anything is launched, the kernels read the device copy.  Offsets named *_offset are byte offsets
+ * into the block, the table fields are int32 ELEMENT offsets into it (block and every table 4-byte aligned):
+ *   bx_bounds [W][2] / by_bounds [H][2]: (first source index, tap count >= 1) per output index, first + count <= w / h,
+ *   count <= kx / ky;  bx_coef [W][kx] / by_coef [H][ky]: int32 coefficients (22 fractional bits);
+ *   nx [W] / ny [H]: nearest source index per output index;
+ *   mask_offs [num_masks + 1]: where every mask's run ends begin (and the last one's end), as elements behind ends_base (itself
+ *   an element offset into the block); a mask's run ends are the inclusive prefix sums of its RLE counts, uint32:
+ *   non-decreasing, at least one, the last one == h * w.
+ * A flip is a reversed table: the kernels know nothing about it.  x_identity / y_identity: w == W / h == H, that pass is
+ * skipped (its table has one tap and is used as an index table only).  row0, nrows: the source rows the vertical pass reads
+ * (every by_bounds row inside [row0, row0 + nrows)); only those go through the horizontal pass.  h * w and H * W < 2^31.
+ * Status: 0 ok; -1 bad argument (sizes, offsets or buffers too small); -2 bad run ends; -3 a table entry out of range.  Nothing
+ * is launched and no output is written unless the status is 0. */
+typedef struct U2AugImage {
+  int h, w, H, W;
+  int kx, ky, x_identity, y_identity;
+  int row0, nrows, num_masks, first_mask;
+  long long src_offset, lab_offset;              /* HWC uint8 [h][w][3]; uint8 [h][w] (-1: no label map) */
+  long long img_out_offset, lab_out_offset, mask_out_offset; /* bytes in img_out; int64 ELEMENTS in lab_out; bytes in mask_out */
+  long long bx_bounds, bx_coef, by_bounds, by_coef, nx, ny, mask_offs, ends_base;
+} U2AugImage;
+/* img_out[img_out_offset + (c * H + y) * W + x] = clip8((2^21 + sum_k t[c][by_first[y] + k][x] * by_coef[y][k]) >> 22) with
+ * t[c][r][x] = clip8((2^21 + sum_k src[r][bx_first[x] + k][c] * bx_coef[x][k]) >> 22) rounded to uint8 (PIL's order: horizontal
+ * first), any tap count.  scratch: u2_aug_resize_bilinear_scratch_bytes(images, num_images) bytes (t of the images that
+ * need both passes; -1 for a bad descriptor). */
+long long u2_aug_resize_bilinear_scratch_bytes(const U2AugImage* images, int num_images);
+int u2_aug_resize_bilinear_u8(const void* block, long long block_bytes, const void* tables_host, void* img_out,
+                              long long img_out_bytes, void* scratch, long long scratch_bytes, const U2AugImage* images,
+                              int num_images, void* stream);
+/* lab_out[lab_out_offset + y * W + x] = label[ny[y]][nx[x]] as int64; images with lab_offset < 0 are skipped. */
+int u2_aug_resize_nearest_u8(const void* block, long long block_bytes, const void* tables_host, long long* lab_out,
+                             long long lab_out_elems, const U2AugImage* images, int num_images, void* stream);
+/* mask_out[mask_out_offset + (m * H + y) * W + x] = parity of the number of run ends of mask m that are <= nx[x] * h + ny[y]
+ * (bytes 0 / 1), counts[first_mask + m] = the number of 1 bytes written (int32, cleared by the call). */
+int u2_aug_rle_masks(const void* block, long long block_bytes, const void* tables_host, void* mask_out,
+                     long long mask_out_bytes, int* counts, int num_counts, const U2AugImage* images, int num_images,
+                     void* stream);
+
 /* ---- optimizer (optim.hip): solver/build.py:36-37,63-73,119-139 ------------------------------- */
 int u2_sgd_clip_step(float* params, const float* grads, float* momentum_buf, const int* chunk_tensor,
                      const long long* chunk_begin, const int* chunk_len, int n_chunks, float* partial /*[n_chunks]*/,

@@ -2,7 +2,12 @@
 """Input-pipeline throughput: DatasetMapper (JPEG decode, ResizeShortestEdge over the config's 10 short-edge choices, flip,
 RLE -> bitmasks) in DataLoader workers, optionally through DevicePrefetcher into HBM.  Builds a throw-away COCO-shaped
 dataset (480x640 / 640x480 JPEGs, 7 RLE instances per image, semantic label maps) under a temp dir, so it runs anywhere.
-Prints one JSON line per worker count; the training step consumes ~197 img/s per GPU."""
+Prints one JSON line per worker count; the training step consumes ~197 img/s per GPU.
+
+--device-mapper: every worker count runs twice in the same process, the host mapper first and then the DeviceMapper whose raw
+records DevicePrefetcher finishes on the GPU; also prints the mapper time per image in one process for
+both mappers, the bytes per batch that cross the shared-memory slot, and the HIP-event time of the three augmentation calls on
+a full per-GPU batch.  --out FILE collects every line into one JSON file."""
 import argparse
 import json
 import os
@@ -51,6 +56,65 @@ def make_dataset(root, n_images, seed=0):
               open(os.path.join(ann_dir, "cocotrain_800.json"), "w"))
 
 
+def mapper_ms_per_image(cfg, device_mapper, dicts, repeats=2):
+    """Mapper time per image in this process (no loader, no transport)."""
+    from u2seg_amd.data import DatasetMapper
+    from u2seg_amd.data.device_mapper import DeviceMapper
+
+    mapper = DeviceMapper(cfg, True) if device_mapper else DatasetMapper(cfg, True)
+    np.random.seed(0)
+    for d in dicts[:4]:
+        mapper(d)
+    t0 = time.perf_counter()
+    for _ in range(repeats):
+        for d in dicts:
+            mapper(d)
+    return 1e3 * (time.perf_counter() - t0) / (repeats * len(dicts))
+
+
+def kernel_times(cfg, dicts, device, batch_size, repeats=20):
+    """HIP-event time of the three calls of csrc/augment.hip on one per-GPU batch of raw records (ms per batch, median)."""
+    from u2seg_amd import _hip
+    from u2seg_amd.data import device_mapper as dm
+    from u2seg_amd.data.slots import layout_batch, unpack, write_batch
+
+    np.random.seed(0)
+    mapper = dm.DeviceMapper(cfg, True)
+    records = [mapper(dicts[i % len(dicts)]) for i in range(batch_size)]
+    staged, nbytes, samples = layout_batch(records)
+    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    write_batch(host.numpy(), staged)
+    block = host.to(device)
+    dev = unpack(block, samples)
+    descs, img_bytes, lab_elems, mask_bytes, masks = dm.describe_batch(dev, block.data_ptr())
+    n = len(dev)
+    image = torch.empty(img_bytes, dtype=torch.uint8, device=device)
+    labels = torch.empty(max(lab_elems, 1), dtype=torch.int64, device=device)
+    mask_out = torch.empty(max(mask_bytes, 1), dtype=torch.bool, device=device)
+    counts = torch.empty(max(masks, 1), dtype=torch.int32, device=device)
+    need = int(_hip.call_nostream("u2_aug_resize_bilinear_scratch_bytes", descs, n))
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    calls = [("bilinear", lambda: _hip.call("u2_aug_resize_bilinear_u8", block, nbytes, host.data_ptr(), image, img_bytes, scratch,
+                                             need, descs, n)),
+             ("nearest", lambda: _hip.call("u2_aug_resize_nearest_u8", block, nbytes, host.data_ptr(), labels, lab_elems, descs, n)),
+             ("rle_masks", lambda: _hip.call("u2_aug_rle_masks", block, nbytes, host.data_ptr(), mask_out, mask_bytes, counts,
+                                              masks, descs, n))]
+    times = {name: [] for name, _ in calls}
+    for it in range(repeats + 3):
+        for name, fn in calls:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if it >= 3:
+                times[name].append(e0.elapsed_time(e1))
+    out = {name: round(float(np.median(v)), 4) for name, v in times.items()}
+    out["total"] = round(sum(out.values()), 4)
+    out.update({"images": n, "masks": masks, "bytes_in": nbytes, "bytes_out": img_bytes + 8 * lab_elems + mask_bytes})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=48)
@@ -58,7 +122,18 @@ def main():
     ap.add_argument("--batches", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--device-mapper", action="store_true", help="run every worker count with the host mapper and with the "
+                    "DeviceMapper (needs a GPU: there is no host fallback)")
+    ap.add_argument("--out", default=None, help="also write every result line into this JSON file")
     a = ap.parse_args()
+    if a.device_mapper and not a.device.startswith("cuda"):
+        raise SystemExit("--device-mapper needs a GPU: raw records are finished by HIP kernels")
+    lines = []
+
+    def emit(d):
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+
     os.environ["CLUSTER_NUM"] = "800"
     from u2seg_amd.config import get_cfg
     from u2seg_amd.data import DevicePrefetcher, build_detection_train_loader, register_all_coco
@@ -69,18 +144,28 @@ def main():
     register_all_coco(root)
     cfg = get_cfg()
     cfg.merge_from_file(os.path.join(ROOT, "configs", "COCO-PanopticSegmentation", "u2seg_R50_800.yaml"))
-    print(json.dumps({"dataset": "%d synthetic JPEGs 480x640 / 640x480, 7 RLE instances each" % a.images,
-                      "build_s": round(time.time() - t0, 1), "short_edges": list(cfg.INPUT.MIN_SIZE_TRAIN)}))
-    for nw in a.workers:
+    emit({"dataset": "%d synthetic JPEGs 480x640 / 640x480, 7 RLE instances each" % a.images,
+          "build_s": round(time.time() - t0, 1), "short_edges": list(cfg.INPUT.MIN_SIZE_TRAIN)})
+    if a.device_mapper:
+        from u2seg_amd.data import get_detection_dataset_dicts
+
+        dicts = get_detection_dataset_dicts(cfg.DATASETS.TRAIN, filter_empty=cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS)
+        for dm_on in (False, True, False, True):  # alternating: the spread between equal runs is part of the result
+            emit({"metric": "mapper ms per image, one process", "device_mapper": dm_on,
+                  "ms_per_image": round(mapper_ms_per_image(cfg, dm_on, dicts), 2)})
+        emit(dict({"metric": "augmentation kernels, HIP-event ms per batch"},
+                  **kernel_times(cfg, dicts, a.device, cfg.SOLVER.IMS_PER_BATCH)))
+    for nw, dm_on in [(nw, dm_on) for nw in a.workers for dm_on in ((False, True) if a.device_mapper else (False,))]:
         cfg.defrost()
         cfg.merge_from_list(["DATALOADER.NUM_WORKERS", nw])
-        loader = build_detection_train_loader(cfg, seed=1)
+        loader = build_detection_train_loader(cfg, seed=1, device_mapper=dm_on)
         pre = DevicePrefetcher(loader, a.device) if a.device.startswith("cuda") else None
         stream = iter(pre if pre is not None else loader)
         for _ in range(a.warmup):  # worker start-up, pinned staging blocks, and the batches the workers prefetched
             next(stream)
         if pre is not None:
-            pre.seconds_waiting_for_loader = pre.seconds_staging = 0.0
+            pre.seconds_waiting_for_loader = pre.seconds_staging = pre.seconds_waiting_for_counts = 0.0
+            pre.slot_bytes_moved = 0
         t0, n, px = time.time(), 0, 0
         for _ in range(a.batches):
             batch = next(stream)
@@ -89,12 +174,19 @@ def main():
         if a.device.startswith("cuda"):
             torch.cuda.synchronize()
         dt = time.time() - t0
-        print(json.dumps({"metric": "input pipeline img/s", "workers": nw, "batch": len(batch), "img_per_s": round(n / dt, 1),
-                          "mean_megapixels": round(px / n / 1e6, 2), "to_device": a.device,
-                          "host_s_waiting_for_loader": round(pre.seconds_waiting_for_loader, 2) if pre else None,
-                          "host_s_staging": round(pre.seconds_staging, 2) if pre else None, "wall_s": round(dt, 2),
-                          "host_threads": torch.get_num_threads()}))
+        emit({"metric": "input pipeline img/s", "workers": nw, "device_mapper": dm_on, "batch": len(batch),
+              "img_per_s": round(n / dt, 1), "mean_megapixels": round(px / n / 1e6, 2), "to_device": a.device,
+              "host_s_waiting_for_loader": round(pre.seconds_waiting_for_loader, 2) if pre else None,
+              "host_s_staging": round(pre.seconds_staging, 2) if pre else None,
+              "host_s_waiting_for_counts": round(pre.seconds_waiting_for_counts, 4) if pre else None,
+              "slot_bytes_per_batch": int(pre.slot_bytes_moved / a.batches) if pre else None, "wall_s": round(dt, 2),
+              "host_threads": torch.get_num_threads()})
         del stream, loader, pre
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump({"tool": "tools/bench_data.py", "args": {k: v for k, v in vars(a).items() if k != "out"}, "results": lines},
+                      f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":

@@ -36,9 +36,13 @@ def setup(args):
     return cfg
 
 
-def real_batches(cfg, device, seed=None):
+def real_batches(cfg, device, seed=None, device_mapper=False):
     """Iterator over device-resident training batches of the real dataset, or None when it is not on disk.
-    seed: the sampler's seed (default: cfg.SEED, or a shared random one when it is negative)."""
+    seed: the sampler's seed (default: cfg.SEED, or a shared random one when it is negative).
+    device_mapper: the workers ship raw records and DevicePrefetcher finishes them with csrc/augment.hip."""
+    if device_mapper and not (str(device).startswith("cuda") and torch.cuda.is_available()):
+        raise RuntimeError("--device-mapper finishes the samples with HIP kernels: it needs a GPU (MODEL.DEVICE is %r); there "
+                           "is no host fallback" % (device,))
     names = [n for n in cfg.DATASETS.TRAIN if n != "synthetic"]
     if not names:
         return None
@@ -49,7 +53,7 @@ def real_batches(cfg, device, seed=None):
             return None
     if seed is None and cfg.SEED >= 0:
         seed = cfg.SEED
-    loader = build_detection_train_loader(cfg, seed=seed)
+    loader = build_detection_train_loader(cfg, seed=seed, device_mapper=device_mapper)
     return iter(DevicePrefetcher(loader, device) if str(device).startswith("cuda") else loader)
 
 
@@ -142,7 +146,10 @@ def main(args):
         sched.resume_at(start_iter)  # lr of iteration start_iter, milestones counted from iteration 0
     elif cfg.MODEL.WEIGHTS and rank == 0:
         print("MODEL.WEIGHTS %s not found: random initialisation" % cfg.MODEL.WEIGHTS)
-    stream = real_batches(cfg, c.MODEL.DEVICE)
+    stream = real_batches(cfg, c.MODEL.DEVICE, device_mapper=args.device_mapper)
+    if args.device_mapper and stream is None:
+        raise RuntimeError("--device-mapper needs the real dataset %s on disk: the synthetic generator has no mapper"
+                           % (cfg.DATASETS.TRAIN,))
     if rank == 0:
         print("data: %s" % ("real pipeline over %s" % (cfg.DATASETS.TRAIN,) if stream is not None else "synthetic generator"))
     # engine/defaults.py:428-452: the PreciseBN hook, registered before the checkpointer, so that the checkpoint of the same

@@ -16,6 +16,7 @@ import torch.utils.data as torchdata
 
 from .catalog import DatasetCatalog
 from .dataset_mapper import DatasetMapper
+from .device_mapper import RAW_KEY
 
 logger = logging.getLogger(__name__)
 
@@ -258,10 +259,19 @@ def build_batch_data_loader(dataset, sampler, total_batch_size, *, aspect_ratio_
                                 worker_init_fn=worker_init_reset_seed, **kwargs)
 
 
-def build_detection_train_loader(cfg, mapper=None, *, dataset=None, sampler=None, seed=None):
-    """build.py:437-551 for the sampler the U2Seg configs name (TrainingSampler)."""
+def build_detection_train_loader(cfg, mapper=None, *, dataset=None, sampler=None, seed=None, device_mapper=False):
+    """build.py:437-551 for the sampler the U2Seg configs name (TrainingSampler).
+
+    device_mapper=True: the workers run data/device_mapper.py's DeviceMapper and the loader yields raw records (source-size
+    pixels, undecoded RLE runs, index tables); DevicePrefetcher finishes them on the GPU into exactly what the default mapper
+    yields.  There is no host fallback for that: the loader must be wrapped in a DevicePrefetcher on a GPU."""
     if dataset is None:
         dataset = get_detection_dataset_dicts(cfg.DATASETS.TRAIN, filter_empty=cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS)
+    if device_mapper:
+        from .device_mapper import DeviceMapper
+
+        assert mapper is None, "device_mapper=True builds its own mapper"
+        mapper = DeviceMapper(cfg, True)
     if mapper is None:
         mapper = DatasetMapper(cfg, True)
     if sampler is None:
@@ -321,7 +331,11 @@ class DevicePrefetcher:
     The next batch is packed into one of three reusable pinned staging blocks and copied on a dedicated HIP stream while
     the caller still computes on the current one; before a batch is handed out the consumer stream waits on the copy's
     event, and the tensors are recorded on the consumer stream so the caching allocator does not recycle them early.
-    Label maps travel as bytes (the mapper's int64 has 8x the volume for values 0..255) and are widened on the device."""
+    Label maps travel as bytes (the mapper's int64 has 8x the volume for values 0..255) and are widened on the device.
+
+    Raw records (build_detection_train_loader(device_mapper=True)) are finished here: after the copy, the three calls of
+    csrc/augment.hip run on the prefetch stream and the per-mask pixel counts start their way back to pinned memory; rows whose
+    mask came out empty are dropped when the batch is handed out, one step later (`seconds_waiting_for_counts`)."""
 
     def __init__(self, loader, device, _pinned=True):
         self.ring = getattr(loader, "ring", None)  # HostUnpacked: take the packed stream and unpack on the device instead
@@ -332,6 +346,9 @@ class DevicePrefetcher:
         self.arenas = [_StagingArena(_pinned) for _ in range(3)]
         self.turn = 0
         self.seconds_waiting_for_loader = self.seconds_staging = 0.0  # where the host time of this iterator went
+        self.seconds_waiting_for_counts = 0.0  # raw records: waiting at hand-out for the kernels' per-mask counts
+        self.counts = [None] * len(self.arenas)  # pinned landing buffers of those counts, one per staging block
+        self.slot_bytes_moved = 0  # bytes that came through shared-memory slots (tools/bench_data.py)
 
     @staticmethod
     def _tensors_of(v):
@@ -360,17 +377,30 @@ class DevicePrefetcher:
     def _stage_packed(self, packed):
         """A batch that arrived in a shared-memory slot: one memcpy into the pinned block, one host-to-device copy, the
         tensors rebuilt on the device as views of that block (label maps and bit-packed masks widened there)."""
-        from .slots import unpack
-
-        arena = self.arenas[self.turn]
+        turn = self.turn
+        arena = self.arenas[turn]
         self.turn = (self.turn + 1) % len(self.arenas)
         arena.reset(self.ring.slot_bytes)  # full slot size from the start: the pinned block is allocated exactly once
         np.copyto(arena.buf[: packed.nbytes].numpy(), self.ring.view(packed.slot)[: packed.nbytes])
+        self.slot_bytes_moved += packed.nbytes
+        return self._ship_block(turn, packed.nbytes, packed.samples)
+
+    def _ship_block(self, turn, nbytes, samples):
+        """The first nbytes of staging block `turn` hold a batch laid out as `samples` says (data/slots.py): one copy to the
+        device, the tensors rebuilt there; raw records then go through the augmentation kernels."""
+        from .slots import is_raw, unpack
+
+        arena = self.arenas[turn]
         ctx = torch.cuda.stream(self.stream) if self.on_gpu else contextlib.nullcontext()
         with ctx:
-            staged = arena.buf[: packed.nbytes]
+            staged = arena.buf[:nbytes]
             block = staged.to(self.device, non_blocking=True) if self.on_gpu else staged.clone()
-            moved = unpack(block, packed.samples)
+            moved = unpack(block, samples)
+            if is_raw(samples):
+                from .device_mapper import launch_batch
+
+                moved = launch_batch(moved, block, staged, self.counts[turn])  # raises without a GPU: no host fallback
+                self.counts[turn] = moved.counts_host
             done = None
             if self.on_gpu:
                 done = torch.cuda.Event()
@@ -381,6 +411,15 @@ class DevicePrefetcher:
     def _stage(self, batch):
         if not isinstance(batch, list):
             return self._stage_packed(batch)
+        if batch and isinstance(batch[0], dict) and RAW_KEY in batch[0]:  # raw records that did not come through a slot
+            from .slots import layout_batch, write_batch
+
+            staged, nbytes, samples = layout_batch(batch)
+            turn = self.turn
+            self.turn = (self.turn + 1) % len(self.arenas)
+            self.arenas[turn].reset(nbytes)
+            write_batch(self.arenas[turn].buf.numpy(), staged)
+            return self._ship_block(turn, nbytes, samples)
         arena = self.arenas[self.turn]
         self.turn = (self.turn + 1) % len(self.arenas)
         arena.reset(_StagingArena.footprint([t for d in batch for v in d.values() for t in self._tensors_of(v)]))
@@ -435,5 +474,10 @@ class DevicePrefetcher:
             pending = self._next_staged(it)
             if self.on_gpu:
                 torch.cuda.current_stream(self.device).wait_event(done)
+                if not isinstance(batch, list):  # raw records: the counts were copied before `done` was recorded
+                    t0 = time.perf_counter()
+                    done.synchronize()
+                    self.seconds_waiting_for_counts += time.perf_counter() - t0
+                    batch = batch.finish(torch.cuda.current_stream(self.device))
                 self._record(batch)
             yield batch

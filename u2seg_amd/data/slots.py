@@ -63,35 +63,53 @@ class BatchPacker:
     def __call__(self, batch):
         if self.ring is None:
             return batch
-        staged, cursor, samples = [], 0, []
-        for d in batch:
-            entries = []
-            for key, v in d.items():
-                if isinstance(v, torch.Tensor):
-                    arr, enc, dtype, shape = _encode(v)
-                    entries.append((key, "tensor", enc, dtype, shape, cursor, arr.shape))
-                    staged.append((cursor, arr))
-                    cursor = _align(cursor + arr.nbytes)
-                elif isinstance(v, Instances):
-                    fields = []
-                    for name, f in v.get_fields().items():
-                        arr, enc, dtype, shape = _encode(getattr(f, "tensor", f))
-                        fields.append((name, type(f) if hasattr(f, "tensor") else None, enc, dtype, shape, cursor, arr.shape))
-                        staged.append((cursor, arr))
-                        cursor = _align(cursor + arr.nbytes)
-                    entries.append((key, "instances", tuple(v.image_size), fields))
-                else:
-                    entries.append((key, "value", v))
-            samples.append(entries)
+        staged, cursor, samples = layout_batch(batch)
         if cursor > self.ring.slot_bytes:
             return batch
         info = torchdata.get_worker_info()
         slot = (info.id if info is not None else 0) * self.ring.depth + self._count % self.ring.depth
         self._count += 1
-        buf = self.ring.view(slot)
-        for off, arr in staged:
-            buf[off:off + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+        write_batch(self.ring.view(slot), staged)
         return PackedBatch(slot, cursor, samples)
+
+
+def layout_batch(batch):
+    """Where every tensor of a batch (list of mapped dicts or raw records) goes in one block: (staged = [(offset, array)],
+    bytes, samples = the layout record `unpack` reads)."""
+    staged, cursor, samples = [], 0, []
+    for d in batch:
+        entries = []
+        for key, v in d.items():
+            if isinstance(v, torch.Tensor):
+                arr, enc, dtype, shape = _encode(v)
+                entries.append((key, "tensor", enc, dtype, shape, cursor, arr.shape))
+                staged.append((cursor, arr))
+                cursor = _align(cursor + arr.nbytes)
+            elif isinstance(v, Instances):
+                fields = []
+                for name, f in v.get_fields().items():
+                    arr, enc, dtype, shape = _encode(getattr(f, "tensor", f))
+                    fields.append((name, type(f) if hasattr(f, "tensor") else None, enc, dtype, shape, cursor, arr.shape))
+                    staged.append((cursor, arr))
+                    cursor = _align(cursor + arr.nbytes)
+                entries.append((key, "instances", tuple(v.image_size), fields))
+            else:
+                entries.append((key, "value", v))
+        samples.append(entries)
+    return staged, cursor, samples
+
+
+def write_batch(buf, staged):
+    """buf: uint8 numpy view of the block."""
+    for off, arr in staged:
+        buf[off:off + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+
+
+def is_raw(samples):
+    """Whether the layout record of a packed batch describes raw records of the DeviceMapper (data/device_mapper.py)."""
+    from .device_mapper import RAW_KEY
+
+    return bool(samples) and any(e[0] == RAW_KEY for e in samples[0])
 
 
 _SHIFTS = {}
