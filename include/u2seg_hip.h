@@ -68,6 +68,19 @@ int u2_conv1x1_bwd_fused_bn(const void* x, const void* dz, const void* y, const 
                             const void* wt, void* dx, float* dw, int M, int C, int x_ld, int N, int dy_ld, int wt_ld, int dx_ld,
                             int n_valid, int c_valid, long long dw_stride_n, int dw_stride_c, int variant, void* stream);
 
+/* The data gradient of a bottleneck's conv1 (1x1, stride 1: u2_conv_igemm with KH = KW = 1, mul = div = 1, no bias) whose input
+ * is the previous block's output (backbone/resnet.py:194-210), with that block's tail reduce in its epilogue: with g1 the value
+ * u2_conv_igemm would have stored, dz = relu_bits * bf16(g1 + dout2) and sums[0][n] += sum dz, sums[1][n] += sum dz (y - mean) invstd
+ * - u2_conv_igemm followed by u2_norm_bwd_reduce(dout = g1, dout2, dz_out, mask_is_bits = 1) in one launch, dz bit for bit and
+ * the sums up to the order of the fp32 additions; g1 is never stored.  in: [B][H][W][in_ld] (C reduction channels), wt: [N][C]
+ * data-gradient layout, dout2 / y / dz: [B * H * W][N] (out_ld == N), bits: [B * H * W][N / 8] as u2_affine_act writes them,
+ * sums: [2][N] fp32 zeroed by the caller.  Served: (C, N) = (64, 256), (128, 512), (256, 1024) on maps the streaming kernel
+ * takes (variant bits 16, 17, 26 as for u2_conv_igemm: 8 work-groups only, lift the size rule, never).  Returns 0 when launched,
+ * 1 when not served - nothing is written, the caller issues the two launches. */
+int u2_conv_dgrad_tail(const void* in, const void* wt, const void* dout2, const void* y, const void* bits, const float* mean,
+                       const float* invstd, void* dz, float* sums, int B, int H, int W, int C, int in_ld, int N, int out_ld,
+                       int variant, void* stream);
+
 /* Test / debugging aid: a code for the kernel (family, tile configuration) the most recent u2_conv_igemm or u2_conv_wgrad
  * call on this thread selected (encoding in csrc/conv_args.h).  With variant 0 the selection can be steered through the
  * environment variables U2_CONV_VARIANT / U2_WGRAD_VARIANT (same bits as the variant argument). */

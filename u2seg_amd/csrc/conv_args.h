@@ -87,6 +87,18 @@ int launch_conv_halo(ConvArgs& a, int N, int C, int variant, hipStream_t s);
 // through an LDS ring; same return convention as launch_conv_tile.  g_last_conv_kernel code: 7xx.
 int launch_conv_stream(ConvArgs& a, int N, int C, int variant, hipStream_t s);
 
+// conv_stream.hip, tail mode: the same launch as the data gradient of a residual block's conv1, with the backward reduce of the
+// previous block's tail in the epilogue.  out = dz = mask * bf16(bf16(conv) + g2), stats[0][n] += sum dz,
+// stats[1][n] += sum dz (y - mean) invstd (u2_norm_bwd_reduce with dout2, dz_out and the bit mask).
+struct TailArgs {
+  const bf16_t* g2 = nullptr;           // the other consumer's gradient, [M][N]
+  const bf16_t* y = nullptr;            // the normalised tensor (conv3 output), [M][N]
+  const unsigned char* bits = nullptr;  // ReLU bits of u2_affine_act, [M][N / 8]
+  const float* mean = nullptr;
+  const float* invstd = nullptr;
+};
+int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, int variant, hipStream_t s);
+
 // wgrad_halo.hip: 3x3 / stride 1 / pad 1 weight gradient, all nine taps per work-group with the input halo in LDS; same
 // return convention as launch_conv_tile.  g_last_conv_kernel code: 2900.
 int launch_wgrad_halo(const bf16_t* x, const bf16_t* dy, float* dw, long long dw_sn, int dw_st, int dw_sc, int n_valid,

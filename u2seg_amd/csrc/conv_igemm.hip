@@ -1472,6 +1472,29 @@ extern "C" int u2_conv_igemm(const void* in, const void* wt, void* out, const fl
   return 0;
 }
 
+extern "C" int u2_conv_dgrad_tail(const void* in, const void* wt, const void* dout2, const void* y, const void* bits,
+                                  const float* mean, const float* invstd, void* dz, float* sums, int B, int H, int W, int C,
+                                  int in_ld, int N, int out_ld, int variant, void* stream) {
+  if (B <= 0 || H <= 0 || W <= 0 || N <= 0 || C <= 0) return 1;
+  ConvArgs a;
+  a.in = (const bf16_t*)in; a.wt = (const bf16_t*)wt; a.out = (bf16_t*)dz; a.bias = nullptr; a.stats = sums;
+  a.zero = zero_page_ptr();
+  if (!a.zero) return -2;
+  a.abl = 0; a.stagger_by_parity = 0; a.sk_ws = nullptr; a.sk_flags = nullptr;
+  a.B = B; a.Hin = H; a.Win = W; a.C = C; a.in_ld = in_ld;
+  a.N = N; a.out_ld = out_ld; a.mul = 1; a.relu = 0; a.accumulate = 0;
+  a.wt_taps = 1; a.ntaps = 1;
+  a.KW = 1; a.pad_h = 0; a.pad_w = 0;
+  a.Hfull = H; a.Wfull = W; a.Hout = H; a.Wout = W; a.M = B * H * W;
+  a.tap_dy[0] = a.tap_dx[0] = a.tap_w[0] = 0; a.tap_pk[0] = 0;
+  a.remap_out = 0; a.out_sy = a.out_sx = 1; a.out_y0 = a.out_x0 = 0;
+  TailArgs t;
+  t.g2 = (const bf16_t*)dout2; t.y = (const bf16_t*)y; t.bits = (const unsigned char*)bits; t.mean = mean; t.invstd = invstd;
+  const int rc = launch_conv_stream_tail(a, t, N, C, env_variant("U2_CONV_VARIANT", variant), (hipStream_t)stream);
+  if (rc == 1) return 0;
+  return rc < 0 ? rc : 1;
+}
+
 extern "C" int u2_conv1x1_bwd_fused(const void* x, const void* dy, const void* wt, void* dx, float* dw, int M, int C, int x_ld,
                                     int N, int dy_ld, int wt_ld, int dx_ld, int n_valid, int c_valid, long long dw_stride_n,
                                     int dw_stride_c, int variant, void* stream) {

@@ -17,6 +17,12 @@
 //     out of order and only make the wait conservative);
 //   * wave tile 64 channels x (16..128) pixels, conv_tile.hip's register-direct epilogue (two 16-byte runs per lane, bias / ReLU,
 //     BN column statistics by a transposing DPP reduction, accumulated per lane over the work-group's life and flushed once).
+//
+// TAIL (the data gradient of a residual block's conv1 whose input is the previous block's output): the epilogue is also the
+// backward reduce of that block's tail (colreduce_kernel<1, 3, true> of norm.hip).  The lane that holds 16 channels of a pixel
+// of the gradient g1 loads the other consumer's gradient g2, the conv3 output y and the pixel's ReLU bits at the same place,
+// stores dz = mask * bf16(bf16(g1) + g2) and accumulates sum dz and sum dz (y - mean) invstd - g1 is never stored, and the
+// reduce pass (3 reads, 1 write of the block output's size) does not run.
 #include <stdlib.h>
 
 #include "common.h"
@@ -54,8 +60,35 @@ template <int CNT, int NF> __device__ __forceinline__ void lds_wait_frags(s16x8 
 // channels, 64 each); NWV: waves per work-group (4: two groups per CU, 8: one); KSS: slabs per ring step - a tile arrives in
 // KS / KSS steps of TM x (64 KSS)-byte rows (KSS < KS keeps five steps of a 256-channel tile in flight in an 80 KB ring where
 // whole tiles would leave room for two: the read-heavy reducing layers 256 -> 64 / 128)
-template <int KS, int TM, int PSW, int NWV, int KSS = KS>
-__global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs a, int ring) {
+// value of lane E of the caller's DPP row (16 lanes), in every lane of the row
+template <int E> __device__ __forceinline__ float row_bcast(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + E, 0xf, 0xf, true));
+}
+
+// lanes 2 e and 2 e + 1 (e a constant after unrolling)
+__device__ __forceinline__ f32x2_t row_bcast_pair(float v, int e) {
+  switch (e) {
+    case 0: return f32x2_t{row_bcast<0>(v), row_bcast<1>(v)};
+    case 1: return f32x2_t{row_bcast<2>(v), row_bcast<3>(v)};
+    case 2: return f32x2_t{row_bcast<4>(v), row_bcast<5>(v)};
+    case 3: return f32x2_t{row_bcast<6>(v), row_bcast<7>(v)};
+    case 4: return f32x2_t{row_bcast<8>(v), row_bcast<9>(v)};
+    case 5: return f32x2_t{row_bcast<10>(v), row_bcast<11>(v)};
+    case 6: return f32x2_t{row_bcast<12>(v), row_bcast<13>(v)};
+    default: return f32x2_t{row_bcast<14>(v), row_bcast<15>(v)};
+  }
+}
+
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
+// what the TAIL epilogue reads beside one output row of a lane: g2 and y under its two 8-channel runs, the row's 64 ReLU bits
+struct TailRow {
+  u32x4_t ga, gb, ya, yb;
+  u32x2_t mk;
+};
+
+template <int KS, int TM, int PSW, int NWV, int KSS = KS, bool TAIL = false>
+__global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs a, int ring, const TailArgs t) {
   constexpr int RB = KSS * 64, CPR = KSS * 4, STAGE = TM * RB;
   constexpr int RPP = 16 / KSS;             // pixel rows per 1 KB LDS-DMA piece
   constexpr int PT = TM * KSS / 16;         // pieces per step
@@ -63,6 +96,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
   constexpr int S = KS / KSS;               // steps per tile
   constexpr int CBW = NWV / PSW, WPX = TM / PSW, NF = WPX / 16;
   static_assert(PT % NWV == 0 && PPW >= 1 && PPW <= 8 && NF >= 1 && (KSS == 1 || KSS == 2 || KSS == 4 || KSS == 8) && KS % KSS == 0 && (S & (S - 1)) == 0, "unsupported configuration");
+  static_assert(!TAIL || (S == 1 && NF % 2 == 0), "the tail epilogue takes whole tiles per step and batches of 1, 2 or 4 rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -98,9 +132,18 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
       wr[ks][i] = v;
     }
   }
+  // TAIL: mean / invstd of ONE channel per lane, the channel whose sums the lane ends up with (st_n below); the epilogue fetches
+  // the 16 channels of a row by DPP broadcast (32 registers otherwise)
+  float t_mu = 0.f, t_is = 0.f;
+  if constexpr (TAIL) {
+    const int tn = n0 + fg * 8 + (fr >> 3) * 32 + (fr & 7);
+    t_mu = t.mean[tn];
+    t_is = t.invstd[tn];
+  }
   // the loads above must have landed before the first LDS-DMA is issued: a later compiler-generated wait for them would
   // otherwise have to drain the ring
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (TAIL) asm volatile("" : "+v"(t_mu), "+v"(t_is));
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
@@ -153,8 +196,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
       asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %2, off offset:16\n\ts_waitcnt vmcnt(0)"
                    : "=&v"(bia[2]), "=&v"(bia[3]) : "v"(a.bias + nb + 32) : "memory");
   }
-  const bool do_stats = a.stats && !(a.abl & 2);
-  typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+  const bool do_stats = TAIL || (a.stats && !(a.abl & 2));
 
   // every memory operation of the epilogue is inline asm (conv_tile.hip: a compiler-visible global access inside the tile loop
   // makes the wait-count pass drain the LDS-DMA queue in front of the next fragment read)
@@ -200,6 +242,103 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
     }
   };
 
+  // ---- TAIL epilogue.  The companions arrive in batches of TR rows (18 registers a row).  Loads return in order, so a wait for a batch also
+  // waits for every LDS-DMA piece issued before it: batch 0 is requested right after the barrier, IN FRONT of the ring step
+  // issued there, and its wait leaves that step in flight; the later batches wait for everything (the step is then older than
+  // the MFMA phase plus a memory round trip).  The addresses of rows beyond M are clamped, so every load is issued and the
+  // counts are exact; such rows get an all-zero mask, which makes their dz and both their terms zero.
+  constexpr bool EARLY = NF <= 4;   // (NF = 8: the fragments and 128 accumulators leave no room beside the MFMA phase)
+  constexpr int TR = NF >= 8 ? 4 : NF >= 4 ? 2 : 1;   // rows per batch (18 registers each)
+  TailRow tr[TR];
+  auto tail_issue = [&](int ti, int b) {
+    const int m0 = (first_tile + ti * nwalk) * TM + psw * WPX;
+#pragma unroll
+    for (int r = 0; r < TR; ++r) {
+      int m = m0 + (TR * b + r) * 16 + fr;
+      m = m < a.M ? m : a.M - 1;
+      // 32-bit byte offsets beside the scalar base pointers (the launcher checks M * N * 2 < 2^32): one address register for
+      // g2, y and dz
+      const unsigned off = ((unsigned)m * (unsigned)a.out_ld + (unsigned)nb) * 2u;
+      const unsigned moff = (unsigned)m * (unsigned)(a.N >> 3) + (unsigned)(n0 >> 3);
+      asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:64"
+                   : "=&v"(tr[r].ga), "=&v"(tr[r].gb) : "v"(off), "s"(t.g2) : "memory");
+      asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:64"
+                   : "=&v"(tr[r].ya), "=&v"(tr[r].yb) : "v"(off), "s"(t.y) : "memory");
+      asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(tr[r].mk) : "v"(moff), "s"(t.bits) : "memory");
+    }
+  };
+  auto tail_epilogue = [&](int ti, bool step_issued) {
+    const int m0 = (first_tile + ti * nwalk) * TM + psw * WPX;
+    f32x2_t s2[8], ss2[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s2[e] = f32x2_t{0.f, 0.f}; ss2[e] = f32x2_t{0.f, 0.f}; }
+    // g1 as the plain epilogue would have stored it, for the whole tile at once: half the accumulators' registers
+    uint32_t g1p[NF][8];
+#pragma unroll
+    for (int j = 0; j < NF; ++j)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        g1p[j][2 * i] = pack_bf16(acc[i][j][0], acc[i][j][1]);
+        g1p[j][2 * i + 1] = pack_bf16(acc[i][j][2], acc[i][j][3]);
+      }
+    // (tied down here: left to the scheduler the conversions sink to their uses and the accumulators stay live)
+#pragma unroll
+    for (int j = 0; j < NF; ++j)
+      asm volatile("" : "+v"(g1p[j][0]), "+v"(g1p[j][1]), "+v"(g1p[j][2]), "+v"(g1p[j][3]), "+v"(g1p[j][4]), "+v"(g1p[j][5]),
+                        "+v"(g1p[j][6]), "+v"(g1p[j][7]));
+#pragma unroll
+    for (int b = 0; b < NF / TR; ++b) {
+      if (b > 0 || !EARLY) tail_issue(ti, b);
+      // (every path ends in an unconditional wait: tools/check_inflight_moves.py follows the control flow, not the flag)
+      if (EARLY && b == 0 && !step_issued) wait_vm<0>();
+      if (EARLY && b == 0) wait_vm<PPW>();
+      else wait_vm<0>();
+#pragma unroll
+      for (int r = 0; r < TR; ++r)
+        asm volatile("" : "+v"(tr[r].ga), "+v"(tr[r].gb), "+v"(tr[r].ya), "+v"(tr[r].yb), "+v"(tr[r].mk)::"memory");
+#pragma unroll
+      for (int r = 0; r < TR; ++r) {
+        const int j = TR * b + r;
+        const int m = m0 + j * 16 + fr;
+        const bool row_ok = m < a.M;
+        // byte fg of the row's first / second 32 channels: the bits of this lane's two runs
+        const uint32_t bitsA = row_ok ? (tr[r].mk[0] >> (fg * 8)) & 0xffu : 0u;
+        const uint32_t bitsB = row_ok ? (tr[r].mk[1] >> (fg * 8)) & 0xffu : 0u;
+        uint32_t pk[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const uint32_t gw = e < 4 ? tr[r].ga[e & 3] : tr[r].gb[e & 3];
+          const uint32_t yw = e < 4 ? tr[r].ya[e & 3] : tr[r].yb[e & 3];
+          const uint32_t bt = ((e < 4 ? bitsA : bitsB) >> (2 * (e & 3))) & 3u;
+          const f32x2_t g1 = {__uint_as_float(g1p[j][e] << 16), __uint_as_float(g1p[j][e] & 0xffff0000u)};
+          const f32x2_t g2 = {__uint_as_float(gw << 16), __uint_as_float(gw & 0xffff0000u)};
+          const f32x2_t sum = g1 + g2;
+          // colreduce_kernel<1, 3, true>: dz = bf16(g1 + g2) where the bit is set, else +0
+          pk[e] = pack_bf16(sum[0], sum[1]) & (((bt & 1u) ? 0xffffu : 0u) | ((bt & 2u) ? 0xffff0000u : 0u));
+          const f32x2_t dz = {__uint_as_float(pk[e] << 16), __uint_as_float(pk[e] & 0xffff0000u)};
+          const f32x2_t yv = {__uint_as_float(yw << 16), __uint_as_float(yw & 0xffff0000u)};
+          const f32x2_t mu = row_bcast_pair(t_mu, e), is = row_bcast_pair(t_is, e);
+          s2[e] += dz;
+          ss2[e] += dz * (yv - mu) * is;   // the reduce's expression and order; contraction is off
+          // one channel pair after the other: the broadcasts of the next pair wait for this pair's sums (formed for a whole row,
+          // or kept across rows, they and the unpacked operands are some hundred registers and the weights get spilled)
+          asm volatile("" : "+v"(s2[e]), "+v"(ss2[e]), "+v"(t_mu), "+v"(t_is));
+        }
+        if (row_ok) {
+          const unsigned off = ((unsigned)m * (unsigned)a.out_ld + (unsigned)nb) * 2u;
+          const u32x4_t va = {pk[0], pk[1], pk[2], pk[3]}, vb = {pk[4], pk[5], pk[6], pk[7]};
+          asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(off), "v"(va), "s"(a.out) : "memory");
+          asm volatile("global_store_dwordx4 %0, %1, %2 offset:64\n\ts_nop 1" ::"v"(off), "v"(vb), "s"(a.out) : "memory");
+        }
+      }
+    }
+    float s[16], ss[16];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s[2 * e] = s2[e][0]; s[2 * e + 1] = s2[e][1]; ss[2 * e] = ss2[e][0]; ss[2 * e + 1] = ss2[e][1]; }
+    st_s += row16_transpose_sum(s, fr);
+    st_ss += row16_transpose_sum(ss, fr);
+  };
+
   // ---- pipeline: ring - 1 steps in flight; step g waits for its own pieces (counted: the pieces of the up to ring - 2 younger
   // steps stay in flight), the barrier publishes the step and frees the slot of step g - 1 for step g + ring - 1
   const int G = my_tiles * S;
@@ -228,7 +367,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (g + ring - 1 < G) {
+    if constexpr (TAIL && EARLY) tail_issue(ti, 0);
+    const bool step_issued = g + ring - 1 < G;
+    if (step_issued) {
       int s2 = slot - 1;
       if (s2 < 0) s2 += ring;
       issue(g + ring - 1, s2);
@@ -269,13 +410,14 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_stream_kernel(const ConvArgs
     }
     slot = slot + 1 == ring ? 0 : slot + 1;
    }
-    if (!(a.abl & 4)) epilogue(ti);
+    if constexpr (TAIL) tail_epilogue(ti, g + ring - 2 < G);   // (g was advanced past the tile's only step)
+    else if (!(a.abl & 4)) epilogue(ti);
   }
   if (do_stats) wg_flush_column_sums<NWV>(a.stats, a.N, st_n, st_s, st_ss, w, lane, smem);
 }
 
-template <int KS, int TM, int PSW, int NWV, int KSS = KS>
-int launch_stream_cfg(ConvArgs& a, int N, int tiny, int forced, int code, hipStream_t s) {
+template <int KS, int TM, int PSW, int NWV, int KSS = KS, bool TAIL = false>
+int launch_stream_cfg(ConvArgs& a, int N, int tiny, int forced, int code, hipStream_t s, const TailArgs& t = TailArgs{}) {
   constexpr int CBW = NWV / PSW;
   constexpr int STAGE = TM * KSS * 64;
   const int per_cu = NWV == 4 ? 2 : 1;
@@ -292,10 +434,10 @@ int launch_stream_cfg(ConvArgs& a, int N, int tiny, int forced, int code, hipStr
   if (!forced && !tiny && (long long)a.tiles_m * a.tiles_n < 6 * G) return 0;
   static PerDeviceOnce attr_set;
   if (auto once_guard = attr_set.first()) {
-    (void)hipFuncSetAttribute((const void*)conv_stream_kernel<KS, TM, PSW, NWV, KSS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)conv_stream_kernel<KS, TM, PSW, NWV, KSS, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   g_last_conv_kernel = code;
-  hipLaunchKernelGGL((conv_stream_kernel<KS, TM, PSW, NWV, KSS>), dim3((unsigned)G), dim3(NWV * 64), (size_t)ring * STAGE, s, a, ring);
+  hipLaunchKernelGGL((conv_stream_kernel<KS, TM, PSW, NWV, KSS, TAIL>), dim3((unsigned)G), dim3(NWV * 64), (size_t)ring * STAGE, s, a, ring, t);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return -1000 - (int)e;
   return 1;
@@ -335,6 +477,30 @@ int launch_conv_stream(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
   if (N > 128) return launch_stream_cfg<1, 128, 1, 4>(a, N, tiny, forced, code, s);
   if (N > 64) return launch_stream_cfg<1, 128, 2, 4>(a, N, tiny, forced, code + 1, s);
   return launch_stream_cfg<1, 128, 4, 4>(a, N, tiny, forced, code + 2, s);
+}
+
+
+// The data gradient of a residual block's conv1 with the previous block's tail reduce in its epilogue (TAIL above): a.out is
+// dz, a.stats the [2][N] sums.  Serves the three launches the res2-res4 bottlenecks make - (C, N) = (64, 256), (128, 512),
+// (256, 1024), dense rows - under launch_conv_stream's variant bits and fill rule; everything else is "not served" (0) and
+// nothing is written.  g_last_conv_kernel code: 705 + C / 32 * 10.
+int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, int variant, hipStream_t s) {
+  if ((variant >> 26) & 1) return 0;
+  if (variant & 0xffff) return 0;
+  const bool forced = (variant >> 17) & 1;
+  if (a.remap_out || a.accumulate || a.relu || a.bias || a.ntaps != 1 || a.wt_taps != 1 || a.pad_h != 0 || a.pad_w != 0 ||
+      a.mul != 1 || a.Hin != a.Hout || a.Win != a.Wout)
+    return 0;
+  if (!((C == 64 && N == 256) || (C == 128 && N == 512) || (C == 256 && N == 1024))) return 0;
+  if (a.out_ld != N || a.in_ld < C || (a.in_ld & 7) || a.M < 1) return 0;
+  if ((unsigned long long)a.M * a.in_ld * 2ull >= 0xffffffffull || (unsigned long long)a.M * N * 2ull >= 0xffffffffull) return 0;
+  if (!a.stats || !a.out || !t.g2 || !t.y || !t.bits || !t.mean || !t.invstd) return 0;
+  const int tiny = (variant >> 16) & 1;
+  const int code = 705 + (C / 32) * 10;
+  a.abl = 0;
+  if (C == 64) return launch_stream_cfg<2, 128, 1, 4, 2, true>(a, N, tiny, forced, code, s, t);
+  if (C == 128) return launch_stream_cfg<4, 64, 1, 4, 4, true>(a, N, tiny, forced, code, s, t);
+  return launch_stream_cfg<8, 64, 2, 8, 8, true>(a, N, tiny, forced, code, s, t);
 }
 
 }  // namespace u2conv

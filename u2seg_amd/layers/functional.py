@@ -363,8 +363,9 @@ class _Conv2dFn(Function):
     (reference: detectron2/layers/wrappers.py:127-134)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, relu, want_stats, param_ref=None, round_bias=True):
+    def forward(ctx, x, weight, bias, stride, pad, relu, want_stats, param_ref=None, round_bias=True, tail=None):
         _check_act(x)
+        ctx.tail = tail   # x is a residual block's output whose tail reduce this layer's data gradient may take over (_TailState)
         # boxed so that autograd does not treat them as inputs: the owning Parameter and its arena gradient slice (looked up by
         # conv2d() - Function.forward runs with autograd disabled, where grad_slot() answers None)
         param = param_ref[0] if param_ref is not None else None
@@ -409,7 +410,7 @@ class _Conv2dFn(Function):
     @staticmethod
     def backward(ctx, dout, _dstats):
         if dout is None:
-            return (None,) * 9
+            return (None,) * 10
         x, weight, out = ctx.saved_tensors
         stride, pad, relu, has_bias = ctx.cfg
         n, cin, kh, kw = weight.shape
@@ -426,7 +427,7 @@ class _Conv2dFn(Function):
             if dst is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _hip.call_status(
                     "u2_conv1x1_bwd_fused_bn", x, lz_dz, lz_y, lz_k[2], lz_k[3], lz_k[4], wd, dx, dst, b * h * w_, cp, cp, npad, npad,
                     npad, cp, n, cin, cin, 1, 0) == 0:
-                return dx, None, None, None, None, None, None, None, None
+                return dx, None, None, None, None, None, None, None, None, None
             dout = torch.empty_like(lz_y)   # not served after all: the apply step as its own launch, then the usual paths
             _hip.call("u2_norm_bwd_apply", lz_dz, None, lz_y, lz_k[2], lz_k[3], lz_k[4], dout, None, 1, b * h * w_, npad, npad, 0,
                       None, None)
@@ -458,6 +459,11 @@ class _Conv2dFn(Function):
                                      cin, 1, 0) == 0
         if fused:
             pass
+        elif ctx.needs_input_grad[0] and _tail_launch(ctx, dz, x, weight, relu, stride, pad):
+            # conv1 of a bottleneck behind an identity block: the data gradient g1 is formed, summed with the residual path's
+            # gradient, masked and reduced in one launch (u2_conv_dgrad_tail); what autograd carries to the previous block's
+            # tail is a placeholder, (dz, sums) wait in the tail's state
+            dx = ctx.tail.placeholder
         elif ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             if ho == 1 and wo == 1 and pad == 0 and h == kh and w_ == kw and kh * kw > 1:
@@ -506,7 +512,30 @@ class _Conv2dFn(Function):
                 sums = zeros_f32((1, 2, npad), x.device)
                 _hip.call("u2_colstats", dz, sums, 1, b * ho * wo, npad, npad)
                 db = sums[0, 0, :n]
-        return dx, dw, db, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None
+
+
+def _tail_launch(ctx, dz, x, weight, relu, stride, pad):
+    """_Conv2dFn.backward: launch the fused data gradient + tail reduce if this layer was marked for it in the forward pass, the
+    other consumer's gradient has been posted and the kernel serves the shape.  False: the caller takes the two launches."""
+    tail = ctx.tail
+    if tail is None or not TAIL_BWD_FUSE or tail.g2 is None or tail.result is not None:
+        return False
+    n, cin, kh, kw = weight.shape
+    b, h, w_, cp = x.shape
+    if relu or kh != 1 or kw != 1 or stride != 1 or pad != 0 or tuple(tail.g2.shape) != tuple(x.shape) \
+            or tuple(tail.y.shape) != tuple(x.shape) or not tail.g2.is_contiguous() or dz.shape[3] != n:
+        return False
+    wd = weight_dgrad_layout(weight, cp, n, ctx.param)
+    dzt = torch.empty_like(tail.y)
+    sums = zeros_f32((2, cp), x.device)
+    if _hip.call_status("u2_conv_dgrad_tail", dz, wd, tail.g2, tail.y, tail.bits, tail.mean, tail.invstd, dzt, sums, b, h, w_, n, n,
+                        cp, cp, ctx.variant) != 0:
+        return False   # declined (shape, fill rule, switched off by the variant bits): nothing was written
+    ph = _lazy_placeholder(x.device, _TAIL_LAZY).expand(x.shape)
+    _TAIL_LAZY[(ph.device.index, ph.data_ptr())] = (ph, tail)
+    tail.result, tail.placeholder = (dzt, sums), ph
+    return True
 
 
 def _conv_bias(bias, round_bias):
@@ -551,8 +580,13 @@ def conv2d(x, weight, bias=None, stride=1, pad=0, relu=False, want_stats=False, 
         param = weight
     slot = grad_slot(param) if param is not None else None
     bslot = grad_slot(bias) if isinstance(bias, torch.nn.Parameter) else None
+    tail = getattr(x, "_u2_tail", None) if TAIL_BWD_FUSE and torch.is_grad_enabled() else None
+    if tail is not None and not (bias is None and not relu and stride == 1 and pad == 0 and tuple(weight.shape[2:]) == (1, 1)
+                                 and (weight.shape[0], x.shape[3]) in _TAIL_SHAPES and weight.shape[1] == x.shape[3]
+                                 and getattr(x, "_u2_twin", None) is not None):
+        tail = None   # (a strided or biased consumer, a width the kernel does not serve, the second handle: two launches)
     out, stats = _Conv2dFn.apply(x, weight, bias, stride, pad, relu, want_stats,
-                                 (param, slot, bslot) if param is not None else None, round_bias)
+                                 (param, slot, bslot) if param is not None else None, round_bias, tail)
     if LAZY_BN_APPLY and want_stats and slot is not None and bias is None and not relu and stride == 1 and pad == 0 \
             and x.requires_grad and tuple(weight.shape[2:]) == (1, 1) and 128 < weight.shape[0] <= 256 and x.shape[3] <= 64 \
             and x.shape[0] * x.shape[1] * x.shape[2] >= FUSED_BWD_MIN_PIXELS:
@@ -654,7 +688,7 @@ class _BatchNormActFn(Function):
 
     @staticmethod
     def forward(ctx, y, stats, gamma, beta, running_mean, running_var, residual, relu, momentum, eps, grad_dst=None,
-                twin=False, sync=True, res_up=False, lazy_ok=False):
+                twin=False, sync=True, res_up=False, lazy_ok=False, tail=None, res_tail=None):
         _check_act(y)
         b, h, w, c = y.shape
         m = b * h * w
@@ -693,6 +727,12 @@ class _BatchNormActFn(Function):
         remask = relu and residual is None
         keep_out = relu and not remask
         ctx.mask_bits = bool(keep_out and bits is not None)
+        # tail: this block's own state, for the next block's conv1 (needs the bit mask); res_tail: the state of the block whose
+        # output is this block's identity shortcut - this tail's backward posts the residual gradient there
+        ctx.tail = tail if (tail is not None and ctx.mask_bits and twin) else None
+        if ctx.tail is not None:
+            tail.y, tail.bits, tail.mean, tail.invstd = y, bits, mean, invstd
+        ctx.res_tail = res_tail
         ctx.save_for_backward(y, (bits if ctx.mask_bits else out) if keep_out else None, gamma, mean, invstd,
                               scale if remask else None, shift if remask else None)
         ctx.cfg = (relu, count, world, residual is not None)
@@ -711,21 +751,27 @@ class _BatchNormActFn(Function):
         relu, count, world, has_res = ctx.cfg
         b, h, w, c = y.shape
         m = b * h * w
-        nret = 15
-        arrived = [g.contiguous() for g in (dout, dout2, dout3) if g is not None]
-        if not arrived:
-            return (None,) * nret
+        nret = 17
         fuse = has_res and relu  # residual block tail: dz is materialised by the reduce pass and is the residual gradient
-        if not fuse and len(arrived) > 1:
-            total = arrived[0]
-            for g in arrived[1:]:
-                total = total + g
-            arrived = [total]
-        dout, dout2, dout3 = (arrived + [None, None])[:3]
-        dz = torch.empty_like(y) if fuse else None
-        sums = zeros_f32((2, c), y.device)
-        _hip.call("u2_norm_bwd_reduce", dout, out, y, mean, invstd, sums, 1, m, c, c, int(relu), msc, msh, dout2, dz, dout3,
-                  int(bool(ctx.mask_bits and fuse)))
+        done = _tail_take(ctx.tail, dout, dout2, dout3, y)
+        if done is not None:
+            dz, sums = done   # the next block's conv1 data gradient has formed them (u2_conv_dgrad_tail)
+        else:
+            arrived = [g.contiguous() for g in (dout, dout2, dout3) if g is not None]
+            if not arrived:
+                return (None,) * nret
+            if not fuse and len(arrived) > 1:
+                total = arrived[0]
+                for g in arrived[1:]:
+                    total = total + g
+                arrived = [total]
+            dout, dout2, dout3 = (arrived + [None, None])[:3]
+            dz = torch.empty_like(y) if fuse else None
+            sums = zeros_f32((2, c), y.device)
+            _hip.call("u2_norm_bwd_reduce", dout, out, y, mean, invstd, sums, 1, m, c, c, int(relu), msc, msh, dout2, dz, dout3,
+                      int(bool(ctx.mask_bits and fuse)))
+        if fuse and ctx.res_tail is not None and TAIL_BWD_FUSE:
+            ctx.res_tail.g2 = dz   # for the conv1 that shares the previous block's output with this block's shortcut
         local = sums
         if world > 1:
             local = sums.clone()
@@ -744,7 +790,7 @@ class _BatchNormActFn(Function):
             if isinstance(ctx.lazy_ok, dict):
                 ctx.lazy_ok["key"] = (ph.device.index, ph.data_ptr())   # what _lazy_guard must see arrive at the conv output
             return ph, None, (None if direct else dgamma), (None if direct else dbeta), None, None, (dz if fuse else None), \
-                None, None, None, None, None, None, None, None
+                None, None, None, None, None, None, None, None, None, None
         dx = torch.empty_like(y)
         # finalize (coefficients of dx, dgamma / dbeta) + apply in one launch (round 4); coef[2:5] is scratch for the channel
         # counts the one-launch form does not serve
@@ -761,7 +807,7 @@ class _BatchNormActFn(Function):
                 _hip.call("u2_fpn_upsample_add_bwd", dout, dres, b, h, w, c)
         if direct:
             dgamma = dbeta = None
-        return dx, None, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None
+        return dx, None, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None, None, None
 
 
 def batch_norm_act(y, stats, gamma, beta, running_mean, running_var, residual=None, relu=False, momentum=0.1,
@@ -779,8 +825,14 @@ def batch_norm_act(y, stats, gamma, beta, running_mean, running_var, residual=No
         # else that makes autograd form a sum, would silently drop the deferred gradient - fail there and then instead
         lazy_ok = {"key": None}
         y.register_hook(functools.partial(_lazy_guard, lazy_ok))
+    # a residual block's tail with exactly two handles: the next block's conv1 may form this tail's (dz, sums) in its data-gradient
+    # launch (_TailState); a tail whose residual is such a block's second handle posts its residual gradient there
+    tail = _TailState() if (TAIL_BWD_FUSE and twin == 1 and relu and residual is not None and not res_up and y.requires_grad) else None
+    res_tail = getattr(residual, "_u2_tail", None) if (residual is not None and not res_up and twin) else None
     out = _BatchNormActFn.apply(y, stats, gamma, beta, running_mean, running_var, residual, relu, momentum, eps, grad_dst,
-                                twin, sync, res_up, lazy_ok)
+                                twin, sync, res_up, lazy_ok, tail, res_tail)
+    if tail is not None and tail.bits is not None:
+        out[0]._u2_tail = out[1]._u2_tail = tail
     if twin == 3:  # a third handle (`._u2_third`) for a third consumer, e.g. the FPN lateral conv on a stage output
         out, other, third = out
         out._u2_twin, out._u2_third = other, third
@@ -1427,6 +1479,58 @@ _LAZY_GRADS = {}   # (device, placeholder address) -> (placeholder, dz, y, coeff
 # (shared state of the tap's backward, level); U2_ROI_SUM_FOLD=0: the tap gathers on the spot and u2_add_n sums afterwards
 ROI_SUM_FOLD = os.environ.get("U2_ROI_SUM_FOLD", "1") != "0"
 _ROI_LAZY = {}
+# The backward reduce of a residual block's tail folded into the next block's conv1 data gradient (u2_conv_dgrad_tail;
+# U2_TAIL_BWD_FUSE=0: two launches).  The lazy placeholders run in the other direction here: the conv hands autograd a placeholder
+# for its input gradient, and the tail's backward, which receives it, finds (dz, sums) in its own state.
+TAIL_BWD_FUSE = os.environ.get("U2_TAIL_BWD_FUSE", "1") != "0"
+_TAIL_SHAPES = ((64, 256), (128, 512), (256, 1024))   # (conv1 output channels, block width) the kernel serves
+_TAIL_LAZY = {}    # (device, placeholder address) -> (placeholder, _TailState)
+
+
+def set_tail_bwd_fuse(on):
+    """Run-time form of U2_TAIL_BWD_FUSE (tests, A/B runs); applies to graphs built afterwards."""
+    global TAIL_BWD_FUSE
+    TAIL_BWD_FUSE = bool(on)
+
+
+class _TailState:
+    """What a residual block's tail (_BatchNormActFn: residual, ReLU, two handles) shares with the two consumers of its output:
+    its saved tensors for the conv1 that may run its reduce; g2, the residual gradient the next tail posts; result, the
+    (dz, sums) that conv1 formed, waiting for this tail's backward together with the placeholder autograd was handed."""
+    __slots__ = ("y", "bits", "mean", "invstd", "g2", "result", "placeholder")
+
+    def __init__(self):
+        self.y = self.bits = self.mean = self.invstd = self.g2 = self.result = self.placeholder = None
+
+
+def _tail_take(tail, dout, dout2, dout3, y):
+    """_BatchNormActFn.backward: (dz, sums) if the next block's conv1 has formed them - then `dout` must be that launch's
+    placeholder and `dout2` the gradient it summed, untouched; None for the two-launch path.  Anything else that involves a
+    placeholder (one that arrives at another layer, in another position or summed with a further gradient; a result whose
+    placeholder never arrives) would drop a gradient silently and raises instead."""
+    grads = (dout, dout2, dout3)
+    hits = [i for i, g in enumerate(grads) if g is not None and (g.device.index, g.data_ptr()) in _TAIL_LAZY] if _TAIL_LAZY else []
+    pending = tail is not None and tail.result is not None
+    if not hits and not pending:
+        if tail is not None:
+            tail.g2 = None
+        return None
+    ent = _TAIL_LAZY.pop((dout.device.index, dout.data_ptr()), None) if hits == [0] else None
+    ok = ent is not None and pending and ent[1] is tail and dout2 is not None and dout3 is None and tail.g2 is not None \
+        and dout2.data_ptr() == tail.g2.data_ptr() and tuple(dout2.shape) == tuple(y.shape) and tuple(dout.shape) == tuple(y.shape)
+    if not ok:
+        n = len(_TAIL_LAZY) + (1 if ent is not None else 0)
+        _TAIL_LAZY.clear()
+        if tail is not None:
+            tail.g2 = tail.result = tail.placeholder = None
+        raise RuntimeError("a residual tail's gradient formed by the next block's conv1 did not arrive as posted (placeholder in "
+                           "positions %s, result pending: %s): a further consumer of the block output, or a changed gradient; "
+                           "%d deferred tail gradients dropped - set U2_TAIL_BWD_FUSE=0 for such graphs" % (hits, pending, n))
+    done = tail.result
+    tail.g2 = tail.result = tail.placeholder = None
+    return done
+
+
 _LAZY_POOL = {}    # device index -> [zero-filled bf16 pool, next slot]: placeholders are ZEROS, so that a sum autograd forms with
                    # one by accident is numerically the other addend (and is then caught by _lazy_guard / the checks below)
 _LAZY_SLOTS = 64
@@ -1441,11 +1545,12 @@ def _lazy_placeholder(device, registry=None):
         slot = ent[0][ent[1] : ent[1] + 1]
         ent[1] = (ent[1] + 1) % _LAZY_SLOTS
         key = (device.index, slot.data_ptr())
-        if key not in _LAZY_GRADS and key not in _ROI_LAZY:
+        if key not in _LAZY_GRADS and key not in _ROI_LAZY and key not in _TAIL_LAZY:
             return slot
-    n = len(_LAZY_GRADS) + len(_ROI_LAZY)
+    n = len(_LAZY_GRADS) + len(_ROI_LAZY) + len(_TAIL_LAZY)
     _LAZY_GRADS.clear()
     _ROI_LAZY.clear()
+    _TAIL_LAZY.clear()
     raise RuntimeError("%d deferred gradients were not consumed by their consumers" % n)
 
 
@@ -1467,10 +1572,11 @@ def reset_deferred_gradients(strict=True):
     one that raised midway leaves entries behind, which must not meet the addresses of the next pass."""
     global _UP2_BWD_LAST
     _UP2_BWD_LAST = None
-    if _LAZY_GRADS or _ROI_LAZY:
-        n = len(_LAZY_GRADS) + len(_ROI_LAZY)
+    if _LAZY_GRADS or _ROI_LAZY or _TAIL_LAZY:
+        n = len(_LAZY_GRADS) + len(_ROI_LAZY) + len(_TAIL_LAZY)
         _LAZY_GRADS.clear()
         _ROI_LAZY.clear()
+        _TAIL_LAZY.clear()
         if strict:
             raise RuntimeError("%d deferred gradients of an earlier backward pass were never consumed" % n)
 
@@ -1479,12 +1585,13 @@ def assert_no_deferred_gradients():
     """After a backward pass: every deferred batch-norm gradient must have been consumed by its convolution."""
     global _UP2_BWD_LAST
     _UP2_BWD_LAST = None   # the shared upsample gradient of the semantic head: nothing of this pass stays referenced
-    if _LAZY_GRADS or _ROI_LAZY:
-        n, m = len(_LAZY_GRADS), len(_ROI_LAZY)
+    if _LAZY_GRADS or _ROI_LAZY or _TAIL_LAZY:
+        n, m, t = len(_LAZY_GRADS), len(_ROI_LAZY), len(_TAIL_LAZY)
         _LAZY_GRADS.clear()
         _ROI_LAZY.clear()
+        _TAIL_LAZY.clear()
         raise RuntimeError("%d deferred batch-norm gradients were not consumed by their convolutions, %d deferred ROIAlign "
-                           "gathers not by their fan-out nodes" % (n, m))
+                           "gathers not by their fan-out nodes, %d residual-tail gradients not by their tails" % (n, m, t))
 ROI_ORDER_MIN = int(os.environ.get("U2_ROI_ORDER_MIN", "1000000000"))
 
 
