@@ -494,6 +494,35 @@ long long u2_mask_polygon_scratch_words(const U2PolyMask* masks, int num_masks);
 int u2_mask_planes_from_polygons(const double* xy, const long long* poly_offs, const U2PolyMask* masks, int num_masks,
                                  void* planes, int* area, void* scratch, long long scratch_words, void* stream);
 
+/* ---- pseudo-panoptic label merge (labelprep.hip): data/pseudo_panoptic.py's merge_image, DESIGN.md section 18 ----------------
+ * A ragged batch of images in a HOST array.  Image i: its n instances in paint order (rank 0 is painted first, rank n - 1
+ * last and on top) as n planes of W * ceil(H / 64) words from word plane_offset of `planes` (the layout above, as
+ * u2_mask_planes_from_counts writes it); its semantic labels, uint8 [H][W], from byte pix_offset of `sem` (0..26 are the 27
+ * classes, any other value belongs to none); the same pix_offset, in elements, places the image in rank, label and ids, and
+ * 3 * pix_offset in rgb.  pix_offset is a multiple of 4; first = instances of the images before it (its entries of
+ * `present`).  H * W < 2^31, n <= 65535.  Integer atomics and plain stores only: no result depends on any order.
+ * u2_label_paint: rank [pixels] = 1 + the highest rank whose plane has the pixel's bit (0: none); present [first + rank] = 1 for
+ *   every rank that won a pixel, 0 otherwise; hist [num_images][U2_LABEL_HIST]: [c] = pixels of class c = label + 1 in 1..27,
+ *   [32 + c] = those of them with rank != 0.  present and hist are cleared by the call.
+ * u2_label_decide (one launch, the images in order): image i's instances are base_i + rank, base_0 = first_id (< 2^32);
+ *   then every class c = 1..27 in order takes the next id iff hist[c] - hist[32 + c] > 0 and not 10 hist[32 + c] > 7 hist[c];
+ *   base_(i+1) = the next free id.  counts [num_images] (device) = n of every image.  decisions [num_images][U2_LABEL_DEC]
+ *   uint32: [l] = id of label l (0 = not claimed), [27] = next free id, [28] = base_i.  Ids are uint32 and must not pass 2^32
+ *   (the caller checks first_id + sum(n + 27)).
+ * u2_label_emit (each output optional): id = base_i + rank - 1 under an instance, else the label's id, else 0;
+ *   rgb [pixels][3] uint8 = id & 255, id >> 8 & 255, id >> 16 & 255 (id2rgb, wrapping at 2^24 like it); label [pixels] uint8 = 0
+ *   under an instance, c for a claimed class c, 255 elsewhere; ids [pixels] uint32 = id.  rank and ids 16-byte, sem, rgb and
+ *   label 4-byte aligned. */
+#define U2_LABEL_CLASSES 27
+#define U2_LABEL_HIST 64
+#define U2_LABEL_DEC 32
+typedef struct U2LabelImage { int first, n, H, W; long long plane_offset, pix_offset; } U2LabelImage;
+int u2_label_paint(const void* planes, const void* sem, int* rank, int* present, int* hist, const U2LabelImage* images,
+                   int num_images, void* stream);
+int u2_label_decide(const int* hist, const int* counts, void* decisions, long long first_id, int num_images, void* stream);
+int u2_label_emit(const int* rank, const void* sem, const void* decisions, void* rgb, void* label, void* ids,
+                  const U2LabelImage* images, int num_images, void* stream);
+
 /* ---- panoptic quality (panopticeval.hip): evaluation/panoptic_ops.py, DESIGN.md section 12 ------------------------------------
  * The joint histogram PQ is computed from: for every image of the HOST array, counts[(G + 2)][P] = pixels shared by a
  * ground-truth row and a predicted id.  pred: the [H][W] int32 id map u2_panoptic_merge writes (0 = void), P = its largest
