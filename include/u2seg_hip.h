@@ -762,6 +762,36 @@ int u2_vit_attention(const void* qkv, void* out, int B, int T, int heads, int he
 /* nn.GELU() (exact erf form, dino.py:77-93) in place on n bf16 elements (n % 8 == 0, 16-byte aligned). */
 int u2_vit_gelu(void* x, long long n, void* stream);
 
+/* ---- test-time augmentation for instance inference (tta.hip): detectron2/modeling/test_time_augmentation.py:244-307 ---------
+ * The box maps between a view (resized, possibly flipped) and the original image, and the mean of the views' mask
+ * probabilities, for the views of ALL images of a call in one launch each (modeling/test_time_augmentation.py, DESIGN.md
+ * section 19).  The arithmetic is the reference's numpy float32 arithmetic, one rounding per step.
+ *
+ * A view v is described by view_desc[v] = (s1x, s1y, s2x, s2y, width) (float32), view_flip[v] (0 / 1) and view_image[v] (the
+ * image it belongs to).  Every array is device memory; boxes are [.][4] float32 (x0, y0, x1, y1), 16-byte aligned.
+ * Status: 0 ok, -1 a bad argument (nothing launched).  Zero rows, zero views of an image and views without rows are valid.
+ *
+ * View -> original (TransformList.inverse().apply_box): if flip, (x0, x1) = minmax(width - x0, width - x1); then x * s1x * s2x and
+ * y * s1y * s2y (two multiplications; 1.0f where a step is absent); after every step the box is the min / max of its mapped
+ * corners as numpy takes them (a NaN in x0 or x1 makes both NaN).  row_view[i]: the view of row i.  out_cand[i] (uint8) = all
+ * four mapped coordinates finite and scores[i] finite and scores[i] > score_thresh; out_boxes[i] = the mapped box clipped to
+ * [0, image_clip[image][0]] x [0, image_clip[image][1]] (width, height) like Boxes.clip (a NaN stays a NaN). */
+int u2_tta_boxes_to_original(const float* boxes, const float* scores, const int* row_view, const float* view_desc,
+                             const int* view_flip, const int* view_image, const float* image_clip, float* out_boxes,
+                             void* out_cand, int num_rows, int num_views, int num_images, float score_thresh, void* stream);
+/* Original -> view (TransformList.apply_box): x * s1x * s2x, y * s1y * s2y, then the flip; not clipped.  The boxes of image i
+ * are rows image_rows[i] .. image_rows[i + 1] (int32 [num_images + 1]); view v writes them to rows view_out_row[v] .. of out.
+ * max_rows: the largest row count of an image. */
+int u2_tta_boxes_to_views(const float* boxes, const int* image_rows, const float* view_desc, const int* view_flip,
+                          const int* view_image, const long long* view_out_row, float* out, int max_rows, int num_views,
+                          int num_images, void* stream);
+/* out[image_rows[i] + r][0][y][x] = (sum over the views v = image_views[i] .. image_views[i + 1] - 1, in this order, of
+ * view_prob[v][r][0][y][view_flip[v] ? P - 1 - x : x]) / float(number of views): sequential float32 additions, one division.
+ * view_prob: device array of num_views pointers to float32 [rows of the image][1][P][P].  max_rows as above; min_views: the
+ * smallest view count of an image (>= 1). */
+int u2_tta_reduce_masks(const void* view_prob, const int* view_flip, const int* image_views, const int* image_rows, float* out,
+                        int max_rows, int min_views, int num_images, int P, void* stream);
+
 /* library self-description */
 int u2_abi_version(void);
 

@@ -79,12 +79,13 @@ def precise_bn_batches(cfg, device, per_gpu, rank, world):
 
 
 def evaluate_on_disk_datasets(cfg, model, eval_mode, device, tasks=("bbox",), panoptic_pq="files", gt_polygons="refuse",
-                              coco_eval="host", sem_seg_boundary_iou=False):
+                              coco_eval="host", sem_seg_boundary_iou=False, output_folder=None, instances_only=False):
     """The reference's Trainer.test (engine/defaults.py:591-640) for the DATASETS.TEST entries that are on disk: first run
     with --eval-mode hungarian_matching (writes ./hungarian_matching/*.json), then with --eval-mode eval.  None when no
-    test dataset is available."""
+    test dataset is available.  output_folder: where the evaluators write (default OUTPUT_DIR/inference); instances_only: the
+    instance evaluator alone, for a model that returns nothing but "instances" (test-time augmentation)."""
     from u2seg_amd.data import build_detection_test_loader
-    from u2seg_amd.evaluation import build_evaluator, inference_on_dataset
+    from u2seg_amd.evaluation import COCOEvaluator, build_evaluator, inference_on_dataset
 
     register_all_coco()
     results = {}
@@ -94,11 +95,34 @@ def evaluate_on_disk_datasets(cfg, model, eval_mode, device, tasks=("bbox",), pa
             continue
         loader = build_detection_test_loader(cfg, name)
         stream = DevicePrefetcher(loader, device) if str(device).startswith("cuda") else loader
-        results[name] = inference_on_dataset(model, stream, build_evaluator(cfg, name, eval_mode=eval_mode, tasks=tasks,
-                                                                                  panoptic_pq=panoptic_pq, gt_polygons=gt_polygons,
-                                                                                  coco_eval=coco_eval,
-                                                                                  sem_seg_boundary_iou=sem_seg_boundary_iou))
+        if instances_only:
+            if meta.evaluator_type not in ("coco", "coco_panoptic_seg"):
+                continue
+            evaluator = COCOEvaluator(name, output_dir=output_folder or os.path.join(cfg.OUTPUT_DIR, "inference"), mode=eval_mode,
+                                      tasks=tasks, gt_polygons=gt_polygons, coco_eval=coco_eval)
+        else:
+            evaluator = build_evaluator(cfg, name, output_folder=output_folder, eval_mode=eval_mode, tasks=tasks,
+                                        panoptic_pq=panoptic_pq, gt_polygons=gt_polygons, coco_eval=coco_eval,
+                                        sem_seg_boundary_iou=sem_seg_boundary_iou)
+        results[name] = inference_on_dataset(model, stream, evaluator)
     return results or None
+
+
+def evaluate_with_tta(cfg, model, eval_mode, device, tasks=("bbox",), gt_polygons="refuse", coco_eval="host"):
+    """The reference's Trainer.test_with_TTA (tools/train_net.py:96-109): the instance tasks once more with the model wrapped in
+    GeneralizedRCNNWithTTA, written under OUTPUT_DIR/inference_TTA, every result key with the suffix _TTA.  The wrapper returns
+    instances only, so of `tasks` the instance tasks (bbox, segm) are scored; None when there is none or no dataset on disk."""
+    from u2seg_amd.modeling import GeneralizedRCNNWithTTA
+
+    tasks = tuple(t for t in tasks if t in ("bbox", "segm"))
+    if not tasks:
+        return None
+    wrapped = GeneralizedRCNNWithTTA(cfg, model, impl="device" if str(device).startswith("cuda") else "host")
+    results = evaluate_on_disk_datasets(cfg, wrapped, eval_mode, device, tasks, gt_polygons=gt_polygons, coco_eval=coco_eval,
+                                        output_folder=os.path.join(cfg.OUTPUT_DIR, "inference_TTA"), instances_only=True)
+    if results is None:
+        return None
+    return {name: {k + "_TTA": v for k, v in res.items()} for name, res in results.items()}
 
 
 def main(args):
@@ -124,6 +148,12 @@ def main(args):
         results = evaluate_on_disk_datasets(cfg, model, args.eval_mode, c.MODEL.DEVICE, tasks, args.panoptic_pq,
                                             args.eval_gt_polygons, args.coco_eval, args.sem_seg_boundary_iou)
         if results is not None:
+            # tools/train_net.py:134-135 of the reference.  Only the scoring pass: the hungarian_matching pass writes the cluster
+            # mapping from the plain model's detections, and a second, augmented run of it would overwrite that file
+            if cfg.TEST.AUG.ENABLED and args.eval_mode == "eval":
+                with_tta = evaluate_with_tta(cfg, model, args.eval_mode, c.MODEL.DEVICE, tasks, args.eval_gt_polygons, args.coco_eval)
+                for name, res in (with_tta or {}).items():
+                    results[name].update(res)
             if rank == 0:
                 print(results)
             return results

@@ -100,11 +100,24 @@ class GeneralizedRCNN(nn.Module):
         losses.update(proposal_losses)
         return losses
 
-    def inference(self, batched_inputs, do_postprocess=True):
+    def _detect_from_features(self, features, image_sizes, detected_instances=None):
+        """The heads behind the backbone (rcnn.py:200-211): RPN + ROI heads, or - given instances with pred_boxes and
+        pred_classes - only the heads that work on given boxes (the mask head)."""
+        if detected_instances is None:
+            proposals, _ = self.proposal_generator(image_sizes, features, None)
+            results, _ = self.roi_heads(None, features, proposals, None)
+            return results
+        detected_instances = [x.to(self.device) for x in detected_instances]
+        return self.roi_heads.forward_with_given_boxes(features, detected_instances)
+
+    def inference(self, batched_inputs, detected_instances=None, do_postprocess=True):
+        """rcnn.py:178-221.  detected_instances: list[Instances] or None; given, the boxes are taken as known and only the
+        other per-ROI outputs are computed."""
         assert not self.training
+        if isinstance(detected_instances, bool):
+            raise TypeError("inference(batched_inputs, detected_instances=None, do_postprocess=True): pass do_postprocess by keyword")
         features, image_sizes, _ = self._backbone_features(batched_inputs)
-        proposals, _ = self.proposal_generator(image_sizes, features, None)
-        results, _ = self.roi_heads(None, features, proposals, None)
+        results = self._detect_from_features(features, image_sizes, detected_instances)
         if not do_postprocess:
             return results
         out_sizes = [(inp.get("height", size[0]), inp.get("width", size[1])) for inp, size in zip(batched_inputs, image_sizes)]
