@@ -113,6 +113,12 @@ int u2_weight_layout_batched(const float* base, const U2LayoutDesc* table, int n
 /* ---- normalisation / activation (norm.hip) ----------------------------------------------------
  * Replaces nn.SyncBatchNorm / nn.GroupNorm / relu_ chosen by detectron2/layers/batch_norm.py:169-197. */
 int u2_colstats(const void* x, float* out /*[slots][2][C]*/, int slots, int rows_per_slot, int C, int ld, void* stream);
+/* u2_colstats with the additions in a fixed order (no atomics): the same call on the same input gives the same bits from run to
+ * run, which u2_colstats does not.  part: scratch float32 [slots][nchunk][2][C], written in full; out [slots][2][C] is written,
+ * not added to.  Pass 1 sums rows_per_slot / nchunk (rounded up) rows per work-group, pass 2 the chunks in order.  C % 8 == 0,
+ * 8 <= C <= 2048, ld % 8 == 0, x 16-byte aligned, 1 <= nchunk <= 65535; -1 otherwise (nothing launched). */
+int u2_colstats_ordered(const void* x, float* part, float* out, int slots, int rows_per_slot, int C, int ld, int nchunk,
+                        void* stream);
 /* dst[c] += sum over rows of x[row][c] for c < n_valid (x: [rows][ld] bf16, C physical channels): the bias gradient of a conv /
  * linear layer (autograd's sum over the output gradient behind layers/wrappers.py:127-134) accumulated straight into the
  * parameter's fp32 gradient storage - no temporary, no AccumulateGrad add. */
@@ -791,6 +797,21 @@ int u2_tta_boxes_to_views(const float* boxes, const int* image_rows, const float
  * smallest view count of an image (>= 1). */
 int u2_tta_reduce_masks(const void* view_prob, const int* view_flip, const int* image_views, const int* image_rows, float* out,
                         int max_rows, int min_views, int num_images, int P, void* stream);
+/* The mean of the views' semantic logits of ONE image, n views per call:
+ *   acc[c][y][x] = (sum over the views v of all calls, in order, of term_v[c][y][flip_v ? W - 1 - x : x]) / float(divisor)
+ * with term_v = sem_seg_postprocess(view v's [C][h_v][w_v] window, (h_v, w_v), H, W): u2_bilinear_resize_f32's value in its
+ * arithmetic, or the source element itself when (h_v, w_v) == (H, W), so that a NaN or an Inf passes through as it does there.
+ * Sequential float32 additions in view order, one division: the views of an image split over calls in any grouping that
+ * keeps their order give the same bits as one call.
+ *   view_logits  DEVICE array of n pointers to float32 logits (the window's element [0][0][0]; x stride 1)
+ *   views        HOST array [n][5]: h, w, row stride, channel stride (in elements), flip (0 / 1)
+ *   acc          float32 [C][H][W], in / out; first != 0: the sum starts from the first view's term, acc is not read
+ *   divisor      > 0: this is the last call, every element is divided by float(divisor) after the additions; 0: not yet
+ *   argmax       optional int64 [H][W], written on the last call only: the first maximum over c, a NaN counting as the largest
+ * Status: 0 ok; -1 (nothing launched) for C < 1, C > 64, n < 1, H or W < 1, a window side < 1, a row stride below the window's
+ * width, a negative channel stride or divisor, a null view_logits, views or acc. */
+int u2_tta_accumulate_sem_seg(const void* view_logits, const long long* views, int n, float* acc, int first, int divisor,
+                              long long* argmax, int C, int H, int W, void* stream);
 
 /* library self-description */
 int u2_abi_version(void);

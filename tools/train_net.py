@@ -108,16 +108,27 @@ def evaluate_on_disk_datasets(cfg, model, eval_mode, device, tasks=("bbox",), pa
     return results or None
 
 
-def evaluate_with_tta(cfg, model, eval_mode, device, tasks=("bbox",), gt_polygons="refuse", coco_eval="host"):
+def evaluate_with_tta(cfg, model, eval_mode, device, tasks=("bbox",), gt_polygons="refuse", coco_eval="host", outputs="instances",
+                      panoptic_pq="files", sem_seg_boundary_iou=False):
     """The reference's Trainer.test_with_TTA (tools/train_net.py:96-109): the instance tasks once more with the model wrapped in
     GeneralizedRCNNWithTTA, written under OUTPUT_DIR/inference_TTA, every result key with the suffix _TTA.  The wrapper returns
-    instances only, so of `tasks` the instance tasks (bbox, segm) are scored; None when there is none or no dataset on disk."""
-    from u2seg_amd.modeling import GeneralizedRCNNWithTTA
+    instances only, so of `tasks` the instance tasks (bbox, segm) are scored; None when there is none or no dataset on disk.
+    outputs="panoptic" (--tta-outputs) on a PanopticFPN: the model wrapped in PanopticFPNWithTTA, which returns the semantic and
+    panoptic outputs as well, in front of every evaluator build_evaluator gives the dataset."""
+    from u2seg_amd.modeling import GeneralizedRCNNWithTTA, PanopticFPN, PanopticFPNWithTTA
 
+    impl = "device" if str(device).startswith("cuda") else "host"
+    if outputs == "panoptic" and isinstance(model, PanopticFPN):
+        wrapped = PanopticFPNWithTTA(cfg, model, impl=impl)
+        results = evaluate_on_disk_datasets(cfg, wrapped, eval_mode, device, tasks, panoptic_pq, gt_polygons, coco_eval,
+                                            sem_seg_boundary_iou, output_folder=os.path.join(cfg.OUTPUT_DIR, "inference_TTA"))
+        if results is None:
+            return None
+        return {name: {k + "_TTA": v for k, v in res.items()} for name, res in results.items()}
     tasks = tuple(t for t in tasks if t in ("bbox", "segm"))
     if not tasks:
         return None
-    wrapped = GeneralizedRCNNWithTTA(cfg, model, impl="device" if str(device).startswith("cuda") else "host")
+    wrapped = GeneralizedRCNNWithTTA(cfg, model, impl=impl)
     results = evaluate_on_disk_datasets(cfg, wrapped, eval_mode, device, tasks, gt_polygons=gt_polygons, coco_eval=coco_eval,
                                         output_folder=os.path.join(cfg.OUTPUT_DIR, "inference_TTA"), instances_only=True)
     if results is None:
@@ -151,7 +162,8 @@ def main(args):
             # tools/train_net.py:134-135 of the reference.  Only the scoring pass: the hungarian_matching pass writes the cluster
             # mapping from the plain model's detections, and a second, augmented run of it would overwrite that file
             if cfg.TEST.AUG.ENABLED and args.eval_mode == "eval":
-                with_tta = evaluate_with_tta(cfg, model, args.eval_mode, c.MODEL.DEVICE, tasks, args.eval_gt_polygons, args.coco_eval)
+                with_tta = evaluate_with_tta(cfg, model, args.eval_mode, c.MODEL.DEVICE, tasks, args.eval_gt_polygons, args.coco_eval,
+                                             args.tta_outputs, args.panoptic_pq, args.sem_seg_boundary_iou)
                 for name, res in (with_tta or {}).items():
                     results[name].update(res)
             if rank == 0:

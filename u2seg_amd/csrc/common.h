@@ -182,6 +182,28 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + idx;
 }
 
+// F.interpolate(mode = "bilinear", align_corners = False) in fp32 as ATen computes it, shared by every kernel that has to give the
+// bits of u2_bilinear_resize_f32 (postprocess.hip, tta.hip; the build has -ffp-contract=off).  One axis: output index o of an
+// n_in-long source with scale = (float)n_in / (float)n_out -> source index max(scale * (o + 0.5) - 0.5, 0), its two taps
+// (i1 == i0 at the far edge) and their weights h (of i0) and l (of i1).
+struct BilinearTap {
+  int i0, i1;
+  float h, l;
+};
+__device__ __forceinline__ BilinearTap bilinear_tap(float scale, int o, int n_in) {
+  const float s = fmaxf(scale * ((float)o + 0.5f) - 0.5f, 0.f);
+  BilinearTap t;
+  t.i0 = min((int)s, n_in - 1);
+  t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
+  t.l = s - (float)t.i0;
+  t.h = 1.f - t.l;
+  return t;
+}
+// the value from the four taps: rows y.i0 (v00, v01) and y.i1 (v10, v11), columns x.i0 and x.i1
+__device__ __forceinline__ float bilinear_mix(const BilinearTap& y, const BilinearTap& x, float v00, float v01, float v10, float v11) {
+  return y.h * (x.h * v00 + x.l * v01) + y.l * (x.h * v10 + x.l * v11);
+}
+
 #define U2_CHECK_LAUNCH() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
 
 // Zero-fill of a few words as an ordinary kernel of the stream.  hipMemsetAsync is not used for scratch that the next kernels

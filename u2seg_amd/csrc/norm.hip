@@ -841,6 +841,104 @@ extern "C" int u2_colstats(const void* x, float* out, int slots, int rows_per_sl
   return 0;
 }
 
+// ---- u2_colstats in a fixed order -----------------------------------------------------------------------------------------------
+// The same sums without atomics, for the passes whose results have to come out the same from run to run (GroupNorm when no
+// gradient is recorded: the semantic head at inference).  Pass 1: work-group (chunk, slot) sums its rows - a thread owns 8
+// channels and every rows_par-th row, the rows_par partial sums of a channel are added in thread order - into
+// part[slot][chunk][2][C]; pass 2 adds the chunks of a (slot, channel) in eight runs of consecutive chunks and the runs in order.  Who adds what, and in which order, is a
+// function of the shape alone.
+namespace {
+__global__ __launch_bounds__(256) void colstats_ordered_kernel(const bf16_t* __restrict__ x, float* __restrict__ part, int rows_per_slot,
+                                                               int C, int ld, int rpb) {
+  __shared__ float red[2][256 * 8];
+  const int ncol = C >> 3;               // <= 256
+  const int rows_par = 256 / ncol;       // >= 1
+  const int tid = threadIdx.x, chunk = tid % ncol, rl = tid / ncol;
+  const int slot = blockIdx.y;
+  const size_t row0 = (size_t)slot * rows_per_slot;
+  const int r_begin = blockIdx.x * rpb, r_end = min(r_begin + rpb, rows_per_slot);
+  float s0[8], s1[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s0[e] = s1[e] = 0.f;
+  if (rl < rows_par) {
+    constexpr int U = 4;  // rows in flight per thread; added in row order
+    for (int r = r_begin + rl; r < r_end; r += rows_par * U) {
+      uint4 q[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int ru = r + u * rows_par;
+        q[u] = ru < r_end ? *reinterpret_cast<const uint4*>(x + (row0 + ru) * ld + chunk * 8) : make_uint4(0u, 0u, 0u, 0u);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bf16_t* v = reinterpret_cast<const bf16_t*>(&q[u]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float f = bf2f(v[e]);  // a row behind the end adds +0, which changes no sum
+          s0[e] += f;
+          s1[e] += f * f;
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      red[0][rl * C + chunk * 8 + e] = s0[e];
+      red[1][rl * C + chunk * 8 + e] = s1[e];
+    }
+  }
+  __syncthreads();
+  float* dst = part + ((size_t)slot * gridDim.x + blockIdx.x) * 2 * C;
+  for (int j = tid; j < 2 * C; j += 256) {
+    const int k = j / C, c = j - k * C;
+    float t = 0.f;
+    for (int q = 0; q < rows_par; ++q) t += red[k][q * C + c];
+    dst[j] = t;
+  }
+}
+
+// work-group (32 entries of a slot's 2 C, slot): 8 threads per entry sum an eighth of the chunks each, in chunk order, and the
+// eight partial sums are added in order
+__global__ __launch_bounds__(256) void colstats_ordered_finish_kernel(const float* __restrict__ part, float* __restrict__ out, int C,
+                                                                      int nchunk) {
+  __shared__ float red[8][32];
+  const int slot = blockIdx.y;
+  const int col = threadIdx.x & 31, lane = threadIdx.x >> 5;
+  const int j = blockIdx.x * 32 + col;
+  const int per = (nchunk + 7) >> 3;
+  const int q0 = lane * per, q1 = min(q0 + per, nchunk);
+  float t = 0.f;
+  if (j < 2 * C) {
+    const float* src = part + (size_t)slot * nchunk * 2 * C + j;
+#pragma unroll 8
+    for (int q = q0; q < q1; ++q) t += src[(size_t)q * 2 * C];
+  }
+  red[lane][col] = t;
+  __syncthreads();
+  if (lane == 0 && j < 2 * C) {
+    float total = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) total += red[k][col];
+    out[(size_t)slot * 2 * C + j] = total;
+  }
+}
+
+}  // namespace
+
+extern "C" int u2_colstats_ordered(const void* x, float* part, float* out, int slots, int rows_per_slot, int C, int ld, int nchunk,
+                                   void* stream) {
+  if ((C & 7) || (ld & 7) || C < 8 || C > 2048 || ld < C || nchunk < 1 || nchunk > 65535 || slots > 65535) return -1;
+  if (slots <= 0 || rows_per_slot <= 0) return 0;
+  if (!x || !part || !out || ((uintptr_t)x & 15)) return -1;
+  const int rpb = (rows_per_slot + nchunk - 1) / nchunk;  // chunks behind the last row sum nothing and write zeros
+  hipLaunchKernelGGL(colstats_ordered_kernel, dim3(nchunk, slots), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, part,
+                     rows_per_slot, C, ld, rpb);
+  U2_CHECK_LAUNCH();
+  hipLaunchKernelGGL(colstats_ordered_finish_kernel, dim3((2 * C + 31) / 32, slots), dim3(256), 0, (hipStream_t)stream, part, out,
+                     C, nchunk);
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int u2_colsum_add(const void* x, float* dst, int rows, int C, int ld, int n_valid, void* stream) {
   if ((C & 7) || (ld & 7) || n_valid < 1 || n_valid > C) return -1;
   if (rows <= 0) return 0;

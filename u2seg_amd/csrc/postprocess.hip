@@ -448,15 +448,11 @@ __global__ __launch_bounds__(256) void bilinear_resize_f32_kernel(const float* _
     const int ox = (int)(i % Wo);
     const size_t t = i / Wo;
     const int oy = (int)(t % Ho), c = (int)(t / Ho);
-    const float sy = fmaxf(sch * ((float)oy + 0.5f) - 0.5f, 0.f), sx = fmaxf(scw * ((float)ox + 0.5f) - 0.5f, 0.f);
-    const int y0 = min((int)sy, Hin - 1), x0 = min((int)sx, Win - 1);
-    const int y1 = y0 + (y0 < Hin - 1 ? 1 : 0), x1 = x0 + (x0 < Win - 1 ? 1 : 0);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    const float hy = 1.f - ly, hx = 1.f - lx;
+    const BilinearTap y = bilinear_tap(sch, oy, Hin), x = bilinear_tap(scw, ox, Win);  // common.h: shared with tta.hip
     const float* base = in + (size_t)c * in_cs;
-    const float v00 = base[(size_t)y0 * in_rs + x0], v01 = base[(size_t)y0 * in_rs + x1];
-    const float v10 = base[(size_t)y1 * in_rs + x0], v11 = base[(size_t)y1 * in_rs + x1];
-    out[i] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+    const float v00 = base[(size_t)y.i0 * in_rs + x.i0], v01 = base[(size_t)y.i0 * in_rs + x.i1];
+    const float v10 = base[(size_t)y.i1 * in_rs + x.i0], v11 = base[(size_t)y.i1 * in_rs + x.i1];
+    out[i] = bilinear_mix(y, x, v00, v01, v10, v11);
   }
 }
 

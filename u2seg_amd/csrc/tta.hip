@@ -1,7 +1,7 @@
-// Test-time augmentation for instance inference (gfx950): the box maps between a view and the original image, and the mean of
-// the views' mask probabilities.  Contract: include/u2seg_hip.h, design: DESIGN.md section 19.
+// Test-time augmentation (gfx950): the box maps between a view and the original image, the mean of the views' mask
+// probabilities, and the mean of the views' semantic logits.  Contract: include/u2seg_hip.h, design: DESIGN.md sections 19, 20.
 //
-// Three element-wise kernels, one thread per box or per output pixel.  Their arithmetic restates what the reference does with
+// Element-wise kernels, one thread per box or per output pixel.  Their arithmetic restates what the reference does with
 // numpy on float32 arrays (modeling/test_time_augmentation.py:244-307 through fvcore's apply_box): every step is one float32
 // operation with one rounding - the build has -ffp-contract=off, nothing below may fuse - so that the host definition in
 // modeling/test_time_augmentation.py and these kernels agree bit for bit.
@@ -97,6 +97,78 @@ __global__ __launch_bounds__(TT_THREADS) void tta_reduce_masks_kernel(
   out[(long long)first * pp + e] = acc / (float)(v1 - v0);
 }
 
+// ---- the mean of the views' semantic logits ---------------------------------------------------------------
+// acc[c][oy][ox] (+)= sem_seg_postprocess(view)[c][oy][flip ? W - 1 - ox : ox] for the views of a call in order, the running sum
+// of a pixel's C classes in registers; with divisor > 0 the sum is divided and its argmax written.  The term is
+// bilinear_resize_f32_kernel's value (bilinear_tap / bilinear_mix of common.h), or the source element itself where the window
+// is H x W already (sem_seg_postprocess returns its input there: 0 * inf would make a NaN of a neighbouring inf).
+constexpr int TT_MAXVIEWS = 32;  // views per launch (kernel arguments); the launcher splits longer lists, which changes no bit
+
+struct SemView {
+  long long cs, rs;  // channel and row stride of the [C][h][w] window, in elements
+  float sch, scw;    // (float)h / (float)H, (float)w / (float)W
+  int h, w, flip, identity;
+};
+struct SemViews {
+  SemView v[TT_MAXVIEWS];
+};
+
+// grid: pixel blocks; a thread owns one output pixel (neighbouring threads neighbouring x), computes the taps and weights once
+// per view and loops over the classes
+template <int CMAX>
+__global__ __launch_bounds__(TT_THREADS) void tta_accumulate_sem_seg_kernel(const float* const* __restrict__ view_logits,
+                                                                            const SemViews views, int n, float* __restrict__ acc_mem,
+                                                                            long long* __restrict__ amax, int C, int H, int W,
+                                                                            int first, float divisor) {
+  const long long hw = (long long)H * W;
+  const long long i = (long long)blockIdx.x * TT_THREADS + threadIdx.x;
+  if (i >= hw) return;
+  const int ox = (int)(i % W), oy = (int)(i / W);
+  float acc[CMAX];
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) acc[c] = (!first && c < C) ? acc_mem[c * hw + i] : 0.f;
+  for (int v = 0; v < n; ++v) {
+    const SemView d = views.v[v];
+    const float* __restrict__ src = view_logits[v];
+    const int sx = d.flip ? W - 1 - ox : ox;
+    const bool start = first && v == 0;  // the sum starts from the first term: nothing is added to it
+    if (d.identity) {
+      const float* p = src + oy * d.rs + sx;
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c)
+        if (c < C) {
+          const float t = p[c * d.cs];
+          acc[c] = start ? t : acc[c] + t;
+        }
+    } else {
+      const BilinearTap y = bilinear_tap(d.sch, oy, d.h), x = bilinear_tap(d.scw, sx, d.w);
+      const float* p00 = src + y.i0 * d.rs + x.i0;
+      const float* p01 = src + y.i0 * d.rs + x.i1;
+      const float* p10 = src + y.i1 * d.rs + x.i0;
+      const float* p11 = src + y.i1 * d.rs + x.i1;
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c)
+        if (c < C) {
+          const long long o = c * d.cs;
+          const float t = bilinear_mix(y, x, p00[o], p01[o], p10[o], p11[o]);
+          acc[c] = start ? t : acc[c] + t;
+        }
+    }
+  }
+  float best = 0.f;
+  int besti = 0;
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c)
+    if (c < C) {
+      float f = acc[c];
+      if (divisor > 0.f) f = f / divisor;
+      acc_mem[c * hw + i] = f;
+      // torch.argmax / numpy.argmax: the first maximum, a NaN counts as the largest value
+      if (c == 0 || f > best || (f != f && best == best)) { best = f; besti = c; }
+    }
+  if (amax && divisor > 0.f) amax[i] = besti;
+}
+
 unsigned blocks_of(long long items) { return (unsigned)((items + TT_THREADS - 1) / TT_THREADS); }
 
 }  // namespace
@@ -142,5 +214,43 @@ extern "C" int u2_tta_reduce_masks(const void* view_prob, const int* view_flip, 
   hipLaunchKernelGGL(tta_reduce_masks_kernel, dim3(blocks_of(items), (unsigned)num_images), dim3(TT_THREADS), 0,
                      (hipStream_t)stream, (const float* const*)view_prob, view_flip, image_views, image_rows, out, P);
   U2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int u2_tta_accumulate_sem_seg(const void* view_logits, const long long* views, int n, float* acc, int first, int divisor,
+                                         long long* argmax, int C, int H, int W, void* stream) {
+  if (C < 1 || C > 64 || n < 1 || H < 1 || W < 1 || divisor < 0 || !view_logits || !views || !acc) return -1;
+  const long long hw = (long long)H * W;
+  if (hw >= (1LL << 31) * TT_THREADS) return -1;
+  for (int v = 0; v < n; ++v) {
+    const long long* d = views + 5 * (size_t)v;  // h, w, row stride, channel stride, flip
+    if (d[0] < 1 || d[1] < 1 || d[0] > 0x7fffffffLL || d[1] > 0x7fffffffLL || d[2] < d[1] || d[3] < 0) return -1;
+  }
+  const float* const* ptrs = (const float* const*)view_logits;
+  for (int v0 = 0; v0 < n; v0 += TT_MAXVIEWS) {
+    const int nv = n - v0 < TT_MAXVIEWS ? n - v0 : TT_MAXVIEWS;
+    const bool last = v0 + nv == n;
+    SemViews a;
+    for (int k = 0; k < nv; ++k) {
+      const long long* d = views + 5 * (size_t)(v0 + k);
+      SemView& s = a.v[k];
+      s.h = (int)d[0]; s.w = (int)d[1]; s.rs = d[2]; s.cs = d[3]; s.flip = d[4] != 0;
+      s.identity = s.h == H && s.w == W;
+      s.sch = (float)s.h / (float)H; s.scw = (float)s.w / (float)W;  // as u2_bilinear_resize_f32 forms its scales
+    }
+    for (int k = nv; k < TT_MAXVIEWS; ++k) a.v[k] = a.v[0];
+    const int fst = first && v0 == 0;
+    const float div = last ? (float)divisor : 0.f;
+    long long* am = last ? argmax : nullptr;
+    const dim3 grid(blocks_of(hw)), block(TT_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    if (C <= 8)
+      hipLaunchKernelGGL(tta_accumulate_sem_seg_kernel<8>, grid, block, 0, s, ptrs + v0, a, nv, acc, am, C, H, W, fst, div);
+    else if (C <= 32)
+      hipLaunchKernelGGL(tta_accumulate_sem_seg_kernel<32>, grid, block, 0, s, ptrs + v0, a, nv, acc, am, C, H, W, fst, div);
+    else
+      hipLaunchKernelGGL(tta_accumulate_sem_seg_kernel<64>, grid, block, 0, s, ptrs + v0, a, nv, acc, am, C, H, W, fst, div);
+    U2_CHECK_LAUNCH();
+  }
   return 0;
 }

@@ -118,6 +118,9 @@ def default_argument_parser():
                    help="polygon ground truth in the segm task: refuse it, or rasterize it as cocoapi does (COCO val2017)")
     p.add_argument("--sem-seg-boundary-iou", action="store_true",
                    help="the semantic evaluator also reports BoundaryIoU and min(IoU, B-Iou) per class (eval mode)")
+    p.add_argument("--tta-outputs", default="instances", choices=("instances", "panoptic"),
+                   help="what TEST.AUG.ENABLED augments: the instance tasks (instances), or for a PanopticFPN the semantic and "
+                        "panoptic outputs as well (panoptic; every evaluator once more, keys suffixed _TTA)")
     p.add_argument("--device-mapper", action="store_true",
                    help="training: resize, flip and decode the samples on the GPU instead of in the loader workers (needs a "
                         "GPU and the real dataset; same batches bit for bit)")

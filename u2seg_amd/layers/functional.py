@@ -854,14 +854,21 @@ class _GroupNormActFn(Function):
     """nn.GroupNorm(G, C) (+ReLU) on NHWC (reference: layers/batch_norm.py:189, semantic_seg.py:196-205)."""
 
     @staticmethod
-    def forward(ctx, y, gamma, beta, groups, relu, eps, grad_dst=None):
+    def forward(ctx, y, gamma, beta, groups, relu, eps, grad_dst=None, ordered=False):
         _check_act(y)
         b, h, w, c = y.shape
         hw = h * w
         cg = c // groups
         ctx.grad_dst = grad_dst  # (dgamma, dbeta) arena slices or None
-        stats = zeros_f32((b, 2, c), y.device)
-        _hip.call("u2_colstats", y, stats, b, hw, c, c)
+        if ordered:
+            # sums in a fixed order: the same input gives the same bits from run to run (u2_colstats adds with atomics)
+            nchunk = max(1, min(256, (hw + 255) // 256))
+            part = torch.empty((b, nchunk, 2, c), dtype=torch.float32, device=y.device)
+            stats = torch.empty((b, 2, c), dtype=torch.float32, device=y.device)
+            _hip.call("u2_colstats_ordered", y, part, stats, b, hw, c, c, nchunk)
+        else:
+            stats = zeros_f32((b, 2, c), y.device)
+            _hip.call("u2_colstats", y, stats, b, hw, c, c)
         coef = torch.empty((4, b, c), dtype=torch.float32, device=y.device)
         mean, invstd, scale, shift = coef[0], coef[1], coef[2], coef[3]
         _hip.call("u2_gn_finalize_fwd", stats, gamma.detach(), beta.detach(), float(hw * cg), float(eps), b, c, groups, mean,
@@ -893,13 +900,15 @@ class _GroupNormActFn(Function):
         _hip.call("u2_gn_finalize_bwd", sums, gamma.detach(), mean, invstd, n, b, c, groups, k1, k2, k3, dg, db, int(direct))
         dx = torch.empty_like(y)
         _hip.call("u2_norm_bwd_apply", dout, None, y, k1, k2, k3, dx, None, b, hw, c, c, int(relu), msc, msh)
-        return dx, (None if direct else dg), (None if direct else db), None, None, None, None
+        return dx, (None if direct else dg), (None if direct else db), None, None, None, None, None
 
 
 def group_norm_act(y, gamma, beta, groups, relu=False, eps=1e-5):
     gd, bd = grad_slot(gamma), grad_slot(beta)
     ok = gd is not None and bd is not None and gd.is_contiguous() and bd.is_contiguous() and gd.dtype == torch.float32
-    return _GroupNormActFn.apply(y, gamma, beta, groups, relu, eps, (gd, bd) if ok else None)
+    # without a graph (inference) the statistics are summed in a fixed order, so that a model in eval mode repeats its bits: test-time
+    # augmentation compares and averages passes over the same views (modeling/test_time_augmentation.py)
+    return _GroupNormActFn.apply(y, gamma, beta, groups, relu, eps, (gd, bd) if ok else None, not torch.is_grad_enabled())
 
 
 # --------------------------------------------------------------------------------------------

@@ -8,3 +8,4 @@ from .rpn import (ANCHOR_GENERATOR_REGISTRY, PROPOSAL_GENERATOR_REGISTRY, RPN, R
 from .sampling import set_key_source, set_permutation_source, subsample_labels
 from .semantic_seg import SEM_SEG_HEADS_REGISTRY, SemSegFPNHead, build_sem_seg_head
 from .test_time_augmentation import DatasetMapperTTA, GeneralizedRCNNWithTTA
+from .tta_panoptic import PanopticFPNWithTTA
