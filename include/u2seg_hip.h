@@ -24,18 +24,123 @@ extern "C" {
  *   out[m][n] = sum_{kh,kw,c} in[src(m,kh,kw)][c] * wt[n][kh][kw][c]   (+bias)(+=old)(relu)
  *   src: sy = oy*mul - pad_h + kh; if div > 1 the tap contributes only when sy % div == 0 and then sy /= div.
  *   stats (optional, [2][N] fp32, pre-zeroed): column sum and sum of squares of the stored bf16 outputs.
- * variant bit0: 1 = register-staged operands instead of global_load_lds; bit2 BK 32; bit3 256x128 tile; bits 4-5 LDS ring depth;
- * bit8 / bit9 force / forbid conv_igemm256; bits 12-15: persistent tile configuration of conv_tile.hip (0 automatic,
- * 1-7 see there, 15 never); bit16: 8 work-groups only (tests). */
+ * variant: the conv word, see below. */
+
+/* ---- the `variant` words and the u2_conv_last_kernel codes -------------------------------------
+ * Every convolution entry point takes an `int variant` that steers which kernel serves the launch.  0 = the library's own
+ * choice, which is all the product path passes apart from U2_CV_STREAMK_FORBID.  A caller that passes 0 can be steered from
+ * the environment instead (tests, A/B runs): the variable named with each word carries the same number.  There are three words
+ * with separate encodings.  A one-bit field has one mask; a wider field has X_SHIFT and X_MASK, its value is
+ * (word >> X_SHIFT) & X_MASK.  "force": wherever the kernel can serve the shape, size rules lifted; "forbid": never.
+ * Where both bits of a pair are set, forbid wins unless the field says otherwise.  This block is the one place where the bits
+ * are described; the values are fixed (recorded command lines carry them) and no field reaches bit 31. */
+
+/* The conv word: u2_conv_igemm, u2_conv_dgrad_tail, U2_CONV_VARIANT.
+ * Bits 0-11 choose among the conv_igemm.hip kernels, which run when no other family takes the launch. */
+#define U2_CV_REG_STAGING (1u << 0)           /* register-staged operands instead of global_load_lds */
+#define U2_CV_BK32 (1u << 2)                  /* K tiles of 32 channels instead of 64 */
+#define U2_CV_TILE_256X128 (1u << 3)          /* 256 px x 128 ch tile, 8 waves (layers with > 64 output channels) */
+#define U2_CV_RING_SHIFT 4                    /* LDS ring depth: 0 = default, 1-3 = 2-4 stages */
+#define U2_CV_RING_MASK 3
+#define U2_CV_WIDE_FORCE (1u << 8)            /* conv_igemm256: 256 x 256 tile, 8 waves */
+#define U2_CV_WIDE_FORBID (1u << 9)
+#define U2_CV_WIDE_STAGGER (1u << 10)         /* conv_igemm256 with the staggered two-group schedule */
+#define U2_CV_WIDE_STAGGER_PARITY (1u << 11)  /* ... its wave groups = even / odd waves instead of waves 0-3 / 4-7 */
+/* Persistent tile kernels of conv_tile.hip: 0 = automatic, 1 = 256ch x 256px ring 4, 2 = 256 x 256 ring 5, 3 = 128ch x 256px
+ * ring 3, 4 = 256ch x 128px ring 3, 5 = 128ch x 256px ring 4, 6 = 64ch x 512px ring 4, 7 = 256 x 256 with whole K tiles (C % 64
+ * == 0), 15 = never. */
+#define U2_CV_TILE_CFG_SHIFT 12
+#define U2_CV_TILE_CFG_MASK 15
+#define U2_CV_TILE_CFG_NEVER 15               /* a value of the field, not a mask */
+#define U2_CV_TINY_GRID (1u << 16)            /* 8 work-groups only (tests: several tiles per work-group), every persistent family */
+/* Bit 17 means two things, one per kernel family: the two names below have the same value. */
+#define U2_CV_STREAM_FORCE (1u << 17)         /* conv_stream.hip: force the weights-resident streaming 1x1 kernel */
+#define U2_CV_HALO_TILE128 (1u << 17)         /* conv_halo.hip: 128-channel tiles also for layers with <= 64 output channels */
+/* Measurement switches (ConvArgs::abl, tests/native/selftest bench2 only): the field as a whole and its bits. */
+#define U2_CV_ABL_SHIFT 18
+#define U2_CV_ABL_MASK 63
+#define U2_CV_ABL_NO_STORES (1u << 18)        /* no output stores */
+#define U2_CV_ABL_NO_STATS (1u << 19)         /* no BN statistics */
+#define U2_CV_ABL_NO_EPILOGUE (1u << 20)      /* no epilogue at all */
+#define U2_CV_ABL_NT_STORES (1u << 21)        /* non-temporal stores for outputs > 160 MB (measured slower, off by default) */
+#define U2_CV_ABL_NO_STATS_FLUSH (1u << 22)   /* conv_halo.hip: statistics summed but their atomics not sent */
+#define U2_CV_HALO_FORCE (1u << 24)           /* conv_halo.hip: halo-staged 3x3 / stride 1 / pad 1 kernel */
+#define U2_CV_HALO_FORBID (1u << 25)
+#define U2_CV_STREAM_FORBID (1u << 26)        /* conv_stream.hip (force: U2_CV_STREAM_FORCE) */
+#define U2_CV_STREAMK_FORCE (1u << 27)        /* conv_tile.hip: stream-K form, equal shares of the (tile, half K tile) sequence */
+#define U2_CV_STREAMK_FORBID (1u << 28)       /* whole tiles only; callers with several streams pass this */
+#define U2_CV_HALO_SCHED_SHIFT 29             /* conv_halo.hip schedule: 0 = default; bit 0 s_setprio around the MFMA runs, */
+#define U2_CV_HALO_SCHED_MASK 3               /* bit 1 sched_barrier fences (measured slower, profiles/r03_conv_halo_sched.txt) */
+/* Cross-field rules.  Any bit of U2_CV_EXPLICIT_MASK (bits 0-15, the unnamed ones included) is an explicit kernel choice and
+ * keeps the launch off the streaming kernel; an explicit tile configuration (U2_CV_TILE_CFG != 0) also keeps it off the halo
+ * kernel. */
+#define U2_CV_EXPLICIT_MASK 0xffffu
+
+/* The wgrad word: u2_conv_wgrad, u2_conv_wgrad_into, U2_WGRAD_VARIANT.
+ * Bits 0-11 belong to the per-tap kernels of conv_igemm.hip (128 x 128 and 256 x 256 tiles). */
+#define U2_WG_REG_STAGING (1u << 0)           /* register-staged operands instead of global_load_lds */
+#define U2_WG_SCALAR_GATHER (1u << 1)         /* scalar LDS gathers instead of ds_read_b64_tr_b16 */
+#define U2_WG_FEWER_SPLITS_SHIFT 4            /* resident work-groups (pixel splits) halved this many times */
+#define U2_WG_FEWER_SPLITS_MASK 3
+#define U2_WG_XCD_FORCE (1u << 6)             /* XCD-grouped launch (default: multi-tap filters over >= 200k pixels); */
+#define U2_WG_XCD_FORBID (1u << 7)            /* force wins over forbid */
+/* 256 x 256 tile kernel (default: 1x1 layers over >= 50k pixels with both channel counts % 256 == 0, and the 7x7 fc1); force wins
+ * over forbid; U2_WG_REG_STAGING or U2_WG_SCALAR_GATHER keeps a launch off it. */
+#define U2_WG_WIDE_FORCE (1u << 8)
+#define U2_WG_WIDE_FORBID (1u << 11)
+#define U2_WG_RING_SHIFT 9                    /* LDS ring depth of the 128 x 128 LDS-DMA form: 0 = two buffers, 1 = 3, 2 = 4 */
+#define U2_WG_RING_MASK 3
+#define U2_WG_HALO_FORCE (1u << 12)           /* wgrad_halo.hip: 3x3 / stride 1 / pad 1, all nine taps per work-group */
+#define U2_WG_HALO_FORBID (1u << 13)
+#define U2_WG_HALO_ROUNDS_SHIFT 14            /* wgrad_halo.hip: rounds of work-groups - 1 (0 = one work-group per CU) */
+#define U2_WG_HALO_ROUNDS_MASK 3
+#define U2_WG_ATOMICS (1u << 16)              /* fp32-atomic epilogue, never partial tiles + a reduction pass; wins over ... */
+#define U2_WG_PARTIALS_FORCE (1u << 17)       /* ... the reduction pass wherever there are >= 2 pixel splits */
+#define U2_WG_STREAM_FORCE (1u << 18)         /* wgrad_stream.hip: 1x1 / stride 1, the dW block in registers (default: >= 200k pixels) */
+#define U2_WG_STREAM_FORBID (1u << 19)
+#define U2_WG_STREAM_TINY (1u << 20)          /* wgrad_stream.hip: 8 pixel ranges only (tests) */
+#define U2_WG_STREAM_CFG_SHIFT 21             /* block: 0 = automatic, 1 = 256(n) x 64(c), 2 = 64 x 256, 3 = 128 x 128, 4 = 256 x 256 */
+#define U2_WG_STREAM_CFG_MASK 7
+#define U2_WG_STREAM_PER_CU_SHIFT 24          /* work-groups per CU: 0 = the configuration's default */
+#define U2_WG_STREAM_PER_CU_MASK 3
+/* Cross-field rules.  Any of bits 0-11 (the unnamed ones included) keeps a launch off the streaming kernel, any of bits 0-10
+ * off the halo kernel: the per-tap kernels' own switches ask for those kernels. */
+#define U2_WG_PER_TAP_MASK_STREAM 0xfffu
+#define U2_WG_PER_TAP_MASK_HALO 0x7ffu
+
+/* The fused 1x1 backward word: u2_conv1x1_bwd_fused, u2_conv1x1_bwd_fused_bn, U2_WDGRAD_VARIANT. */
+#define U2_WD_FORCE (1u << 0)                 /* lift the size rule (>= 200 000 pixels, > 128 valid output channels) */
+#define U2_WD_TINY (1u << 1)                  /* 8 pixel ranges only (tests) */
+#define U2_WD_NEVER (1u << 2)                 /* decline (return 1): the caller takes the separate launches */
+#define U2_WD_BN_TWO_GROUPS (1u << 3)         /* _bn only: 4-wave blocks, two work-groups per CU, instead of one 8-wave group */
+#define U2_WD_BN_WIDE (1u << 4)               /* _bn only: also serve N <= 512 by C <= 128 (declined otherwise: DESIGN.md 5.0) */
+
+/* u2_conv_last_kernel: a code for the kernel family and configuration that took the launch. */
+#define U2_K_TILE 100              /* conv_tile.hip, whole tiles: + tile configuration (1-7) */
+#define U2_K_IGEMM256 256          /* conv_igemm256_kernel ... */
+#define U2_K_IGEMM256_STAGGER 1024 /* ... + this with the staggered schedule */
+#define U2_K_HALO 300              /* conv_halo.hip, 128-channel tiles */
+#define U2_K_HALO_N64 301          /* conv_halo.hip, 64-channel tiles */
+#define U2_K_STREAMK 500           /* conv_tile.hip, stream-K form: + tile configuration */
+#define U2_K_STREAM 700            /* conv_stream.hip: + C / 32 * 10 + (1, 2, 4 waves along the pixels -> 0, 1, 2) ... */
+#define U2_K_STREAM_TAIL 5         /* ... or + C / 32 * 10 + this for u2_conv_dgrad_tail */
+/* conv_igemm_kernel<BK, GLDS, TM, TN, NST>: U2_K_IGEMM + BK * 10000 + TM / 64 * 1000 + TN / 64 * 100 + NST * 10 + GLDS */
+#define U2_K_IGEMM 1000000
+#define U2_K_WGRAD 2000            /* conv_wgrad_kernel<GLDS, TR>: + GLDS * 2 + TR */
+#define U2_K_WGRAD_XCD 100         /* added to U2_K_WGRAD / U2_K_WGRAD256 codes when the launch is XCD-grouped */
+#define U2_K_WGRAD256 2256         /* conv_wgrad256_kernel */
+#define U2_K_WGRAD_STREAM 2700     /* wgrad_stream.hip: + block configuration (1-4) */
+#define U2_K_WDGRAD 2750           /* u2_conv1x1_bwd_fused: + 1 (N <= 256 by C <= 64) / + 2 (N <= 512 by C <= 128) */
+#define U2_K_WDGRAD_BN 2760        /* u2_conv1x1_bwd_fused_bn: + 1 default, + 2 U2_WD_BN_TWO_GROUPS, + 3 U2_WD_BN_WIDE block */
+#define U2_K_WGRAD_HALO 2900       /* wgrad_halo.hip */
+
 int u2_conv_igemm(const void* in, const void* wt, void* out, const float* bias, float* stats,
                   int B, int Hin, int Win, int C, int in_ld, int Hout, int Wout, int N, int out_ld,
                   int KH, int KW, int pad_h, int pad_w, int mul, int div, int relu, int accumulate,
                   int variant, void* stream);
 
 /* Weight gradient: dw[n][kh][kw][c] += sum_m dy[m][n] * x[src(m,kh,kw)][c]; fp32 atomics, dw pre-zeroed.
- * variant bit0: register staging; bit1: scalar LDS gathers instead of ds_read_b64_tr_b16; bits 4-5: fewer pixel splits;
- * bit6 / bit7: force / forbid the XCD-grouped launch (default: on for multi-tap filters over >= 200k pixels); bit8 / bit11:
- * force / forbid the 256 x 256 tile kernel (default: 1x1 layers over >= 200k pixels and the 7x7 fc1); bits 9-10: LDS ring depth. */
+ * variant: the wgrad word, see above. */
 int u2_conv_wgrad(const void* x, const void* dy, float* dw, int B, int Hin, int Win, int C, int x_ld,
                   int Hout, int Wout, int N, int dy_ld, int KH, int KW, int pad_h, int pad_w,
                   int stride, int variant, void* stream);
@@ -52,8 +157,8 @@ int u2_conv_wgrad_into(const void* x, const void* dy, float* dw, int B, int Hin,
  * for the expanding 1x1 layers of the bottlenecks, backbone/resnet.py:194-203): dx[m][c] = sum_n dy[m][n] wt[c][n] (bf16, all dx_ld
  * physical channels written) and dw[n * dw_stride_n + c * dw_stride_c] += sum_m dy[m][n] x[m][c] (fp32, n < n_valid, c < c_valid).
  * wt is the data-gradient layout of the filter, [C][wt_ld] with n contiguous (u2_weight_layout mode 1).  Returns 0 when launched,
- * 1 when the shape is not served (blocks of N <= 256 by C <= 64 or N <= 512 by C <= 128 over >= 200 000 pixels; variant bit 0
- * lifts the size rule, bit 1: 8 pixel ranges, bit 2: never) - the caller then issues u2_conv_igemm + u2_conv_wgrad_into. */
+ * 1 when the shape is not served (blocks of N <= 256 by C <= 64 or N <= 512 by C <= 128 over >= 200 000 pixels) - the caller then
+ * issues u2_conv_igemm + u2_conv_wgrad_into.  variant: the fused 1x1 backward word, see above. */
 int u2_conv1x1_bwd_fused(const void* x, const void* dy, const void* wt, void* dx, float* dw, int M, int C, int x_ld, int N, int dy_ld,
                          int wt_ld, int dx_ld, int n_valid, int c_valid, long long dw_stride_n, int dw_stride_c, int variant,
                          void* stream);
@@ -62,8 +167,8 @@ int u2_conv1x1_bwd_fused(const void* x, const void* dy, const void* wt, void* dx
  * 127-134: conv3 + norm of a bottleneck, the projection shortcut): the normalisation's backward apply step
  * dy[m][n] = k1[n] dz[m][n] + k2[n] y[m][n] + k3[n] (u2_norm_bwd_apply with relu = 0, coefficients of u2_bn_finalize_bwd) is
  * evaluated on the staged rows instead of being written and read back; dx and dw are those of u2_conv1x1_bwd_fused on that dy.
- * Served: N <= 256 by C <= 64 (same size rule and variant bits); returns 1 otherwise - the caller then runs u2_norm_bwd_apply
- * followed by u2_conv1x1_bwd_fused (or the two separate launches). */
+ * Served: N <= 256 by C <= 64 (same size rule); returns 1 otherwise - the caller then runs u2_norm_bwd_apply followed by
+ * u2_conv1x1_bwd_fused (or the two separate launches).  variant: the fused 1x1 backward word, see above. */
 int u2_conv1x1_bwd_fused_bn(const void* x, const void* dz, const void* y, const float* k1, const float* k2, const float* k3,
                             const void* wt, void* dx, float* dw, int M, int C, int x_ld, int N, int dy_ld, int wt_ld, int dx_ld,
                             int n_valid, int c_valid, long long dw_stride_n, int dw_stride_c, int variant, void* stream);
@@ -75,15 +180,15 @@ int u2_conv1x1_bwd_fused_bn(const void* x, const void* dz, const void* y, const 
  * the sums up to the order of the fp32 additions; g1 is never stored.  in: [B][H][W][in_ld] (C reduction channels), wt: [N][C]
  * data-gradient layout, dout2 / y / dz: [B * H * W][N] (out_ld == N), bits: [B * H * W][N / 8] as u2_affine_act writes them,
  * sums: [2][N] fp32 zeroed by the caller.  Served: (C, N) = (64, 256), (128, 512), (256, 1024) on maps the streaming kernel
- * takes (variant bits 16, 17, 26 as for u2_conv_igemm: 8 work-groups only, lift the size rule, never).  Returns 0 when launched,
- * 1 when not served - nothing is written, the caller issues the two launches. */
+ * takes.  Returns 0 when launched, 1 when not served - nothing is written, the caller issues the two launches.
+ * variant: the conv word, see above (U2_CV_TINY_GRID, U2_CV_STREAM_FORCE, U2_CV_STREAM_FORBID and U2_CV_EXPLICIT_MASK apply). */
 int u2_conv_dgrad_tail(const void* in, const void* wt, const void* dout2, const void* y, const void* bits, const float* mean,
                        const float* invstd, void* dz, float* sums, int B, int H, int W, int C, int in_ld, int N, int out_ld,
                        int variant, void* stream);
 
 /* Test / debugging aid: a code for the kernel (family, tile configuration) the most recent u2_conv_igemm or u2_conv_wgrad
- * call on this thread selected (encoding in csrc/conv_args.h).  With variant 0 the selection can be steered through the
- * environment variables U2_CONV_VARIANT / U2_WGRAD_VARIANT (same bits as the variant argument). */
+ * call on this thread selected (the U2_K_ codes above).  With variant 0 the selection can be steered through the
+ * environment variables U2_CONV_VARIANT / U2_WGRAD_VARIANT / U2_WDGRAD_VARIANT (the variant words above). */
 int u2_conv_last_kernel(void);
 
 /* The only device memory the library owns: the conv kernels' scratch (stream-K hand-over slots of u2_conv_igemm, partial tiles of

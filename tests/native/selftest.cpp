@@ -15,6 +15,11 @@
 #define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); exit(2); } } while (0)
 
 static uint16_t f2bf(float f) { uint32_t u; memcpy(&u, &f, 4); u += 0x7fffu + ((u >> 16) & 1u); return (uint16_t)(u >> 16); }
+// the variant words of u2seg_hip.h as the ints the entry points take
+static constexpr int iv(unsigned word) { return (int)word; }
+static constexpr int cv_tile(int cfg, int tiny = 0) { return cfg << U2_CV_TILE_CFG_SHIFT | (tiny ? iv(U2_CV_TINY_GRID) : 0); }
+static constexpr int cv_ring(int stages) { return (stages - 1) << U2_CV_RING_SHIFT; }   // conv_igemm LDS ring of 2-4 stages
+
 static float bf2f(uint16_t v) { uint32_t u = ((uint32_t)v) << 16; float f; memcpy(&f, &u, 4); return f; }
 static uint32_t rng_state = 12345;
 static float frand() { rng_state = rng_state * 1664525u + 1013904223u; return ((rng_state >> 8) & 0xffff) / 32768.0f - 1.0f; }
@@ -210,7 +215,7 @@ static int test_wdgrad_bn(int M, int C, int N, int cv, int nv, int variant, cons
   }
   for (size_t i = 0; i < gdw.size(); ++i) { e2 = fmax(e2, fabs((double)gdw[i] - gdw2[i])); r2 = fmax(r2, fabs((double)gdw2[i])); }
   // fp32 accumulation order differs between the block shapes: one bf16 ulp on dx, 1e-4 relative on dW
-  const bool ok = e1 <= 0.008 * r1 + 1e-6 && e2 <= 2e-4 * r2 + 1e-4 && code == (N > 256 ? 2763 : (variant & 8) ? 2762 : 2761);
+  const bool ok = e1 <= 0.008 * r1 + 1e-6 && e2 <= 2e-4 * r2 + 1e-4 && code == U2_K_WDGRAD_BN + (N > 256 ? 3 : (iv(U2_WD_BN_TWO_GROUPS) & variant) ? 2 : 1);
   printf("%s %-28s v%d  dx diff %.4g (max %.4g, %zu of %zu differ)  dW diff %.4g (max %.4g)  kernel %d\n", ok ? "PASS" : "FAIL", name, variant, e1,
          r1, ndiff, gdx.size(), e2, r2, code);
   return ok ? 0 : 1;
@@ -300,8 +305,8 @@ static void bench2(int argc, char** argv, bool wgrad) {
   std::vector<int> variants;
   for (int i = 2; i < argc; ++i) variants.push_back((int)strtol(argv[i], nullptr, 0));
   if (variants.empty()) {
-    if (wgrad) variants = {2048, 0, 256, 4096, 4096 | (1 << 14)};
-    else variants = {15 << 12, 0, 1 << 12, 2 << 12, 3 << 12, 4 << 12, 5 << 12, 6 << 12};
+    if (wgrad) variants = {iv(U2_WG_WIDE_FORBID), 0, iv(U2_WG_WIDE_FORCE), iv(U2_WG_HALO_FORCE), iv(U2_WG_HALO_FORCE) | 1 << U2_WG_HALO_ROUNDS_SHIFT};
+    else variants = {cv_tile(U2_CV_TILE_CFG_NEVER), 0, cv_tile(1), cv_tile(2), cv_tile(3), cv_tile(4), cv_tile(5), cv_tile(6)};
   }
   size_t in_elems = (size_t)16 * 200 * 336 * 256, out_elems = (size_t)16 * 200 * 336 * 256;
   const size_t w_elems = (size_t)8192 * 8192;
@@ -392,7 +397,7 @@ int main(int argc, char** argv) {
       {1, 45, 23, 64, 72, 3, 3, 1, 1, 1, 0, 0, 1, 1, "tile 3x3 c64 n72 bias stats"},
       {3, 7, 7, 32, 136, 7, 7, 0, 1, 1, 1, 0, 1, 0, "tile fc 7x7 c32 n136 bias relu"},
   };
-  // conv_halo.hip (variant bit 24): 3x3 / stride 1 / pad 1; partial patches in both directions, one and many slabs, channel
+  // conv_halo.hip (U2_CV_HALO_FORCE): 3x3 / stride 1 / pad 1; partial patches in both directions, one and many slabs, channel
   // tails, several tiles per work-group (bit 16), bias / ReLU / statistics
   const ConvCase hconvs[] = {
       {2, 16, 32, 32, 128, 3, 3, 1, 1, 1, 0, 0, 0, 1, "halo 16x32 c32 n128 stats"},
@@ -411,8 +416,8 @@ int main(int argc, char** argv) {
     const int extra = argc > 2 ? (int)strtol(argv[2], nullptr, 0) : 0;
     for (int tiny = 0; tiny < 2; ++tiny)
       for (const auto& c : hconvs) {
-        fails += test_conv(c, (1 << 24) | (tiny << 16) | extra);
-        const int want = (c.N <= 64 && !((extra >> 17) & 1)) ? 301 : 300;
+        fails += test_conv(c, iv(U2_CV_HALO_FORCE | (tiny ? U2_CV_TINY_GRID : 0u)) | extra);
+        const int want = (c.N <= 64 && !(extra & iv(U2_CV_HALO_TILE128))) ? U2_K_HALO_N64 : U2_K_HALO;
         if (u2_conv_last_kernel() != want) { printf("FAIL %-28s did not take the halo conv kernel %d (%d)\n", c.name, want, u2_conv_last_kernel()); ++fails; }
       }
     printf("SELFTEST chalo %s (%d failures)\n", fails ? "FAILED" : "OK", fails);
@@ -420,13 +425,13 @@ int main(int argc, char** argv) {
   }
   if (argc > 2 && !strcmp(argv[1], "tile")) {  // one persistent-tile configuration only
     const int cfg = atoi(argv[2]);
-    const int extra = argc > 3 ? (int)strtol(argv[3], nullptr, 0) : 0;  // further variant bits (bit 17: slab-major order)
+    const int extra = argc > 3 ? (int)strtol(argv[3], nullptr, 0) : 0;  // further bits of the conv word
     for (int tiny = 0; tiny < 2; ++tiny)
-      for (const auto& c : tconvs) fails += test_conv(c, (cfg << 12) | (tiny << 16) | extra);
+      for (const auto& c : tconvs) fails += test_conv(c, cv_tile(cfg, tiny) | extra);
     printf("SELFTEST tile %d %s (%d failures)\n", cfg, fails ? "FAILED" : "OK", fails);
     return fails ? 1 : 0;
   }
-  const WgCase halo_cases[] = {  // 3x3 / stride 1 / pad 1 only: wgrad_halo.hip (variant bit 12), bits 14-15 = rounds - 1
+  const WgCase halo_cases[] = {  // 3x3 / stride 1 / pad 1 only: wgrad_halo.hip (U2_WG_HALO_FORCE), U2_WG_HALO_ROUNDS = rounds - 1
       {2, 14, 14, 64, 64, 3, 3, 1, 1, "halo 14x14 c64 n64"},
       {1, 13, 17, 128, 136, 3, 3, 1, 1, "halo 13x17 c128 n136"},
       {3, 25, 42, 96, 200, 3, 3, 1, 1, "halo 25x42 c96 n200"},
@@ -440,19 +445,20 @@ int main(int argc, char** argv) {
   auto run_halo = [&]() {
     int f = 0;
     for (const auto& c : halo_cases) {
-      f += test_wgrad(c, 4096);
-      if (u2_conv_last_kernel() != 2900) { printf("FAIL %-28s did not take the halo kernel (%d)\n", c.name, u2_conv_last_kernel()); ++f; }
-      f += test_wgrad(c, 4096 | (1 << 14));
-      f += test_wgrad(c, 4096, true);
-      // partial blocks + reduction pass instead of the atomic epilogue (bit 17), plain and into a strided gradient
-      f += test_wgrad(c, 4096 | (1 << 17));
-      f += test_wgrad(c, 4096 | (1 << 17), true);
-      f += test_wgrad(c, 4096 | (1 << 17) | (1 << 14), true);
+      const int halo = iv(U2_WG_HALO_FORCE), part = iv(U2_WG_PARTIALS_FORCE), rounds2 = 1 << U2_WG_HALO_ROUNDS_SHIFT;
+      f += test_wgrad(c, halo);
+      if (u2_conv_last_kernel() != U2_K_WGRAD_HALO) { printf("FAIL %-28s did not take the halo kernel (%d)\n", c.name, u2_conv_last_kernel()); ++f; }
+      f += test_wgrad(c, halo | rounds2);
+      f += test_wgrad(c, halo, true);
+      // partial blocks + reduction pass instead of the atomic epilogue, plain and into a strided gradient
+      f += test_wgrad(c, halo | part);
+      f += test_wgrad(c, halo | part, true);
+      f += test_wgrad(c, halo | part | rounds2, true);
     }
     return f;
   };
-  // wgrad_stream.hip (variant bit 18 forces it on small maps; bits 21-23 block configuration, bit 20: 8 pixel ranges, bits 24-25
-  // work-groups per CU): M not a multiple of 32, channel tails on both sides, blocks tiled over N and over C, 1 .. many steps per range
+  // wgrad_stream.hip (the U2_WG_STREAM_ fields: forced on small maps, block configuration, 8 pixel ranges, work-groups per
+  // CU): M not a multiple of 32, channel tails on both sides, blocks tiled over N and over C, 1 .. many steps per range
   const WgCase ws_cases[] = {
       {1, 37, 29, 64, 256, 1, 1, 0, 1, "wstream 37x29 c64 n256"},
       {2, 33, 21, 256, 64, 1, 1, 0, 1, "wstream 33x21 c256 n64"},
@@ -512,7 +518,8 @@ int main(int argc, char** argv) {
         {2, 37, 41, 192, 136, 1, 1, 0, 2, 1, 0, 0, 0, 1, "tile7 1x1 s2 c192 n136 stats"},
         {1, 1100, 1, 512, 264, 1, 1, 0, 1, 1, 0, 0, 0, 0, "tile7 gemm k512 n264"},
     };
-    for (int v : {7 << 12, (7 << 12) | (1 << 16), (7 << 12) | (1 << 27), (7 << 12) | (1 << 27) | (1 << 16), (7 << 12) | (1 << 28)})
+    for (int v : {cv_tile(7), cv_tile(7, 1), cv_tile(7) | iv(U2_CV_STREAMK_FORCE), cv_tile(7, 1) | iv(U2_CV_STREAMK_FORCE),
+                  cv_tile(7) | iv(U2_CV_STREAMK_FORBID)})
       for (const auto& c : k64) {
         fails += test_conv(c, v);
         if (u2_conv_last_kernel() % 100 != 7) { printf("FAIL %-28s v%x did not take configuration 7 (%d)\n", c.name, v, u2_conv_last_kernel()); ++fails; }
@@ -521,15 +528,17 @@ int main(int argc, char** argv) {
     return fails ? 1 : 0;
   }
   if (argc > 1 && !strcmp(argv[1], "wdgrad_bn")) {
-    for (int v : {1, 3, 1 | 8, 3 | 8}) {   // forced; | 2: 8 pixel ranges; | 8: the 4-wave block, two work-groups per CU
+    // forced; 8 pixel ranges; the 4-wave block, two work-groups per CU
+    for (int v : {iv(U2_WD_FORCE), iv(U2_WD_FORCE | U2_WD_TINY), iv(U2_WD_FORCE | U2_WD_BN_TWO_GROUPS),
+                  iv(U2_WD_FORCE | U2_WD_TINY | U2_WD_BN_TWO_GROUPS)}) {
       fails += test_wdgrad_bn(37 * 29, 64, 256, 64, 256, v, "wdgrad_bn 64->256");
       fails += test_wdgrad_bn(33 * 21 * 2, 40, 200, 37, 196, v, "wdgrad_bn 40->200 (tails)");
       fails += test_wdgrad_bn(5, 32, 136, 32, 136, v, "wdgrad_bn 5 px");
       fails += test_wdgrad_bn(40 * 70, 8, 16, 8, 16, v, "wdgrad_bn 8->16");
       fails += test_wdgrad_bn(64 * 131, 64, 256, 64, 256, v, "wdgrad_bn 64->256 8384 px");
-      if (!(v & 8)) {
-        fails += test_wdgrad_bn(19 * 45, 128, 512, 128, 512, v | 16, "wdgrad_bn 128->512");
-        fails += test_wdgrad_bn(45 * 23, 72, 264, 70, 260, v | 16, "wdgrad_bn 72->264 (wide, tails)");
+      if (!(v & iv(U2_WD_BN_TWO_GROUPS))) {
+        fails += test_wdgrad_bn(19 * 45, 128, 512, 128, 512, v | iv(U2_WD_BN_WIDE), "wdgrad_bn 128->512");
+        fails += test_wdgrad_bn(45 * 23, 72, 264, 70, 260, v | iv(U2_WD_BN_WIDE), "wdgrad_bn 72->264 (wide, tails)");
       }
     }
     printf("SELFTEST wdgrad_bn %s (%d failures)\n", fails ? "FAILED" : "OK", fails);
@@ -557,10 +566,10 @@ int main(int argc, char** argv) {
         auto run = [&]() {
           if (mode == 0) {
             u2_norm_bwd_apply(ddz.d, nullptr, dy.d, dk.d, dk.d + N, dk.d + 2 * N, ddy.d, nullptr, 1, M, N, N, 0, nullptr, nullptr, nullptr);
-            u2_conv1x1_bwd_fused(dx_in.d, ddy.d, dwt.d, ddx.d, ddw.d, M, C, C, N, N, N, C, N, C, (long long)C, 1, 1, nullptr);
+            u2_conv1x1_bwd_fused(dx_in.d, ddy.d, dwt.d, ddx.d, ddw.d, M, C, C, N, N, N, C, N, C, (long long)C, 1, iv(U2_WD_FORCE), nullptr);
           } else {
             u2_conv1x1_bwd_fused_bn(dx_in.d, ddz.d, dy.d, dk.d, dk.d + N, dk.d + 2 * N, dwt.d, ddx.d, ddw.d, M, C, C, N, N, N, C, N, C, (long long)C, 1,
-                                    res3 ? 1 | 16 : mode == 1 ? 1 : 1 | 8, nullptr);
+                                    iv(U2_WD_FORCE | (res3 ? U2_WD_BN_WIDE : mode == 1 ? 0u : U2_WD_BN_TWO_GROUPS)), nullptr);
           }
         };
         run();
@@ -577,7 +586,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   if (argc > 1 && !strcmp(argv[1], "wdgrad")) {
-    for (int v = 1; v <= 3; v += 2) {   // forced, full grid / forced, 8 pixel ranges
+    for (int v : {iv(U2_WD_FORCE), iv(U2_WD_FORCE | U2_WD_TINY)}) {   // forced, full grid / forced, 8 pixel ranges
       fails += test_wdgrad(37 * 29, 64, 256, 64, 256, v, "wdgrad 64->256");
       fails += test_wdgrad(33 * 21 * 2, 40, 200, 37, 196, v, "wdgrad 40->200 (tails)");
       fails += test_wdgrad(19 * 45, 128, 512, 128, 512, v, "wdgrad 128->512");
@@ -592,11 +601,11 @@ int main(int argc, char** argv) {
     for (int cfg = 0; cfg <= 4; ++cfg)
       for (int tiny = 0; tiny < 2; ++tiny)
         for (const auto& c : ws_cases) {
-          const int v = (1 << 18) | (tiny << 20) | (cfg << 21);
+          const int v = iv(U2_WG_STREAM_FORCE | (tiny ? U2_WG_STREAM_TINY : 0u)) | cfg << U2_WG_STREAM_CFG_SHIFT;
           fails += test_wgrad(c, v);
-          if (u2_conv_last_kernel() / 100 != 27) { printf("FAIL %-28s did not take the streaming kernel (%d)\n", c.name, u2_conv_last_kernel()); ++fails; }
+          if (u2_conv_last_kernel() / 100 != U2_K_WGRAD_STREAM / 100) { printf("FAIL %-28s did not take the streaming kernel (%d)\n", c.name, u2_conv_last_kernel()); ++fails; }
           if (cfg == 0 || tiny) fails += test_wgrad(c, v, true);
-          if (cfg >= 1 && cfg <= 3 && !tiny) fails += test_wgrad(c, v | (1 << 24));   // one work-group per CU
+          if (cfg >= 1 && cfg <= 3 && !tiny) fails += test_wgrad(c, v | 1 << U2_WG_STREAM_PER_CU_SHIFT);   // one work-group per CU
         }
     printf("SELFTEST wstream %s (%d failures)\n", fails ? "FAILED" : "OK", fails);
     return fails ? 1 : 0;
@@ -618,31 +627,35 @@ int main(int argc, char** argv) {
       {1, 200, 1, 128, 801, 1, 1, 0, 1, 1, 0, 0, 1, 0, "linear k128 n801 bias"},
       {1, 9, 9, 64, 64, 3, 3, 1, 1, 1, 1, 1, 0, 0, "3x3 accumulate relu"},
   };
-  const int cvs[] = {0, 1, 32, 48, 4, 4 | 32, 8, 8 | 4 | 32, 256, 256 | 1024};
+  const int bk32 = iv(U2_CV_BK32), big = iv(U2_CV_TILE_256X128), wide = iv(U2_CV_WIDE_FORCE), stagger = iv(U2_CV_WIDE_STAGGER);
+  const int cvs[] = {0, iv(U2_CV_REG_STAGING), cv_ring(3), cv_ring(4), bk32, bk32 | cv_ring(3), big, big | bk32 | cv_ring(3), wide, wide | stagger};
   for (int v : cvs)
     for (const auto& c : convs) fails += test_conv(c, v);
-  // persistent tile kernels (conv_tile.hip): variant bits 12-15 pick the configuration, bit 16 caps the grid at 8
+  // persistent tile kernels (conv_tile.hip): U2_CV_TILE_CFG picks the configuration, U2_CV_TINY_GRID caps the grid at 8
   // work-groups so that every work-group walks several tiles (cross-tile prefetch, accumulator reset, tail waits)
   for (int cfg = 1; cfg <= 6; ++cfg)
     for (int tiny = 0; tiny < 2; ++tiny)
-      for (const auto& c : tconvs) fails += test_conv(c, (cfg << 12) | (tiny << 16));
+      for (const auto& c : tconvs) fails += test_conv(c, cv_tile(cfg, tiny));
   const WgCase wgs[] = {
       {2, 9, 11, 64, 64, 1, 1, 0, 1, "wgrad 1x1 c64 n64"},
       {1, 13, 17, 128, 136, 3, 3, 1, 1, "wgrad 3x3 c128 n136"},
       {2, 14, 18, 72, 96, 3, 3, 1, 2, "wgrad 3x3 s2 c72 n96"},
       {1, 700, 1, 160, 64, 1, 1, 0, 1, "wgrad gemm k160 n64"},
   };
-  for (int v = 0; v < 4; ++v)
+  for (int v : {0, iv(U2_WG_REG_STAGING), iv(U2_WG_SCALAR_GATHER), iv(U2_WG_REG_STAGING | U2_WG_SCALAR_GATHER)})
     for (const auto& c : wgs) fails += test_wgrad(c, v);
-  for (const auto& c : wgs) fails += test_wgrad(c, 64);
-  for (const auto& c : wgs) fails += test_wgrad(c, 1 << 9);
-  for (const auto& c : wgs) fails += test_wgrad(c, 2 << 9);
-  for (const auto& c : wgs) fails += test_wgrad(c, 256);
-  for (const auto& c : wgs) fails += test_wgrad(c, 256, true);
+  for (const auto& c : wgs) fails += test_wgrad(c, iv(U2_WG_XCD_FORCE));
+  for (const auto& c : wgs) fails += test_wgrad(c, 1 << U2_WG_RING_SHIFT);
+  for (const auto& c : wgs) fails += test_wgrad(c, 2 << U2_WG_RING_SHIFT);
+  for (const auto& c : wgs) fails += test_wgrad(c, iv(U2_WG_WIDE_FORCE));
+  for (const auto& c : wgs) fails += test_wgrad(c, iv(U2_WG_WIDE_FORCE), true);
   for (const auto& c : wgs) fails += test_wgrad(c, 0, true);
   fails += run_halo();
   printf("SELFTEST %s (%d failures)\n", fails ? "FAILED" : "OK", fails);
   if (argc > 1 && !strcmp(argv[1], "bench")) {
+    // bench_conv hands one number to u2_conv_igemm and to u2_conv_wgrad: the names below are the conv word's; in the wgrad word
+    // no_wide is U2_WG_RING = 1 and wide / stagger / parity are U2_WG_WIDE_FORCE / U2_WG_RING = 2 / U2_WG_WIDE_FORBID
+    const int no_wide = iv(U2_CV_WIDE_FORBID), parity = iv(U2_CV_WIDE_STAGGER_PARITY);
     for (int v = 0; v < 1; ++v) {
       bench_conv("res2 3x3 64->64 B16", 16, 200, 336, 64, 64, 3, 1, 1, v);
       bench_conv("res2 1x1 64->256 B16", 16, 200, 336, 64, 256, 1, 0, 1, v);
@@ -651,13 +664,13 @@ int main(int argc, char** argv) {
       bench_conv("res4 3x3 256->256 B16", 16, 50, 84, 256, 256, 3, 1, 1, v);
       bench_conv("res4 1x1 1024->256 B16", 16, 50, 84, 1024, 256, 1, 0, 1, v);
       bench_conv("res5 3x3 512->512 B16", 16, 25, 42, 512, 512, 3, 1, 1, v);
-      bench_conv("fpn_out2 3x3 256->256 B16", 16, 200, 336, 256, 256, 3, 1, 1, v | 512);
-      bench_conv("fpn_out3 3x3 256->256 B16", 16, 100, 168, 256, 256, 3, 1, 1, v | 512);
-      bench_conv("lat2 1x1 256->256 B16", 16, 200, 336, 256, 256, 1, 0, 1, v | 512);
-      bench_conv("fc1 12544->1024 M8192", 1, 8192, 1, 12544, 1024, 1, 0, 1, v | 512);
-      bench_conv("gemm 8192x8192x8192", 1, 8192, 1, 8192, 8192, 1, 0, 1, v | 512);
+      bench_conv("fpn_out2 3x3 256->256 B16", 16, 200, 336, 256, 256, 3, 1, 1, v | no_wide);
+      bench_conv("fpn_out3 3x3 256->256 B16", 16, 100, 168, 256, 256, 3, 1, 1, v | no_wide);
+      bench_conv("lat2 1x1 256->256 B16", 16, 200, 336, 256, 256, 1, 0, 1, v | no_wide);
+      bench_conv("fc1 12544->1024 M8192", 1, 8192, 1, 12544, 1024, 1, 0, 1, v | no_wide);
+      bench_conv("gemm 8192x8192x8192", 1, 8192, 1, 8192, 8192, 1, 0, 1, v | no_wide);
     }
-    for (int v : {512 | 4 | 16}) {  // 128 x 128 tile, BK 32, two-stage ring: 32 KB LDS, three work-groups per CU
+    for (int v : {no_wide | bk32 | cv_ring(2)}) {  // 128 x 128 tile, BK 32, two-stage ring: 32 KB LDS, three work-groups per CU
       bench_conv("fpn_out2 3x3 256->256 B16", 16, 200, 336, 256, 256, 3, 1, 1, v);
       bench_conv("res3 3x3 128->128 B16", 16, 100, 168, 128, 128, 3, 1, 1, v);
       bench_conv("res4 3x3 256->256 B16", 16, 50, 84, 256, 256, 3, 1, 1, v);
@@ -665,11 +678,11 @@ int main(int argc, char** argv) {
       bench_conv("res4 1x1 256->1024 B16", 16, 50, 84, 256, 1024, 1, 0, 1, v);
       bench_conv("res3 1x1 512->128 B16", 16, 100, 168, 512, 128, 1, 0, 1, v);
     }
-    for (int v : {512}) {
+    for (int v : {no_wide}) {
       bench_conv("res4 1x1 256->1024 B16", 16, 50, 84, 256, 1024, 1, 0, 1, v);
       bench_conv("res3 1x1 512->128 B16", 16, 100, 168, 512, 128, 1, 0, 1, v);
     }
-    for (int v : {256, 256 | 1024, 256 | 1024 | 2048}) {  // 256 x 256 tile, 8 waves; | 1024: staggered wave groups
+    for (int v : {wide, wide | stagger, wide | stagger | parity}) {  // 256 x 256 tile, 8 waves; staggered wave groups
       bench_conv("fpn_out2 3x3 256->256 B16", 16, 200, 336, 256, 256, 3, 1, 1, v);
       bench_conv("fpn_out3 3x3 256->256 B16", 16, 100, 168, 256, 256, 3, 1, 1, v);
       bench_conv("res4 3x3 256->256 B16", 16, 50, 84, 256, 256, 3, 1, 1, v);
@@ -679,7 +692,7 @@ int main(int argc, char** argv) {
       bench_conv("fc1 12544->1024 M8192", 1, 8192, 1, 12544, 1024, 1, 0, 1, v);
       bench_conv("gemm 8192x8192x8192", 1, 8192, 1, 8192, 8192, 1, 0, 1, v);
     }
-    const int vs[] = {512};  // wgrad: 128 x 128 tiles only (the default picks 256 x 256 when N and C are multiples of 256)
+    const int vs[] = {no_wide};  // wgrad: 128 x 128 tiles only (the default picks 256 x 256 when N and C are multiples of 256)
     for (int v : vs) {
       bench_conv("res2 3x3 64->64 B16", 16, 200, 336, 64, 64, 3, 1, 1, v);
       bench_conv("res3 3x3 128->128 B16", 16, 100, 168, 128, 128, 3, 1, 1, v);

@@ -30,8 +30,8 @@ import pytest
 import torch
 
 from tests import float64_refs as R
-from tests.test_gpu_kernel_variants import (CONV_VARIANTS, NEVER_TILE, STREAM, WS_FORCE, WS_TINY, forced, igemm_code,
-                                            last_kernel)
+from tests.conv_variants import (CONV_VARIANTS, HALO, K, NEVER_TILE, STREAM, TINY, WGRAD_HALO_VARIANTS, WGRAD_TAP_VARIANTS, WS_FORCE,
+                                 forced, igemm_code, last_kernel, stream_code, ws_variant)
 
 pytestmark = pytest.mark.gpu
 
@@ -354,9 +354,9 @@ def test_stride2_data_gradient_parity_classes(F, geom, mode):
 @pytest.mark.parametrize("geom", R.HALO_GEOMS)
 def test_conv_halo_patches(F, geom, tiny, mode):
     """conv_halo.hip (16 x 32 pixel patches, forced): a map inside one patch, exactly one patch, one pixel over on each axis, and
-    33 x 65; 128-channel tiles (300) and the 64-channel tiles (301), ragged channel tails; all gradients."""
-    code = 301 if geom[4] <= 64 else 300
-    variant = (1 << 24) | (tiny << 16)
+    33 x 65; 128-channel tiles (K_HALO) and the 64-channel tiles (K_HALO_N64), ragged channel tails; all gradients."""
+    code = K.K_HALO_N64 if geom[4] <= 64 else K.K_HALO
+    variant = HALO | (TINY if tiny else 0)
     run_layer(F, geom, mode, conv=variant, fwd_code=code, name="halo tiny %d" % tiny)
     if mode == "exact":
         low_amplitude_statistics(F, geom, variant, code, "halo")
@@ -369,16 +369,16 @@ def test_conv_stream_ring(F, geom, mode):
     """conv_stream.hip (1x1, pixel rows through the LDS ring, forced): one pixel, 63 pixels, and - on the 8-work-group grid -
     one pixel short of and one pixel past the point where every walker's ring is full (float64_refs.stream_pixel_counts)."""
     cin, cout, m = geom[3], geom[4], geom[2]
-    code = 700 + (cin // 32) * 10 + (0 if cout > 128 else 1 if cout > 64 else 2)
-    variant = STREAM | ((1 << 16) if m > 63 else 0)
+    code = stream_code(cin, cout)
+    variant = STREAM | (TINY if m > 63 else 0)
     run_layer(F, geom, mode, conv=variant, fwd_code=code, bias_leg="fwd", name="stream")
 
 
 # ---- 6. accumulating epilogue ----
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("geom,code", list(zip(R.ACC_GEOMS, [None, 104, None])))
+@pytest.mark.parametrize("geom,code", list(zip(R.ACC_GEOMS, [None, K.K_TILE + 4, None])))
 def test_accumulating_epilogue(F, geom, code, mode):
-    """conv2d_add_: out = relu(bf16(conv1x1(x) + bias) + out) in place - conv_tile_kernel<4, 1, 3, ACC> (104) and, where the map
+    """conv2d_add_: out = relu(bf16(conv1x1(x) + bias) + out) in place - conv_tile_kernel<4, 1, 3, ACC> (K_TILE + 4) and, where the map
     is too small for it, conv_igemm_kernel's accumulate path (asserted: an igemm code); both roundings in the reference."""
     b, h, w, cin, cout = geom[:5]
     x, wt, bias, _, old = R.conv_operands(geom, mode)
@@ -406,15 +406,13 @@ def test_long_reductions(F, geom, linear, mode):
 @pytest.mark.parametrize("mode", MODES)
 def test_fully_connected_7x7(F, mode):
     """The box head's fc1 as a 7x7 conv over 37 ROIs of 7 x 7 x 256 -> 1024: forward, the plain-GEMM data-gradient branch of
-    _Conv2dFn.backward and the wide-tile weight-gradient rule (Hout == Wout == 1: conv_wgrad256_kernel, 2256)."""
-    run_layer(F, R.FC_GEOM, mode, wgrad_code=2256, bias_leg="fwd", name="fc1")
+    _Conv2dFn.backward and the wide-tile weight-gradient rule (Hout == Wout == 1: conv_wgrad256_kernel, K_WGRAD256)."""
+    run_layer(F, R.FC_GEOM, mode, wgrad_code=K.K_WGRAD256, bias_leg="fwd", name="fc1")
 
 
 # ---- 9. weight-gradient kernels ----
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("variant,code", [(0, 2003), (1, 2001), (2, 2002), (3, 2000), (64, 2103), (128, 2003), (256, 2256),
-                                          (256 | 64, 2356), (16, 2003), (32, 2003), (131072, 2003), (131072 | 256, 2256),
-                                          (131072 | 64, 2103), (65536, 2003)])
+@pytest.mark.parametrize("variant,code", WGRAD_TAP_VARIANTS)
 def test_wgrad_per_tap_variants(F, variant, code, mode):
     """conv_wgrad_kernel<GLDS, TR> (all four), the XCD-grouped launch, conv_wgrad256_kernel, atomics and partial tiles +
     wgrad_reduce_kernel, on 3x3 128 -> 136 and 1x1 256 -> 264 over 2 x 21 x 27."""
@@ -423,12 +421,12 @@ def test_wgrad_per_tap_variants(F, variant, code, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("variant", [4096, 4096 | (1 << 14), 4096 | (1 << 17), 4096 | (1 << 17) | (1 << 14), 4096 | (1 << 16)])
+@pytest.mark.parametrize("variant", WGRAD_HALO_VARIANTS)
 @pytest.mark.parametrize("geom", R.WGRAD_HALO_GEOMS)
 def test_wgrad_halo_variants(F, geom, variant, mode):
     """conv_wgrad_halo_kernel forced: atomics, partial blocks + reduction pass, two rounds.  Its launcher serves H >= 2 and
-    W >= 11 (wgrad_halo.hip:launch_wgrad_halo); the 5 x 7, 1 x 1 and 1 x 9 maps go on to the per-tap kernel (2003)."""
-    code = 2900 if geom[1] >= 2 and geom[2] >= 11 else 2003
+    W >= 11 (wgrad_halo.hip:launch_wgrad_halo); the 5 x 7, 1 x 1 and 1 x 9 maps go on to the per-tap kernel (K_WGRAD + 3)."""
+    code = K.K_WGRAD_HALO if geom[1] >= 2 and geom[2] >= 11 else K.K_WGRAD + 3
     run_layer(F, geom, mode, wgrad=variant, wgrad_code=code, stats=False, bias_leg=None, name="wgrad halo %d" % variant)
 
 
@@ -439,12 +437,12 @@ def test_wgrad_stream_configurations(F, cfg, tiny, mode):
     """wgrad_stream_kernel, every block configuration, 8 pixel ranges and the full grid: one pixel, 323, 1073 and 1386 pixels (no
     multiple of the 32-pixel step or of a range), channel tails on both operands."""
     for geom in R.WGRAD_STREAM_GEOMS:
-        variant = WS_FORCE | (WS_TINY if tiny else 0) | (cfg << 21)
+        variant = ws_variant(cfg, tiny)
         b, h, w, cin, cout = geom[:5]
         r = plain_refs(geom, mode)
         with forced(wgrad=variant):
             got = abi_wgrad(F, r["x"], r["gy"], geom)
-            assert last_kernel() // 100 == 27 and (cfg == 0 or last_kernel() == 2700 + cfg), (cfg, last_kernel())
+            assert last_kernel() // 100 == K.K_WGRAD_STREAM // 100 and (cfg == 0 or last_kernel() == K.K_WGRAD_STREAM + cfg), (cfg, last_kernel())
         check_f32("wgrad stream %d %d %s" % (cfg, tiny, geom), got, r["dw"][0], r["dw"][1], b * h * w, mode)
 
 
@@ -462,9 +460,11 @@ def guarded_destination(n_valid, c_valid, taps, g, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("geom,variant,code", [(R.WGRAD_TAP_GEOMS[0], 8192, 2003), (R.WGRAD_TAP_GEOMS[0], 4096, 2900),
-                                               (R.WGRAD_TAP_GEOMS[0], 4096 | (1 << 17), 2900), (R.WGRAD_TAP_GEOMS[1], 1 << 19, 2003),
-                                               (R.WGRAD_TAP_GEOMS[1], WS_FORCE, 2703), (R.WGRAD_TAP_GEOMS[1], 256, 2256)])
+@pytest.mark.parametrize("geom,variant,code", [
+    (R.WGRAD_TAP_GEOMS[0], K.WG_HALO_FORBID, K.K_WGRAD + 3), (R.WGRAD_TAP_GEOMS[0], K.WG_HALO_FORCE, K.K_WGRAD_HALO),
+    (R.WGRAD_TAP_GEOMS[0], K.WG_HALO_FORCE | K.WG_PARTIALS_FORCE, K.K_WGRAD_HALO),
+    (R.WGRAD_TAP_GEOMS[1], K.WG_STREAM_FORBID, K.K_WGRAD + 3), (R.WGRAD_TAP_GEOMS[1], WS_FORCE, K.K_WGRAD_STREAM + 3),
+    (R.WGRAD_TAP_GEOMS[1], K.WG_WIDE_FORCE, K.K_WGRAD256)])
 def test_wgrad_into_strided_destination(F, geom, variant, code, mode):
     """u2_conv_wgrad_into: += into a destination that holds non-zero values, laid out with the reference's [N][Cin][KH][KW]
     strides, n_valid < N and c_valid < C; the bands around and between the written rows come back untouched (bit for bit in
@@ -494,7 +494,7 @@ def test_wgrad_into_strided_destination(F, geom, variant, code, mode):
 @pytest.mark.parametrize("tiny", [0, 1])
 @pytest.mark.parametrize("geom", R.FUSED_GEOMS)
 def test_fused_1x1_backward(F, geom, tiny, mode):
-    """u2_conv1x1_bwd_fused (variant bit 0 lifts the size rule; bit 1: 8 pixel ranges): dx (all physical channels written, the
+    """u2_conv1x1_bwd_fused (U2_WD_FORCE lifts the size rule; U2_WD_TINY: 8 pixel ranges): dx (all physical channels written, the
     padded ones zero) and dw += into a non-zero [N][Cin] destination, blocks of N <= 256 by C <= 64 (2751) and N <= 512 by
     C <= 128 (2752), one pixel and 2 x 37 x 41 pixels, channel tails.  The launcher must answer 0 (launched)."""
     from u2seg_amd import _hip
@@ -511,8 +511,8 @@ def test_fused_1x1_backward(F, geom, tiny, mode):
     wdl = F.weight_dgrad_layout(r["w"].float().to(DEV), cp, npad)
     dx = torch.full((b, h, w, cp), 7.0, dtype=BF16, device=DEV)
     rc = _hip.call_status("u2_conv1x1_bwd_fused", xd, dzd, wdl, dx, buf, m, cp, cp, npad, npad, npad, cp, cout, cin, cin, 1,
-                          1 | (2 if tiny else 0))
-    assert rc == 0 and last_kernel() == (2751 if cout <= 256 else 2752), (rc, last_kernel())
+                          K.WD_FORCE | (K.WD_TINY if tiny else 0))
+    assert rc == 0 and last_kernel() == K.K_WDGRAD + (1 if cout <= 256 else 2), (rc, last_kernel())
     got_dx, pad = host_act(dx, cin)
     assert pad == 0.0
     check_bf16("fused dx %s" % (geom,), got_dx, r["dx"][0], r["dx"][1], cout, mode)
@@ -550,8 +550,8 @@ def test_fused_1x1_backward_with_norm_apply_exact(F, geom, tiny):
     wdl = F.weight_dgrad_layout(wt.float().to(DEV), cp, npad)
     dx = torch.full((b, h, w, cp), 7.0, dtype=BF16, device=DEV)
     rc = _hip.call_status("u2_conv1x1_bwd_fused_bn", xd, dzd, ynd, ks[0], ks[1], ks[2], wdl, dx, buf, m, cp, cp, npad, npad, npad, cp,
-                          cout, cin, cin, 1, 1 | (2 if tiny else 0))
-    assert rc == 0 and last_kernel() == 2761, (rc, last_kernel())
+                          cout, cin, cin, 1, K.WD_FORCE | (K.WD_TINY if tiny else 0))
+    assert rc == 0 and last_kernel() == K.K_WDGRAD_BN + 1, (rc, last_kernel())
     got_dx, pad = host_act(dx, cin)
     assert pad == 0.0
     check_bf16("fused bn dx %s" % (geom,), got_dx, ref_dx[0], ref_dx[1], cout, "exact")

@@ -10,12 +10,14 @@ Two kinds of test:
     256 -> 256; non-temporal output stores, the deepest LDS ring, XCD-grouped wgrad) forward / dgrad / wgrad and a few
     more layers forward, against an fp32 reference evaluated at sampled output positions.
 """
-import contextlib
 import os
 
 import pytest
 import torch
 import torch.nn.functional as TF
+
+from tests.conv_variants import (CONV_VARIANTS, HALO, K, NARROW_VARIANTS, STREAM, TINY, WGRAD_HALO_VARIANTS, WGRAD_TAP_VARIANTS,
+                                 forced, last_kernel, stream_code, ws_variant)
 
 pytestmark = pytest.mark.gpu
 
@@ -52,28 +54,6 @@ def rel_err(a, b):
     return float((a.detach() - b.detach()).abs().max() / (b.detach().abs().max() + 1e-12))
 
 
-@contextlib.contextmanager
-def forced(conv=None, wgrad=None):
-    old = {k: os.environ.get(k) for k in ("U2_CONV_VARIANT", "U2_WGRAD_VARIANT")}
-    try:
-        for k, v in (("U2_CONV_VARIANT", conv), ("U2_WGRAD_VARIANT", wgrad)):
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        # the kernel tests see the library's own dispatch: the product path's rule of where the stream-K form may run
-        # (layers/functional.py:streamk_region - only the bottom-up backbone asks for it) is tested in test_streamk_region_rule
-        from u2seg_amd.layers import functional as _fn
-        with _fn.streamk_region():
-            yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 # One bf16 rounding of the result: the HIP output is the correctly rounded fp32 sum (up to accumulation-order noise), so against
 # the UNROUNDED fp32 reference it is off by at most half a bf16 step, 2^-9 of the element and < 4e-3 of the largest one.
 ULP = 4e-3
@@ -81,44 +61,6 @@ ULP = 4e-3
 # bf(w) = w.bfloat16().float(), whose backward rounds the gradient to bf16 (as the reference's autocast does for the gradient of
 # a bf16 weight copy) - the same half-step bound applies, with the HIP side the more precise one.
 WG_TOL = 4e-3
-
-
-def last_kernel():
-    from u2seg_amd import _hip
-
-    return _hip.call_nostream("u2_conv_last_kernel")
-
-
-def igemm_code(bk, tm, tn, nst, glds=1):
-    return 1000000 + bk * 10000 + (tm // 64) * 1000 + (tn // 64) * 100 + nst * 10 + glds
-
-
-NEVER_TILE = 15 << 12
-# (U2_CONV_VARIANT, expected u2_conv_last_kernel of the FORWARD launch) on the 3x3 64 -> 256 case below (K = 576)
-CONV_VARIANTS = [
-    (NEVER_TILE, igemm_code(64, 128, 128, 2)),            # 128 x 128, BK 64, 2-stage LDS-DMA ring (the default of that family)
-    (NEVER_TILE | 1, igemm_code(64, 128, 128, 2, 0)),     # register-staged operands
-    (NEVER_TILE | 32, igemm_code(64, 128, 128, 3)),       # 3-stage ring
-    (NEVER_TILE | 48, igemm_code(64, 128, 128, 4)),       # 4-stage ring
-    (NEVER_TILE | 4, igemm_code(32, 128, 128, 4)),        # BK 32 (default ring depth 4)
-    (NEVER_TILE | 4 | 16, igemm_code(32, 128, 128, 2)),
-    (NEVER_TILE | 4 | 32, igemm_code(32, 128, 128, 3)),
-    (NEVER_TILE | 4 | 1, igemm_code(32, 128, 128, 2, 0)),
-    (NEVER_TILE | 8, igemm_code(64, 256, 128, 2)),        # 256 x 128 tile, 8 waves
-    (NEVER_TILE | 8 | 1, igemm_code(64, 256, 128, 2, 0)),
-    (NEVER_TILE | 8 | 32, igemm_code(64, 256, 128, 3)),
-    (NEVER_TILE | 8 | 4, igemm_code(32, 256, 128, 4)),
-    (NEVER_TILE | 8 | 4 | 16, igemm_code(32, 256, 128, 2)),
-    (NEVER_TILE | 8 | 4 | 32, igemm_code(32, 256, 128, 3)),
-    (NEVER_TILE | 8 | 4 | 1, igemm_code(32, 256, 128, 2, 0)),
-    (NEVER_TILE | 256, 256),                              # conv_igemm256_kernel<false>
-    (NEVER_TILE | 256 | 1024, 256 + 1024),                # conv_igemm256_kernel<true> (staggered wave groups)
-    (NEVER_TILE | 256 | 1024 | 2048, 256 + 1024),
-] + [((cfg << 12) | (tiny << 16), 100 + cfg) for cfg in range(1, 7) for tiny in (0, 1)] + [
-    # stream-K form (variant bit 27), 24 work-groups: shares begin and end inside tiles, partial tiles are handed over
-    ((cfg << 12) | (1 << 16) | (1 << 27), 500 + cfg) for cfg in (1, 2, 3, 4)] + [
-    (1 << 24, 300), ((1 << 24) | (1 << 16), 300),         # conv_halo.hip (halo-staged 3x3), 12 tiles / 8 work-groups
-]
 
 
 @pytest.mark.parametrize("variant,code", CONV_VARIANTS)
@@ -153,7 +95,7 @@ def test_conv_forced_variant_fwd_bwd(F, variant, code):
 def test_conv_halo_64_channel_tiles(F, cin, cout, tiny):
     """conv_halo_kernel<16, 32, 3, 1> (<= 64 output channels: all eight waves along the pixels, four pixel fragments each):
     ragged patches in both directions and a ragged channel tail, statistics / bias + ReLU, forward and both gradients vs fp32;
-    bit 17 puts the same launch on the 128-channel tiles (code 300) and the two must agree to the bit."""
+    U2_CV_HALO_TILE128 puts the same launch on the 128-channel tiles (K_HALO) and the two must agree to the bit."""
     g = torch.Generator().manual_seed(cin * 100 + cout + tiny)
     x = bf(torch.randn((2, cin, 37, 45), generator=g))
     w = (torch.randn((cout, cin, 3, 3), generator=g) / (cin * 9) ** 0.5).requires_grad_(True)
@@ -164,15 +106,15 @@ def test_conv_halo_64_channel_tiles(F, cin, cout, tiny):
     yr.backward(gy)
     xd = nhwc(x).requires_grad_(True)
     wd = w.detach().to(DEV).requires_grad_(True)
-    with forced(conv=(1 << 24) | (tiny << 16)):
+    with forced(conv=HALO | (TINY if tiny else 0)):
         y, stats = F._Conv2dFn.apply(xd, wd, None, 1, 1, False, True)
-        assert last_kernel() == 301, last_kernel()
+        assert last_kernel() == K.K_HALO_N64, last_kernel()
         yb = F.conv2d(nhwc(x), w.detach().to(DEV), bias.to(DEV), 1, 1, relu=True)
-        assert last_kernel() == 301
+        assert last_kernel() == K.K_HALO_N64
         y.backward(nhwc(gy))
-    with forced(conv=(1 << 24) | (1 << 17) | (tiny << 16)):
+    with forced(conv=HALO | K.CV_HALO_TILE128 | (TINY if tiny else 0)):
         y128, stats128 = F._Conv2dFn.apply(nhwc(x), wd.detach(), None, 1, 1, False, True)
-        assert last_kernel() == 300, last_kernel()
+        assert last_kernel() == K.K_HALO, last_kernel()
     assert torch.equal(y, y128)
     yy = nchw(y, cout)
     assert rel_err(yy, yr.detach()) < ULP
@@ -183,9 +125,6 @@ def test_conv_halo_64_channel_tiles(F, cin, cout, tiny):
     assert rel_err(nchw(yb, cout), ref_b) < ULP
     assert rel_err(nchw(xd.grad, cin), xr.grad) < ULP
     assert rel_err(wd.grad.cpu(), w.grad) < WG_TOL
-
-
-STREAM = 1 << 17   # conv_stream.hip wherever it applies; bit 16: 8 work-groups per 256-channel block (many tiles per group)
 
 
 @pytest.mark.parametrize("tiny", [0, 1])
@@ -201,14 +140,14 @@ def test_conv_stream_kernel(F, cin, cout, tiny):
     x = bf(torch.randn((b, cin, h, w_), generator=g))
     w = (torch.randn((cout, cin, 1, 1), generator=g) / cin ** 0.5).requires_grad_(True)
     bias = torch.randn(cout, generator=g) * 0.1
-    code = 700 + (cin // 32) * 10 + (0 if cout > 128 else 1 if cout > 64 else 2)
+    code = stream_code(cin, cout)
     xr = x.clone().requires_grad_(True)
     yr = TF.conv2d(xr, bf(w), None)
     gy = bf(torch.randn(yr.shape, generator=g))
     yr.backward(gy)
     xd = nhwc(x).requires_grad_(True)
     wd = w.detach().to(DEV).requires_grad_(True)
-    with forced(conv=STREAM | (tiny << 16)):
+    with forced(conv=STREAM | (TINY if tiny else 0)):   # TINY: 8 work-groups per 256-channel block
         y, stats = F._Conv2dFn.apply(xd, wd, None, 1, 0, False, True)
         assert last_kernel() == code, (last_kernel(), code)
         yb = F.conv2d(nhwc(x), w.detach().to(DEV), bias.to(DEV), 1, 0, relu=True)
@@ -223,10 +162,7 @@ def test_conv_stream_kernel(F, cin, cout, tiny):
     assert rel_err(nchw(xd.grad, cin), xr.grad) < ULP
 
 
-@pytest.mark.parametrize("variant,code", [(NEVER_TILE, igemm_code(64, 256, 64, 2)), (NEVER_TILE | 1, igemm_code(64, 256, 64, 2, 0)),
-                                          (NEVER_TILE | 32, igemm_code(64, 256, 64, 3)), (NEVER_TILE | 48, igemm_code(64, 256, 64, 4)),
-                                          (NEVER_TILE | 4, igemm_code(32, 256, 64, 4)), (NEVER_TILE | 4 | 16, igemm_code(32, 256, 64, 2)),
-                                          (NEVER_TILE | 4 | 32, igemm_code(32, 256, 64, 3)), (NEVER_TILE | 4 | 1, igemm_code(32, 256, 64, 2, 0))])
+@pytest.mark.parametrize("variant,code", NARROW_VARIANTS)
 def test_conv_narrow_tile_variants(F, variant, code):
     """The 256 x 64 tile family (layers with <= 64 output channels): 1x1 512 -> 40 with bias and ReLU."""
     g = torch.Generator().manual_seed(5 + variant % 97)
@@ -241,10 +177,7 @@ def test_conv_narrow_tile_variants(F, variant, code):
     assert float(y[..., 40:].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("variant,code", [(0, 2003), (1, 2001), (2, 2002), (3, 2000), (64, 2103), (128, 2003), (256, 2256),
-                                          (256 | 64, 2356), (16, 2003), (32, 2003),
-                                          # bit 17: partial tiles + wgrad_reduce_kernel wherever there are >= 2 pixel splits, bit 16: atomics
-                                          (131072, 2003), (131072 | 256, 2256), (131072 | 64, 2103), (65536, 2003)])
+@pytest.mark.parametrize("variant,code", WGRAD_TAP_VARIANTS)
 def test_wgrad_forced_variants(F, variant, code):
     """conv_wgrad_kernel<GLDS, TR> (all four), the XCD-grouped launch and conv_wgrad256_kernel on 3x3 s1 128 -> 136 (the plain
     layout) and on 1x1 (the direct-into-arena layout), vs fp32."""
@@ -263,14 +196,11 @@ def test_wgrad_forced_variants(F, variant, code):
         assert rel_err(wd.grad.cpu(), w.grad) < WG_TOL
 
 
-WS_FORCE, WS_TINY = 1 << 18, 1 << 20
-
-
 @pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4])
 @pytest.mark.parametrize("tiny", [0, 1])
 def test_wgrad_stream_kernel(F, cfg, tiny):
     """wgrad_stream_kernel (1x1 / stride 1: a persistent work-group per pixel range holds a whole block of dW in registers),
-    every block configuration forced (U2_WGRAD_VARIANT bit 18, bits 21-23) with 8 pixel ranges and with the full grid, on maps
+    every block configuration forced (U2_WG_STREAM_FORCE, U2_WG_STREAM_CFG) with 8 pixel ranges and with the full grid, on maps
     whose pixel count is not a multiple of the 32-pixel step, with channel tails on both operands (40, 104, 136, 264, 520: blocks
     tiled over N and over C, half-empty blocks, 8-channel remainders) and a 5-pixel map (ranges without a step), vs fp32.  The 1x1
     weight gradient goes through u2_conv_wgrad_into (the arena layout [N][Cin]) whenever the weight owns a gradient slot."""
@@ -283,22 +213,22 @@ def test_wgrad_stream_kernel(F, cfg, tiny):
         gy = bf(torch.randn(yr.shape, generator=g))
         yr.backward(gy)
         wd = w.detach().to(DEV).requires_grad_(True)
-        with forced(wgrad=WS_FORCE | (WS_TINY if tiny else 0) | (cfg << 21)):
+        with forced(wgrad=ws_variant(cfg, tiny)):
             y, _ = F._Conv2dFn.apply(nhwc(x), wd, None, 1, 0, False, False)
             y.backward(nhwc(gy))
-            assert last_kernel() // 100 == 27, (cfg, last_kernel())
+            assert last_kernel() // 100 == K.K_WGRAD_STREAM // 100, (cfg, last_kernel())
             if cfg:
-                assert last_kernel() == 2700 + cfg
+                assert last_kernel() == K.K_WGRAD_STREAM + cfg
         assert rel_err(wd.grad.cpu(), w.grad) < WG_TOL, (cfg, tiny, cin, cout)
 
 
 @pytest.mark.parametrize("name,b,h,w,cin,cout,code", [
-    ("res2 conv3 1x1 64->256 @200x336", 16, 200, 336, 64, 256, 2701),
-    ("res2 conv1 1x1 256->64 @200x336", 16, 200, 336, 256, 64, 2702),
-    ("res3 conv3 1x1 128->512 @100x168", 16, 100, 168, 128, 512, 2703),
-    ("fpn lateral2 1x1 256->256 @200x336", 16, 200, 336, 256, 256, 2704),
-    ("semantic predictor 1x1 128->28 @200x336", 16, 200, 336, 128, 28, 2702),
-    ("res4 conv3 1x1 256->1024 @50x84 (stays on the tile kernels)", 16, 50, 84, 256, 1024, 2256),
+    ("res2 conv3 1x1 64->256 @200x336", 16, 200, 336, 64, 256, K.K_WGRAD_STREAM + 1),
+    ("res2 conv1 1x1 256->64 @200x336", 16, 200, 336, 256, 64, K.K_WGRAD_STREAM + 2),
+    ("res3 conv3 1x1 128->512 @100x168", 16, 100, 168, 128, 512, K.K_WGRAD_STREAM + 3),
+    ("fpn lateral2 1x1 256->256 @200x336", 16, 200, 336, 256, 256, K.K_WGRAD_STREAM + 4),
+    ("semantic predictor 1x1 128->28 @200x336", 16, 200, 336, 128, 28, K.K_WGRAD_STREAM + 2),
+    ("res4 conv3 1x1 256->1024 @50x84 (stays on the tile kernels)", 16, 50, 84, 256, 1024, K.K_WGRAD256),
 ])
 def test_wgrad_stream_full_shapes_auto_dispatch(F, name, b, h, w, cin, cout, code):
     """Benchmark-shape 1x1 weight gradients through the automatic dispatch: the streaming kernel takes the stride-4 / stride-8
@@ -322,10 +252,10 @@ def test_wgrad_stream_full_shapes_auto_dispatch(F, name, b, h, w, cin, cout, cod
 def test_fused_1x1_backward(F, tiny):
     """u2_conv1x1_bwd_fused (wgrad_stream_kernel<.., DG>): the data gradient and the weight gradient of a 1x1 / stride-1 conv in
     one pass over the output gradient - reached from _Conv2dFn.backward when the weight owns an arena slot (solver.FlatSGD) -
-    forced on small maps (U2_WDGRAD_VARIANT bit 0; the automatic rule takes >= 200 000 pixels), both block shapes (all of N <= 256
+    forced on small maps (U2_WD_FORCE; the automatic rule takes >= 200 000 pixels), both block shapes (all of N <= 256
     by 64 input channels; N <= 512 by 64 in two c-tiles), pixel counts that are no multiple of the 32-pixel step, channel tails
     on both sides, vs fp32: dx at one bf16 step, dW like the other weight-gradient kernels; the padded input channels of dx are
-    written as zeros.  The same module without the fused launch (bit 2: never) gives the same gradients to fp32 summation order."""
+    written as zeros.  The same module without the fused launch (U2_WD_NEVER) gives the same gradients to fp32 summation order."""
     from u2seg_amd.layers.modules import Conv2d
     from u2seg_amd.solver import FlatSGD
 
@@ -333,8 +263,8 @@ def test_fused_1x1_backward(F, tiny):
     g = torch.Generator().manual_seed(40 + tiny)
     try:
         F.FUSED_BWD_MIN_PIXELS = 0
-        for (b, cin, cout, h, w_, code) in ((1, 64, 256, 37, 29, 2751), (2, 40, 200, 33, 21, 2751), (1, 128, 512, 19, 45, 2752),
-                                           (1, 72, 264, 45, 23, 2752)):
+        for (b, cin, cout, h, w_, code) in ((1, 64, 256, 37, 29, K.K_WDGRAD + 1), (2, 40, 200, 33, 21, K.K_WDGRAD + 1), (1, 128, 512, 19, 45, K.K_WDGRAD + 2),
+                                           (1, 72, 264, 45, 23, K.K_WDGRAD + 2)):
             x = bf(torch.randn((b, cin, h, w_), generator=g))
             w = torch.randn((cout, cin, 1, 1), generator=g) / cin ** 0.5
             xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
@@ -342,7 +272,7 @@ def test_fused_1x1_backward(F, tiny):
             gy = bf(torch.randn(yr.shape, generator=g))
             yr.backward(gy)
             got = {}
-            for mode, variant in (("fused", 1 | (2 if tiny else 0)), ("separate", 4)):
+            for mode, variant in (("fused", K.WD_FORCE | (K.WD_TINY if tiny else 0)), ("separate", K.WD_NEVER)):
                 conv = Conv2d(cin, cout, 1, bias=False).to(DEV)
                 with torch.no_grad():
                     conv.weight.copy_(w.to(DEV))
@@ -407,7 +337,7 @@ def test_fused_1x1_backward_with_batch_norm_apply(F, tail):
     placeholder from _BatchNormActFn.backward to _Conv2dFn.backward.  Against the same module with the step as its own launch
     (F.LAZY_BN_APPLY False, the fused launch 2751 on the stored dy): the input gradient to the few bf16 roundings of dy that the
     atomically summed coefficients flip between two runs (bit for bit on fixed coefficients: tests/native/selftest wdgrad_bn), dW and
-    dgamma / dbeta to fp32 summation order, the residual's gradient identical.  Third leg: the deferral is taken but the fused launcher declines (variant bit 2) -
+    dgamma / dbeta to fp32 summation order, the residual's gradient identical.  Third leg: the deferral is taken but the fused launcher declines (U2_WD_NEVER) -
     the conv materialises dy with u2_norm_bwd_apply and takes the separate launches; same gradients."""
     from u2seg_amd.layers.modules import BatchNorm2d, Conv2d
     from u2seg_amd.solver import FlatSGD
@@ -437,13 +367,13 @@ def test_fused_1x1_backward_with_batch_norm_apply(F, tail):
                 opt.zero_grad()
                 xd = nhwc(x).requires_grad_(True)
                 rd = nhwc(res).requires_grad_(True) if tail else None
-                os.environ["U2_WDGRAD_VARIANT"] = "1"
+                os.environ["U2_WDGRAD_VARIANT"] = str(K.WD_FORCE)
                 out = conv(xd, residual=rd, relu=tail)
                 if mode == "declined":
-                    os.environ["U2_WDGRAD_VARIANT"] = "4"
+                    os.environ["U2_WDGRAD_VARIANT"] = str(K.WD_NEVER)
                 out.backward(nhwc(gy))
                 if mode == "in the conv":
-                    assert last_kernel() == 2761, (cin, cout, last_kernel())
+                    assert last_kernel() == K.K_WDGRAD_BN + 1, (cin, cout, last_kernel())
                 F.assert_no_deferred_gradients()
                 F.join_all_streams()
                 got[mode] = (xd.grad.clone(), conv.weight.grad.detach().float().clone(), conv.norm.weight.grad.detach().clone(),
@@ -479,7 +409,7 @@ def test_deferred_batch_norm_gradient_guards(F):
     g = torch.Generator().manual_seed(5)
     try:
         F.FUSED_BWD_MIN_PIXELS = 0
-        os.environ["U2_WDGRAD_VARIANT"] = "1"
+        os.environ["U2_WDGRAD_VARIANT"] = str(K.WD_FORCE)
         conv = Conv2d(64, 256, 1, bias=False, norm=BatchNorm2d(256, sync=False)).to(DEV)
         conv.train()
         opt = FlatSGD(conv, lr=0.1)
@@ -503,7 +433,7 @@ def test_deferred_batch_norm_gradient_guards(F):
         opt.zero_grad()
         xd = x.clone().requires_grad_(True)
         conv(xd).float().sum().backward()
-        assert last_kernel() == 2761
+        assert last_kernel() == K.K_WDGRAD_BN + 1
         F.assert_no_deferred_gradients()
         F.join_all_streams()
         assert float(xd.grad.float().abs().max()) >= 0 and torch.isfinite(conv.weight.grad).all()
@@ -529,7 +459,7 @@ def test_fused_1x1_backward_full_shape_auto(F):
     with forced():
         y = conv(x)
         y.backward(gy)
-        assert last_kernel() == 2751, last_kernel()
+        assert last_kernel() == K.K_WDGRAD + 1, last_kernel()
     F.join_all_streams()
     wq = conv.weight.detach().reshape(cout, cin).bfloat16().float()
     ref_dw = gy.reshape(-1, cout).float().t() @ x.detach().reshape(-1, cin).float()
@@ -539,13 +469,13 @@ def test_fused_1x1_backward_full_shape_auto(F):
     assert rel_err(x.grad.reshape(-1, cin)[idx].float(), ref_dx) < ULP
 
 
-@pytest.mark.parametrize("variant", [4096, 4096 | (1 << 14), 4096 | (1 << 17), 4096 | (1 << 17) | (1 << 14), 4096 | (1 << 16)])
+@pytest.mark.parametrize("variant", WGRAD_HALO_VARIANTS)
 @pytest.mark.parametrize("shape", [(2, 64, 64, 14, 14), (1, 128, 136, 13, 17), (3, 96, 200, 25, 42), (2, 64, 256, 40, 70),
                                    (2, 32, 8, 3, 11), (1, 32, 72, 5, 101)])
 def test_wgrad_halo_kernel(F, variant, shape):
     """conv_wgrad_halo_kernel (3x3 / stride 1 / pad 1, all nine taps per work-group over padded pixel coordinates) forced on
     small maps - every row wrap count (W + 1 < 16, < 32, >= 32), partial channel tiles, one to many steps per work-group -
-    vs fp32, with the atomic epilogue (bit 16) and with partial blocks + wgrad_halo_reduce_kernel (bit 17); the automatic
+    vs fp32, with the atomic epilogue (U2_WG_ATOMICS) and with partial blocks + wgrad_halo_reduce_kernel (U2_WG_PARTIALS_FORCE); the automatic
     dispatch takes it from ~400 positions per work-group (test_wgrad_halo_mid_size_shapes_auto_dispatch)."""
     b, cin, cout, h, w_ = shape
     g = torch.Generator().manual_seed(h * 100 + w_ + variant)
@@ -558,7 +488,7 @@ def test_wgrad_halo_kernel(F, variant, shape):
     with forced(wgrad=variant):
         y, _ = F._Conv2dFn.apply(nhwc(x), wd, None, 1, 1, False, False)
         y.backward(nhwc(gy))
-        assert last_kernel() == 2900, last_kernel()
+        assert last_kernel() == K.K_WGRAD_HALO, last_kernel()
     assert rel_err(wd.grad.cpu(), w.grad) < WG_TOL
 
 
@@ -584,7 +514,7 @@ def test_wgrad_halo_mid_size_shapes_auto_dispatch(F, name, b, h, w, cin, cout):
         for _ in range(2):
             y, _ = F._Conv2dFn.apply(x, wd, None, 1, 1, False, False)
             y.backward(gy)
-            assert last_kernel() == 2900, (name, last_kernel())
+            assert last_kernel() == K.K_WGRAD_HALO, (name, last_kernel())
     n0, c0 = cout - 16, cin // 2
     xs = x[..., c0:c0 + 16].float().permute(0, 3, 1, 2)
     gs = gy[..., n0:n0 + 16].float().permute(0, 3, 1, 2)
@@ -615,17 +545,17 @@ def _sampled_conv_ref(x, w, bias, pos, pad):
 
 FULL_SHAPES = [
     # name, B, H, W, cin, cout, k, pad, relu+bias, expected forward kernel under the automatic dispatch
-    ("fpn_output2 3x3 256->256 @200x336", 16, 200, 336, 256, 256, 3, 1, False, 300),   # conv_halo.hip
-    ("rpn conv 3x3 256->256 @100x168 bias relu", 16, 100, 168, 256, 256, 3, 1, True, 501),   # stream-K form of configuration 1
-    ("res3 conv2 3x3 128->128 @100x168", 16, 100, 168, 128, 128, 3, 1, False, 300),
-    ("res2 conv2 3x3 64->64 @200x336", 16, 200, 336, 64, 64, 3, 1, False, 301),   # 64-channel tiles
-    ("res4 conv3 1x1 256->1024 @50x84", 16, 50, 84, 256, 1024, 1, 0, False, 780),            # conv_stream.hip
-    ("res2 conv3 1x1 64->256 @200x336", 16, 200, 336, 64, 256, 1, 0, False, 720),
-    ("res2 conv1 1x1 256->64 @200x336", 16, 200, 336, 256, 64, 1, 0, False, 782),
-    ("res3 conv3 1x1 128->512 @100x168", 16, 100, 168, 128, 512, 1, 0, False, 740),
-    ("res5 conv1 1x1 2048->512 @25x42", 16, 25, 42, 2048, 512, 1, 0, False, 502),            # 132 tiles: stream-K
-    ("fpn_output4 3x3 256->256 @50x84", 16, 50, 84, 256, 256, 3, 1, False, 501),            # 263 tiles: stream-K
-    ("mask head 3x3 256->256 @261x14x14 bias relu", 261, 14, 14, 256, 256, 3, 1, True, 101),
+    ("fpn_output2 3x3 256->256 @200x336", 16, 200, 336, 256, 256, 3, 1, False, K.K_HALO),   # conv_halo.hip
+    ("rpn conv 3x3 256->256 @100x168 bias relu", 16, 100, 168, 256, 256, 3, 1, True, K.K_STREAMK + 1),   # stream-K form of configuration 1
+    ("res3 conv2 3x3 128->128 @100x168", 16, 100, 168, 128, 128, 3, 1, False, K.K_HALO),
+    ("res2 conv2 3x3 64->64 @200x336", 16, 200, 336, 64, 64, 3, 1, False, K.K_HALO_N64),   # 64-channel tiles
+    ("res4 conv3 1x1 256->1024 @50x84", 16, 50, 84, 256, 1024, 1, 0, False, stream_code(256, 1024)),            # conv_stream.hip
+    ("res2 conv3 1x1 64->256 @200x336", 16, 200, 336, 64, 256, 1, 0, False, stream_code(64, 256)),
+    ("res2 conv1 1x1 256->64 @200x336", 16, 200, 336, 256, 64, 1, 0, False, stream_code(256, 64)),
+    ("res3 conv3 1x1 128->512 @100x168", 16, 100, 168, 128, 512, 1, 0, False, stream_code(128, 512)),
+    ("res5 conv1 1x1 2048->512 @25x42", 16, 25, 42, 2048, 512, 1, 0, False, K.K_STREAMK + 2),            # 132 tiles: stream-K
+    ("fpn_output4 3x3 256->256 @50x84", 16, 50, 84, 256, 256, 3, 1, False, K.K_STREAMK + 1),            # 263 tiles: stream-K
+    ("mask head 3x3 256->256 @261x14x14 bias relu", 261, 14, 14, 256, 256, 3, 1, True, K.K_TILE + 1),
 ]
 
 
@@ -668,7 +598,7 @@ def test_conv_fpn_output2_backward_full_shape(F):
     with forced():
         y, _ = F._Conv2dFn.apply(x, wd, None, 1, 1, False, True)
         y.backward(gy)
-        assert last_kernel() == 2900, last_kernel()  # the wgrad ran last: nine-tap halo kernel (wgrad_halo.hip)
+        assert last_kernel() == K.K_WGRAD_HALO, last_kernel()  # the wgrad ran last: nine-tap halo kernel (wgrad_halo.hip)
     # data gradient = conv of gy with the flipped, transposed filter
     wflip = bf(wt).flip(2, 3).permute(1, 0, 2, 3).contiguous().to(DEV)
     pos = torch.stack([torch.randint(0, b, (2048,), generator=g), torch.randint(0, h, (2048,), generator=g),
@@ -690,8 +620,8 @@ def test_conv_fpn_output2_backward_full_shape(F):
             assert float((got_w - ref_w).abs().max() / ref_w.abs().max()) < WG_TOL, (kh, kw)
 
 
-@pytest.mark.parametrize("shape", [(4, 200, 169, 64, 256, 104), (2, 37, 41, 64, 256, None), (1, 90, 70, 512, 2048, 104),
-                                   (3, 20, 24, 256, 1024, 104)])
+@pytest.mark.parametrize("shape", [(4, 200, 169, 64, 256, K.K_TILE + 4), (2, 37, 41, 64, 256, None),
+                                   (1, 90, 70, 512, 2048, K.K_TILE + 4), (3, 20, 24, 256, 1024, K.K_TILE + 4)])
 def test_conv_accumulating_epilogue(F, shape):
     """conv_tile_kernel<4, 1, 3, ACC>: out = relu(bf16(conv1x1(x) + bias) + out) in place - the residual tail of a bottleneck at
     inference (backbone/resnet.py:204-210 with the fixed-statistics norm folded into the conv) - vs fp32, with partial tiles;
@@ -714,7 +644,7 @@ def test_conv_accumulating_epilogue(F, shape):
 def test_streamk_region_rule(F):
     """Where the product path lets a convolution take the stream-K form (layers/functional.py:streamk_region): inside the region
     (the bottom-up backbone) the library's fill rule decides - fpn_output4's shape takes configuration 501, forward and data
-    gradient -, outside it the call carries variant bit 28 and runs whole tiles (101) while the branch streams are on, and the
+    gradient -, outside it the call carries U2_CV_STREAMK_FORBID and runs whole tiles (K_TILE + 1) while the branch streams are on, and the
     rule is off when they are off (set_stream_overlap(False)) or U2_STREAMK_EVERYWHERE=1; results agree either way."""
     g = torch.Generator().manual_seed(5)
     b, h, w, c = 16, 50, 84, 256
@@ -725,9 +655,9 @@ def test_streamk_region_rule(F):
         with F.streamk_region():
             xin = x.clone().requires_grad_(True)
             y_in, _ = F._Conv2dFn.apply(xin, wt, None, 1, 1, False, False)
-            assert last_kernel() == 501, last_kernel()
+            assert last_kernel() == K.K_STREAMK + 1, last_kernel()
         y_out, _ = F._Conv2dFn.apply(x, wt, None, 1, 1, False, False)
-        assert last_kernel() == 101, last_kernel()
+        assert last_kernel() == K.K_TILE + 1, last_kernel()
         # the backward pass of a layer created inside the region keeps the permission outside of it
         y_in.backward(torch.ones_like(y_in))
         F.join_all_streams()
@@ -735,12 +665,12 @@ def test_streamk_region_rule(F):
         F.set_stream_overlap(False)
         try:
             F._Conv2dFn.apply(x, wt, None, 1, 1, False, False)
-            assert last_kernel() == 501, last_kernel()
+            assert last_kernel() == K.K_STREAMK + 1, last_kernel()
         finally:
             F.set_stream_overlap(True)
         os.environ["U2_STREAMK_EVERYWHERE"] = "1"
         F._Conv2dFn.apply(x, wt, None, 1, 1, False, False)
-        assert last_kernel() == 501, last_kernel()
+        assert last_kernel() == K.K_STREAMK + 1, last_kernel()
         assert float((y_in.float() - y_out.float()).abs().max()) <= 2 ** -7 * float(y_out.float().abs().max())
     finally:
         os.environ.pop("U2_STREAMK_EVERYWHERE", None)

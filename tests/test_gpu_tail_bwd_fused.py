@@ -27,13 +27,14 @@ epilogue of conv_stream.hip; U2_TAIL_BWD_FUSE in layers/functional.py).
 import pytest
 import torch
 
+from tests.conv_variants import K
 from tests.test_gpu_norm_full_size import DEV, EPS, MOM, NormRef, U, check_backward, gen, randn_bf, reduce_depth
 
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
 F64 = torch.float64
-FORCED_TINY = (1 << 17) | (1 << 16)   # conv_stream.hip: lift the size rule, 8 work-groups per channel block only
+FORCED_TINY = K.CV_STREAM_FORCE | K.CV_TINY_GRID   # conv_stream.hip: lift the size rule, 8 work-groups per channel block only
 # (TM pixels per tile, waves along the pixels, waves per work-group) of the three tail instantiations, by reduction width C
 TAIL_CFG = {64: (128, 1, 4), 128: (64, 1, 4), 256: (64, 2, 8)}
 
@@ -104,7 +105,7 @@ def test_tail_kernel_against_two_launches(H, c, n, m):
         # the two launches
         g1 = torch.empty((m, n), dtype=BF16, device=DEV)
         H.call("u2_conv_igemm", dy, wt, g1, None, None, b, h, w, c, c, h, w, n, n, 1, 1, 0, 0, 1, 1, 0, 0, FORCED_TINY)
-        assert 700 <= H.call_nostream("u2_conv_last_kernel") < 800, "the data gradient did not run on the streaming kernel"
+        assert K.K_STREAM <= H.call_nostream("u2_conv_last_kernel") < K.K_STREAM + 100, "the data gradient did not run on the streaming kernel"
         dz_ref = torch.empty_like(g1)
         sums_ref = torch.zeros((2, n), device=DEV)
         H.call("u2_norm_bwd_reduce", g1, bits, y, mean, invstd, sums_ref, 1, m, n, n, 1, None, None, g2, dz_ref, None, 1)
@@ -113,7 +114,7 @@ def test_tail_kernel_against_two_launches(H, c, n, m):
         sums = torch.zeros((2, n), device=DEV)
         rc = H.call_status("u2_conv_dgrad_tail", dy, wt, g2, y, bits, mean, invstd, dz, sums, b, h, w, c, c, n, n, FORCED_TINY)
         assert rc == 0, "u2_conv_dgrad_tail declined a served shape"
-        assert H.call_nostream("u2_conv_last_kernel") == 705 + c // 32 * 10
+        assert H.call_nostream("u2_conv_last_kernel") == K.K_STREAM + K.K_STREAM_TAIL + c // 32 * 10
         torch.cuda.synchronize()
         assert torch.equal(dz, dz_ref), "%s: dz differs from the two-launch path in %d elements" % (mask_mode, int((dz != dz_ref).sum()))
         if mask_mode == "zeros":

@@ -49,6 +49,36 @@ def declared_symbols(header_path=_HEADER):
     return out
 
 
+_INT = r"(0[xX][0-9a-fA-F]+|[0-9]+)[uU]?"
+_CONST_VALUE = re.compile(r"(?:%s|\(\s*%s\s*<<\s*%s\s*\))$" % (_INT, _INT, _INT))
+
+
+def constants(header_path=_HEADER):
+    """Parse the `#define U2_NAME value` lines of include/u2seg_hip.h -> {name: int}: the variant words' fields and the
+    u2_conv_last_kernel codes.  A value is an integer literal or (literal << literal); anything else is an error, nothing is
+    evaluated."""
+    text = open(header_path).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    out = {}
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(U2_\w+)[ \t]+(.*?)[ \t]*$", text, flags=re.M):
+        v = _CONST_VALUE.match(m.group(2))
+        if not v:
+            raise ValueError("unsupported constant in header: " + m.group(0).strip())
+        lit, base, shift = v.groups()
+        out[m.group(1)] = int(lit, 0) if lit is not None else int(base, 0) << int(shift, 0)
+    return out
+
+
+class _Constants:
+    """The header's constants as attributes without the U2_ prefix: K.CV_STREAMK_FORBID."""
+
+    def __init__(self, table):
+        self.__dict__.update((k[3:], v) for k, v in table.items())
+
+
+K = _Constants(constants())
+
+
 def lib_path():
     return _LIB_PATH
 

@@ -2,6 +2,7 @@
 // conv_stream.hip, wgrad_halo.hip, wgrad_stream.hip).
 #pragma once
 #include "common.h"
+#include "conv_variant.h"
 
 namespace u2conv {
 
@@ -30,9 +31,9 @@ struct ConvArgs {
   // slot and one flag per work-group, device memory owned by the library (per stream)
   float* sk_ws;
   int* sk_flags;
-  int abl;                 // conv_halo.hip measurement switches (tests/native/selftest bench2 only; 0 in production):
-                           // bit 0 no output stores, bit 1 no BN statistics, bit 2 no epilogue at all, bit 3 `nt` stores for outputs > 160 MB
-                           // (rounds 1-2 default; round 3 measured it 29-38 % SLOWER on the write-heavy 1x1 layers, -0.55 ms per step)
+  int abl;                 // measurement switches (tests/native/selftest bench2 only; 0 in production): the U2_CV_ABL field of the
+                           // conv word (include/u2seg_hip.h), bit k here = bit U2_CV_ABL_SHIFT + k there.  Bit 3, `nt` stores, was
+                           // the default of rounds 1-2; round 3 measured it 29-38 % SLOWER on the write-heavy 1x1 layers
 };
 
 // Tile shapes: (TM pixels x TN output channels) = 128x128 (default) or 256x64 (layers with <= 64 output channels,
@@ -70,22 +71,20 @@ union Frag {
 };
 
 // Which kernel the most recent u2_conv_igemm / u2_conv_wgrad launch selected (u2_conv_last_kernel, a test / debugging aid):
-//   conv_tile_kernel configuration k -> 100 + k;  conv_igemm256_kernel -> 256 (+ 1024 staggered);
-//   conv_igemm_kernel<BK, GLDS, TM, TN, NST> -> 1000000 + BK * 10000 + (TM / 64) * 1000 + (TN / 64) * 100 + NST * 10 + GLDS;
-//   conv_wgrad_kernel<GLDS, TR> -> 2000 + GLDS * 2 + TR (+ 100 when XCD-grouped);  conv_wgrad256_kernel -> 2256 (+ 100).
+// the U2_K_ codes of include/u2seg_hip.h.
 extern int g_last_conv_kernel;
 
 // conv_tile.hip: persistent 64(ch) x 128(px)-per-wave tile kernels; returns 1 when it took the launch, 0 when the shape is
 // not served (caller falls back to conv_igemm_kernel), -1000 - hipError_t on a launch failure.
-int launch_conv_tile(ConvArgs& a, int N, int C, int variant, hipStream_t s);
+int launch_conv_tile(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s);
 
 // conv_halo.hip: 3x3 / stride 1 / pad 1 with the input halo of a 16 x 32 pixel patch staged once per 32-channel slab; same
 // return convention as launch_conv_tile.  g_last_conv_kernel code: 300.
-int launch_conv_halo(ConvArgs& a, int N, int C, int variant, hipStream_t s);
+int launch_conv_halo(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s);
 
 // conv_stream.hip: 1x1 / stride 1 layers with <= 256 input channels - weights resident in registers, whole pixel rows streamed
 // through an LDS ring; same return convention as launch_conv_tile.  g_last_conv_kernel code: 7xx.
-int launch_conv_stream(ConvArgs& a, int N, int C, int variant, hipStream_t s);
+int launch_conv_stream(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s);
 
 // conv_stream.hip, tail mode: the same launch as the data gradient of a residual block's conv1, with the backward reduce of the
 // previous block's tail in the epilogue.  out = dz = mask * bf16(bf16(conv) + g2), stats[0][n] += sum dz,
@@ -97,7 +96,7 @@ struct TailArgs {
   const float* mean = nullptr;
   const float* invstd = nullptr;
 };
-int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, int variant, hipStream_t s);
+int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, const ConvVariant& v, hipStream_t s);
 
 // wgrad_halo.hip: 3x3 / stride 1 / pad 1 weight gradient, all nine taps per work-group with the input halo in LDS; same
 // return convention as launch_conv_tile.  g_last_conv_kernel code: 2900.
@@ -114,7 +113,7 @@ int launch_wgrad_stream(const bf16_t* x, const bf16_t* dy, float* dw, long long 
 
 int launch_wdgrad_stream(const bf16_t* x, const bf16_t* dy, const bf16_t* wt, bf16_t* dx, float* dw, long long dw_sn, int dw_sc,
                          int n_valid, int c_valid, const bf16_t* zero, int M, int C, int x_ld, int N, int dy_ld, int wt_ld,
-                         int dx_ld, int force, int tiny, hipStream_t s, const bf16_t* yn = nullptr, const float* k1 = nullptr,
+                         int dx_ld, const FusedBwdVariant& v, hipStream_t s, const bf16_t* yn = nullptr, const float* k1 = nullptr,
                          const float* k2 = nullptr, const float* k3 = nullptr);
 
 // Library-owned device scratch (conv_igemm.hip), one block per (device, stream, kind): the kernels of a stream run one after

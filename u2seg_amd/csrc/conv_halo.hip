@@ -41,7 +41,7 @@ constexpr int LDS_BYTES = WBASE + WR * WSLOT;  // 155648
 
 // OPT bit 0: no s_setprio around the MFMA runs, bit 1: no sched_barrier fences between the MFMA runs and the LDS reads / staging.
 // Measured (profiles/r03_conv_halo_sched.txt): without both the kernel is 4 % faster (fpn_output2 1208 -> 1260 TFLOP/s), either
-// one alone +2 % / -1 %: the default is 3; variant bits 29-30 select OPT ^ 3 (so 0 there = the default).
+// one alone +2 % / -1 %: the default is 3; the conv word's U2_CV_HALO_SCHED field selects OPT ^ 3 (so 0 there = the default).
 // CW: waves along the output channels (64 each).  CW = 2: 128-channel tiles, wave tile 64 ch x 128 px (8 pixel fragments).  CW = 1
 // (round 4): 64-channel tiles for the layers with <= 64 output channels (res2 conv2 and its data gradient) - all eight waves along
 // the pixels, wave tile 64 ch x 64 px (4 fragments): no half of the MFMA and epilogue work spent on absent channels.
@@ -371,15 +371,15 @@ double patch_fill(int H, int W, int ph, int pw) {
 
 }  // namespace
 
-// Serves 3x3 / stride 1 / pad 1 launches (C % 32 == 0, N % 8 == 0, not accumulating).  variant bit 24: always where it applies,
-// bit 25: never; otherwise automatic, from tests/native/selftest bench2 (profiles/r03_conv_halo.txt):
+// Serves 3x3 / stride 1 / pad 1 launches (C % 32 == 0, N % 8 == 0, not accumulating).  Automatic choice, from
+// tests/native/selftest bench2 (profiles/r03_conv_halo.txt):
 // the halo kernel wins wherever its patches are reasonably full - the stride-4 maps (200 x 336: 92 % full, +7...31 %) and the
 // layers with <= 128 output channels on the stride-8 maps (78-84 % full, +11 %) - and loses on small maps (50 x 84 and below,
 // 14 x 14 ROI maps), which stay on the tile kernels.  g_last_conv_kernel code: 300 (128-channel tiles) / 301 (64-channel tiles).
-int launch_conv_halo(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
-  if ((variant >> 25) & 1) return 0;
-  if (((variant >> 12) & 15) != 0) return 0;  // a tile-kernel configuration was asked for explicitly
-  const bool forced = (variant >> 24) & 1;
+int launch_conv_halo(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s) {
+  if (v.halo == Choice::Never) return 0;
+  if (v.tile_cfg != 0) return 0;  // a tile-kernel configuration was asked for explicitly
+  const bool forced = v.halo == Choice::Force;
   if (a.remap_out || a.accumulate || a.ntaps != 9 || a.KW != 3 || a.wt_taps != 9 || a.pad_h != 1 || a.pad_w != 1 || a.mul != 1 ||
       a.Hin != a.Hout || a.Win != a.Wout)
     return 0;
@@ -395,14 +395,13 @@ int launch_conv_halo(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
     if (tiles < 512) return 0;                          // less than two rounds of tiles: the tile kernels' finer grain wins
     if (!(fill >= 0.88 || (N <= 128 && fill >= 0.70))) return 0;
   }
-  const int tiny = (variant >> 16) & 1;
-  a.abl = (variant >> 18) & 63;
-  if (N <= 64 && !((variant >> 17) & 1)) {  // 64-channel tiles (bit 17: the 128-channel tiles anyway, for A/B runs)
-    g_last_conv_kernel = 301;
+  const int tiny = v.tiny;
+  if (N <= 64 && !v.halo_tile128) {  // 64-channel tiles (U2_CV_HALO_TILE128: the 128-channel tiles anyway, for A/B runs)
+    g_last_conv_kernel = U2_K_HALO_N64;
     return launch_halo_cfg<16, 32, 3, 1>(a, N, tiny, s);
   }
-  g_last_conv_kernel = 300;
-  switch ((variant >> 29) & 3) {
+  g_last_conv_kernel = U2_K_HALO;
+  switch (v.halo_sched) {
     case 1: return launch_halo_cfg<16, 32, 2>(a, N, tiny, s);
     case 2: return launch_halo_cfg<16, 32, 1>(a, N, tiny, s);
     case 3: return launch_halo_cfg<16, 32, 0>(a, N, tiny, s);

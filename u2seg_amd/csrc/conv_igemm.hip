@@ -1287,28 +1287,28 @@ int env_variant(const char* name, int variant) {
 }
 
 int launch_conv(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
-  variant = env_variant("U2_CONV_VARIANT", variant);
-  a.abl = (variant >> 18) & 63;  // measurement switches (conv_args.h); bit 3 = `nt` output stores, applies to every kernel below
+  const ConvVariant v = decode_conv_variant((unsigned)env_variant("U2_CONV_VARIANT", variant));
+  a.abl = v.abl;  // measurement switches (conv_args.h); bit 3 = `nt` output stores, applies to every kernel below
   {  // 1x1 / stride 1 layers with <= 256 input channels on large maps: weights-resident streaming kernel (conv_stream.hip)
-    const int rc = launch_conv_stream(a, N, C, variant, s);
+    const int rc = launch_conv_stream(a, N, C, v, s);
     if (rc == 1) return 0;
     if (rc < 0) return rc;
   }
   {  // 3x3 / stride 1 / pad 1 layers on large maps: halo-staged kernel (conv_halo.hip)
-    const int rc = launch_conv_halo(a, N, C, variant, s);
+    const int rc = launch_conv_halo(a, N, C, v, s);
     if (rc == 1) return 0;
     if (rc < 0) return rc;
   }
   {  // persistent tile kernels (conv_tile.hip) first; 0 = shape / variant not served there
-    const int rc = launch_conv_tile(a, N, C, variant, s);
+    const int rc = launch_conv_tile(a, N, C, v, s);
     if (rc == 1) return 0;
     if (rc < 0) return rc;
   }
-  // wide layers: 256 x 256 tile, 8 waves, four-deep half-K-tile ring (variant bit 8 forces it, bit 9 forbids it)
+  // wide layers: 256 x 256 tile, 8 waves, four-deep half-K-tile ring (v.wide)
   const bool wide_ok = !a.remap_out && C % 64 == 0 && a.ntaps * (C / 32) >= 4;
   // measured win: deep reductions (K >= 1024) with at least two full waves of 256 x 256 tiles; short-K 1x1 layers lose
   const bool wide_auto = N % 256 == 0 && a.ntaps * C >= 1024 && (long long)a.M * N >= 256LL * 256 * 512;
-  if (wide_ok && !(variant & 512) && ((variant & 256) || wide_auto)) {
+  if (wide_ok && v.wide != Choice::Never && (v.wide == Choice::Force || wide_auto)) {
     a.tiles_m = (a.M + 255) / 256;
     a.tiles_n = (N + 255) / 256;
     static PerDeviceOnce attr_set;
@@ -1316,9 +1316,9 @@ int launch_conv(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
       (void)hipFuncSetAttribute((const void*)conv_igemm256_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       (void)hipFuncSetAttribute((const void*)conv_igemm256_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
-    a.stagger_by_parity = (variant & 2048) ? 1 : 0;
-    g_last_conv_kernel = 256 + ((variant & 1024) ? 1024 : 0);
-    if (variant & 1024)  // staggered two-group schedule
+    a.stagger_by_parity = v.wide_stagger_parity ? 1 : 0;
+    g_last_conv_kernel = U2_K_IGEMM256 + (v.wide_stagger ? U2_K_IGEMM256_STAGGER : 0);
+    if (v.wide_stagger)  // staggered two-group schedule
       hipLaunchKernelGGL(conv_igemm256_kernel<true>, dim3(a.tiles_m * a.tiles_n), dim3(C256_THREADS), C256_LDS_BYTES, s, a);
     else
       hipLaunchKernelGGL(conv_igemm256_kernel<false>, dim3(a.tiles_m * a.tiles_n), dim3(C256_THREADS), C256_LDS_BYTES, s, a);
@@ -1326,18 +1326,17 @@ int launch_conv(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
     return 0;
   }
   const bool narrow = N <= 64;  // 256 x 64 tile
-  const bool big = !narrow && (variant & 8);  // 256 x 128 tile, 8 waves
+  const bool big = !narrow && v.tile_256x128;  // 256 x 128 tile, 8 waves
   const int TM = (narrow || big) ? 256 : 128, TN = narrow ? 64 : 128;
   a.tiles_m = (a.M + TM - 1) / TM;
   a.tiles_n = (N + TN - 1) / TN;
   const dim3 grid(a.tiles_m * a.tiles_n), block(big ? 512 : 256);
-  const bool glds = (variant & 1) == 0;
-  // variant: bit0 register staging, bit2 force BK = 32, bit3 256x128 tile, bits 4-5 LDS ring depth override (0 = default)
+  const bool glds = !v.reg_staging;
   // Layers whose whole reduction is <= 256 deep (1x1 convs on <= 256 channels) are HBM-bound and never reach a steady
   // K loop: a small BK = 32 / 2-stage footprint (38 KB) keeps 4 work-groups per CU in flight instead of 2.
   const bool shallow = (long long)a.ntaps * C <= 256;  // K = 256: 440 vs 358 TFLOP/s on the 50x84 256->1024 layer
-  const int bk = (C % 64 == 0 && !(variant & 4) && !shallow) ? 64 : 32;
-  int nst = (variant >> 4) & 3;
+  const int bk = (C % 64 == 0 && !v.bk32 && !shallow) ? 64 : 32;
+  int nst = v.ring;
   if (nst == 0) nst = (bk == 64 || shallow) ? 2 : 4;
   else nst += 1;  // 1 -> 2 stages, 2 -> 3, 3 -> 4
   if (!glds) nst = 2;
@@ -1347,7 +1346,7 @@ int launch_conv(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
   if (lds > 160 * 1024) return -3;
 #define U2_LAUNCH_CONV(BK_, GL_, TM_, TN_, NST_)                                                                 \
   do {                                                                                                           \
-    g_last_conv_kernel = 1000000 + BK_ * 10000 + (TM_ / 64) * 1000 + (TN_ / 64) * 100 + NST_ * 10 + (GL_ ? 1 : 0); \
+    g_last_conv_kernel = U2_K_IGEMM + BK_ * 10000 + (TM_ / 64) * 1000 + (TN_ / 64) * 100 + NST_ * 10 + (GL_ ? 1 : 0); \
     static PerDeviceOnce attr_set;                                                                                \
     if (auto once_guard = attr_set.first()) {                                                                                             \
       (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<BK_, GL_, TM_, TN_, NST_>,                        \
@@ -1490,7 +1489,8 @@ extern "C" int u2_conv_dgrad_tail(const void* in, const void* wt, const void* do
   a.remap_out = 0; a.out_sy = a.out_sx = 1; a.out_y0 = a.out_x0 = 0;
   TailArgs t;
   t.g2 = (const bf16_t*)dout2; t.y = (const bf16_t*)y; t.bits = (const unsigned char*)bits; t.mean = mean; t.invstd = invstd;
-  const int rc = launch_conv_stream_tail(a, t, N, C, env_variant("U2_CONV_VARIANT", variant), (hipStream_t)stream);
+  const int rc = launch_conv_stream_tail(a, t, N, C, decode_conv_variant((unsigned)env_variant("U2_CONV_VARIANT", variant)),
+                                         (hipStream_t)stream);
   if (rc == 1) return 0;
   return rc < 0 ? rc : 1;
 }
@@ -1502,11 +1502,11 @@ extern "C" int u2_conv1x1_bwd_fused(const void* x, const void* dy, const void* w
   const bf16_t* zero = zero_page_ptr();
   if (!zero) return -2;
   if (M <= 0) return 0;
-  variant = env_variant("U2_WDGRAD_VARIANT", variant);
-  if (variant & 4) return 1;   // switched off (A/B runs): the caller takes the two separate launches
+  const FusedBwdVariant v = decode_fused_bwd_variant((unsigned)env_variant("U2_WDGRAD_VARIANT", variant));
+  if (v.never) return 1;   // switched off (A/B runs): the caller takes the two separate launches
   const int rc = launch_wdgrad_stream((const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)wt, (bf16_t*)dx, dw, dw_stride_n,
-                                      dw_stride_c, n_valid, c_valid, zero, M, C, x_ld, N, dy_ld, wt_ld, dx_ld, variant & 1,
-                                      (variant >> 1) & 1, (hipStream_t)stream);
+                                      dw_stride_c, n_valid, c_valid, zero, M, C, x_ld, N, dy_ld, wt_ld, dx_ld, v,
+                                      (hipStream_t)stream);
   if (rc == 1) return 0;
   return rc < 0 ? rc : 1;
 }
@@ -1519,12 +1519,11 @@ extern "C" int u2_conv1x1_bwd_fused_bn(const void* x, const void* dz, const void
   const bf16_t* zero = zero_page_ptr();
   if (!zero) return -2;
   if (M <= 0) return 0;
-  variant = env_variant("U2_WDGRAD_VARIANT", variant);
-  if (variant & 4) return 1;
+  const FusedBwdVariant v = decode_fused_bwd_variant((unsigned)env_variant("U2_WDGRAD_VARIANT", variant));
+  if (v.never) return 1;
   const int rc = launch_wdgrad_stream((const bf16_t*)x, (const bf16_t*)dz, (const bf16_t*)wt, (bf16_t*)dx, dw, dw_stride_n,
-                                      dw_stride_c, n_valid, c_valid, zero, M, C, x_ld, N, dy_ld, wt_ld, dx_ld,
-                                      (variant & 1) | ((variant >> 2) & 2) | ((variant >> 2) & 4), (variant >> 1) & 1, (hipStream_t)stream, (const bf16_t*)y,
-                                      k1, k2, k3);
+                                      dw_stride_c, n_valid, c_valid, zero, M, C, x_ld, N, dy_ld, wt_ld, dx_ld, v,
+                                      (hipStream_t)stream, (const bf16_t*)y, k1, k2, k3);
   if (rc == 1) return 0;
   return rc < 0 ? rc : 1;
 }
@@ -1551,50 +1550,46 @@ extern "C" int u2_conv_wgrad_into(const void* x, const void* dy, float* dw, int 
   a.Hout = Hout; a.Wout = Wout; a.N = N; a.dy_ld = dy_ld;
   a.KH = KH; a.KW = KW; a.pad_h = pad_h; a.pad_w = pad_w; a.stride = stride;
   a.M = B * Hout * Wout;
-  // 256 x 256 tiles: only on request (variant bit 8).  Measured 516 vs 805 TFLOP/s on the 200x336 3x3 256->256 layer: with
+  // 256 x 256 tiles on the multi-tap layers: only on request (v.wide).  Measured 516 vs 805 TFLOP/s on the 200x336 3x3 256->256 layer: with
   // one resident work-group per CU the transposing reads of a step are not hidden behind anything, while four resident
   // 128 x 128 groups hide them behind each other, which outweighs the halved operand traffic.
-  variant = env_variant("U2_WGRAD_VARIANT", variant);
-  // 1x1 / stride 1 over large maps: streaming kernel with the whole dW block in registers (wgrad_stream.hip); variant bit 18
-  // forces it on any size, bit 19 forbids it (as does any of the per-tap kernel's own variant bits 0-11), bit 20: 8 pixel ranges
-  // only (tests), bits 21-23: block configuration (0 = automatic), bits 24-25: work-groups per CU (0 = the configuration's default)
-  if (KH * KW == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && Hin == Hout && Win == Wout && !(variant & (1 << 19)) &&
-      (variant & 0xfff) == 0) {
+  const WgradVariant v = decode_wgrad_variant((unsigned)env_variant("U2_WGRAD_VARIANT", variant));
+  // 1x1 / stride 1 over large maps: streaming kernel with the whole dW block in registers (wgrad_stream.hip)
+  if (KH * KW == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && Hin == Hout && Win == Wout && v.stream != Choice::Never &&
+      !v.per_tap_stream) {
     const int rc = launch_wgrad_stream(a.x, a.dy, dw, dw_stride_n, dw_stride_c, n_valid, c_valid, a.zero, a.M, C, x_ld, N, dy_ld,
-                                       (variant >> 18) & 1, (variant >> 20) & 1, (variant >> 21) & 7, (variant >> 24) & 3,
+                                       v.stream == Choice::Force, v.stream_tiny, v.stream_cfg, v.stream_per_cu,
                                        (hipStream_t)stream);
     if (rc == 1) return 0;
     if (rc < 0) return rc;
   }
-  // 3x3 / stride 1 / pad 1: all nine taps per work-group, input halo in LDS (wgrad_halo.hip); variant bit 12 forces it,
-  // bit 13 forbids it (as does any of the per-tap kernel's own variant bits 0-10), bits 14-15: rounds of work-groups (0 = one per CU);
-  // automatic when a work-group gets >= 4000 positions to reduce
+  // 3x3 / stride 1 / pad 1: all nine taps per work-group, input halo in LDS (wgrad_halo.hip); automatic when a work-group gets
+  // >= 4000 positions to reduce
   const bool halo_ok = KH == 3 && KW == 3 && stride == 1 && pad_h == 1 && pad_w == 1 && Hin == Hout && Win == Wout;
-  if (halo_ok && !(variant & 8192) && (variant & 0x7ff) == 0) {
+  if (halo_ok && v.halo != Choice::Never && !v.per_tap_halo) {
     const int rc = launch_wgrad_halo(a.x, a.dy, dw, dw_stride_n, dw_stride_tap, dw_stride_c, n_valid, c_valid, a.zero, B, Hin, Win,
-                                     C, x_ld, N, dy_ld, ((variant >> 14) & 3) + 1, (variant & 4096) ? 1 : 0,
-                                     (variant & 65536) ? 1 : ((variant & 131072) ? 2 : 0), (hipStream_t)stream);
-    if (rc == 1) { g_last_conv_kernel = 2900; return 0; }
+                                     C, x_ld, N, dy_ld, v.halo_rounds, v.halo == Choice::Force ? 1 : 0,
+                                     v.atomics ? 1 : (v.partials_force ? 2 : 0), (hipStream_t)stream);
+    if (rc == 1) { g_last_conv_kernel = U2_K_WGRAD_HALO; return 0; }
     if (rc < 0) return rc;
   }
   // 256 x 256 tiles (half the operand traffic per flop) win where nothing else hides the memory stream: 1x1 layers over the
-  // stride-4 / stride-8 maps and the 7x7 "fully connected" fc1 (tests/native/selftest bench2w, profiles/r02_wgrad_variants.txt);
-  // variant bit 8 forces them, bit 11 forbids them
+  // stride-4 / stride-8 maps and the 7x7 "fully connected" fc1 (tests/native/selftest bench2w, profiles/r02_wgrad_variants.txt)
   // Round 4, with the partial-tile reduction in place of the 256 KB atomic epilogue (bench2w 0 256 2048, profiles/r04_wgrad_partials.txt):
   // the 256-wide tiles also win on the stride-16 1x1 layers (res4 256 <-> 1024: 71 -> 67-69 us on two boxes, the stride-2 512 -> 1024
   // 124 -> 112) - wherever both channel counts fill 256-wide tiles; with a 128-channel side (128 <-> 512, 256 -> 128) the result
   // flipped between two boxes (+-10 %), so those stay on the 128-wide tiles; below ~50 k pixels (res5, the FC layers) they lose.
   const bool wide_1x1 = KH * KW == 1 && a.M >= 50000 && N % 256 == 0 && C % 256 == 0;
-  const bool wide_auto = !(variant & 2048) &&
+  const bool wide_auto = v.wide != Choice::Never &&
                          (wide_1x1 || ((N % 256 == 0) && (C % 256 == 0) && KH * KW > 1 && a.M <= 16384 && Hout == 1 && Wout == 1));
-  const bool wide = ((variant & 256) || wide_auto) && (variant & 3) == 0;
+  const bool wide = (v.wide == Choice::Force || wide_auto) && !v.reg_staging && !v.scalar_gather;
   const int tw = wide ? 256 : 128;
   a.tiles_n = (N + tw - 1) / tw;
   a.tiles_c = (C + tw - 1) / tw;
   const int tiles = a.tiles_n * a.tiles_c * KH * KW;
   // Pixel splits: fill the chip once (4 resident work-groups per CU = 1024 slots) but keep >= 2048 pixels per
   // work-group so that the 64 KB fp32-atomic epilogue stays a small fraction; tiny layers fall back to >= 512 groups.
-  int slots = (wide ? 256 : 1024) >> ((variant >> 4) & 3);  // resident work-groups; variant bits 4-5: tuning knob
+  int slots = (wide ? 256 : 1024) >> v.fewer_splits;  // resident work-groups; U2_WG_FEWER_SPLITS: tuning knob
   int splits = slots / tiles;
   if (splits < 1) splits = 1;
   // (1024 and 512 pixels per work-group measured 25 % slower on the stride-16 / 32 layers: the epilogue grows with the splits)
@@ -1613,21 +1608,21 @@ extern "C" int u2_conv_wgrad_into(const void* x, const void* dy, float* dw, int 
   a.pix_per_wg = ppw;
   a.tiles = tiles;
   // measured: +29% on res3 3x3, +6% on the 200x336 3x3 layers, -3..-10% on small-M layers and plain GEMMs
-  a.xcd_group = ((variant & 64) || (!(variant & 128) && KH * KW > 1 && a.M >= 200000)) ? 1 : 0;
+  a.xcd_group = (v.xcd == Choice::Force || (v.xcd != Choice::Never && KH * KW > 1 && a.M >= 200000)) ? 1 : 0;
   const dim3 grid = a.xcd_group ? dim3(tiles * splits) : dim3(tiles, splits);
   const dim3 block(256);
   hipStream_t s = (hipStream_t)stream;
-  // partial tiles + one reduction pass instead of the fp32-atomic epilogue (variant bit 16 keeps the atomics); a single split
+  // partial tiles + one reduction pass instead of the fp32-atomic epilogue (U2_WG_ATOMICS keeps the atomics); a single split
   // has nothing to reduce and little to gain
   a.part = nullptr;
   // Measured (tests/native/selftest bench2w 0 65536, round 4): the atomics of a long kernel hide behind the work-groups that are
   // still multiplying, so the pass only pays where the launch is short or has many tiles - 1x1 layers on the stride-8 ... 32 maps
   // (res4 78 -> 72 us, res5 67 -> 58, lat3 126 -> 113, res3 256->512 138 -> 114), mid-size 3x3 layers (+3...10 %); it loses on
   // the stride-4 1x1 layers with one or two tiles and 512 splits (64 MB of partials: 64->256 134 -> 156 us) and on the big 3x3
-  // layers (-2...4 %).  variant bit 17 forces the pass wherever splits >= 2.
+  // layers (-2...4 %).  U2_WG_PARTIALS_FORCE forces the pass wherever splits >= 2.
   const long long dw_elems = (long long)a.tiles_n * a.tiles_c * tw * tw;
   const bool part_auto = dw_elems >= 4LL * 128 * 128 && !(KH * KW > 1 && a.M >= 200000);
-  if (!(variant & 65536) && splits >= 2 && (part_auto || (variant & 131072)))
+  if (!v.atomics && splits >= 2 && (part_auto || v.partials_force))
     a.part = wgrad_scratch(s, (size_t)tiles * splits * tw * tw * sizeof(float));
   auto reduce = [&]() -> int {
     if (!a.part) return 0;
@@ -1641,8 +1636,8 @@ extern "C" int u2_conv_wgrad_into(const void* x, const void* dy, float* dw, int 
     U2_CHECK_LAUNCH();
     return 0;
   };
-  const bool glds = (variant & 1) == 0, tr = (variant & 2) == 0;
-  g_last_conv_kernel = (wide ? 2256 : 2000 + (glds ? 2 : 0) + (tr ? 1 : 0)) + (a.xcd_group ? 100 : 0);
+  const bool glds = !v.reg_staging, tr = !v.scalar_gather;
+  g_last_conv_kernel = (wide ? U2_K_WGRAD256 : U2_K_WGRAD + (glds ? 2 : 0) + (tr ? 1 : 0)) + (a.xcd_group ? U2_K_WGRAD_XCD : 0);
   if (wide) {
     static PerDeviceOnce attr_set;
     if (auto once_guard = attr_set.first()) {
@@ -1652,7 +1647,7 @@ extern "C" int u2_conv_wgrad_into(const void* x, const void* dy, float* dw, int 
     U2_CHECK_LAUNCH();
     return reduce();
   }
-  const int ring = (variant >> 9) & 3;  // bits 9-10: LDS ring depth of the LDS-DMA form (0 = two buffers, 1 = 3, 2 = 4)
+  const int ring = v.ring;  // LDS ring depth of the LDS-DMA form (0 = two buffers, 1 = 3, 2 = 4)
   if (glds && tr && ring == 1)      hipLaunchKernelGGL((conv_wgrad_kernel<true, true, 3>), grid, block, 0, s, a);
   else if (glds && tr && ring == 2) hipLaunchKernelGGL((conv_wgrad_kernel<true, true, 4>), grid, block, 0, s, a);
   else if (glds && tr)  hipLaunchKernelGGL((conv_wgrad_kernel<true, true>), grid, block, 0, s, a);

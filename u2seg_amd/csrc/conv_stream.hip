@@ -445,20 +445,26 @@ int launch_stream_cfg(ConvArgs& a, int N, int tiny, int forced, int code, hipStr
 
 }  // namespace
 
-// Serves 1x1 / stride 1 / unpadded launches with C in {32, 64, 128, 256}, N % 8 == 0, not accumulating.  variant bit 17:
-// always where it applies, bit 26: never; any explicit kernel selection (bits 0-15) keeps the launch on the older kernels.
+// What the conv word says to both streaming launchers: false = forbidden, or an explicit kernel selection keeps the launch on
+// the older kernels.
+static bool stream_allowed(const ConvVariant& v, bool& forced, int& tiny) {
+  forced = v.stream == Choice::Force;
+  tiny = v.tiny;
+  return v.stream != Choice::Never && !v.explicit_kernel;
+}
+
+// Serves 1x1 / stride 1 / unpadded launches with C in {32, 64, 128, 256}, N % 8 == 0, not accumulating.
 // g_last_conv_kernel code: 700 + C / 32 * 10 + (1, 2, 4 waves along the pixels -> 0, 1, 2).
-int launch_conv_stream(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
-  if ((variant >> 26) & 1) return 0;
-  if (variant & 0xffff) return 0;
-  const bool forced = (variant >> 17) & 1;
+int launch_conv_stream(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s) {
+  bool forced;
+  int tiny;
+  if (!stream_allowed(v, forced, tiny)) return 0;
   if (a.remap_out || a.accumulate || a.ntaps != 1 || a.wt_taps != 1 || a.pad_h != 0 || a.pad_w != 0 || a.mul != 1 ||
       a.Hin != a.Hout || a.Win != a.Wout)
     return 0;
   if (!(C == 32 || C == 64 || C == 128 || C == 256) || (N & 7) || (a.out_ld & 7) || a.in_ld < C || a.M < 1) return 0;
   if ((unsigned long long)a.M * a.in_ld * 2ull >= 0xffffffffull) return 0;
-  const int tiny = (variant >> 16) & 1;
-  const int code = 700 + (C / 32) * 10;
+  const int code = U2_K_STREAM + (C / 32) * 10;
   if (C == 64) {
     if (N > 128) return launch_stream_cfg<2, 128, 1, 4>(a, N, tiny, forced, code, s);
     if (N > 64) return launch_stream_cfg<2, 128, 2, 4>(a, N, tiny, forced, code + 1, s);
@@ -482,12 +488,12 @@ int launch_conv_stream(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
 
 // The data gradient of a residual block's conv1 with the previous block's tail reduce in its epilogue (TAIL above): a.out is
 // dz, a.stats the [2][N] sums.  Serves the three launches the res2-res4 bottlenecks make - (C, N) = (64, 256), (128, 512),
-// (256, 1024), dense rows - under launch_conv_stream's variant bits and fill rule; everything else is "not served" (0) and
+// (256, 1024), dense rows - under launch_conv_stream's variant rules and fill rule; everything else is "not served" (0) and
 // nothing is written.  g_last_conv_kernel code: 705 + C / 32 * 10.
-int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, int variant, hipStream_t s) {
-  if ((variant >> 26) & 1) return 0;
-  if (variant & 0xffff) return 0;
-  const bool forced = (variant >> 17) & 1;
+int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, const ConvVariant& v, hipStream_t s) {
+  bool forced;
+  int tiny;
+  if (!stream_allowed(v, forced, tiny)) return 0;
   if (a.remap_out || a.accumulate || a.relu || a.bias || a.ntaps != 1 || a.wt_taps != 1 || a.pad_h != 0 || a.pad_w != 0 ||
       a.mul != 1 || a.Hin != a.Hout || a.Win != a.Wout)
     return 0;
@@ -495,8 +501,7 @@ int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, int va
   if (a.out_ld != N || a.in_ld < C || (a.in_ld & 7) || a.M < 1) return 0;
   if ((unsigned long long)a.M * a.in_ld * 2ull >= 0xffffffffull || (unsigned long long)a.M * N * 2ull >= 0xffffffffull) return 0;
   if (!a.stats || !a.out || !t.g2 || !t.y || !t.bits || !t.mean || !t.invstd) return 0;
-  const int tiny = (variant >> 16) & 1;
-  const int code = 705 + (C / 32) * 10;
+  const int code = U2_K_STREAM + U2_K_STREAM_TAIL + (C / 32) * 10;
   a.abl = 0;
   if (C == 64) return launch_stream_cfg<2, 128, 1, 4, 2, true>(a, N, tiny, forced, code, s, t);
   if (C == 128) return launch_stream_cfg<4, 64, 1, 4, 4, true>(a, N, tiny, forced, code, s, t);

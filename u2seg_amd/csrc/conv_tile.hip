@@ -755,11 +755,11 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
 // every persistent-kernel hand-over does); it does NOT rely on co-residency of the whole grid.
 //
 // Round 6: MEASURED OTHERWISE.  With the semantic / mask head's kernels on their own streams beside it, the driver's bench command hung
-// in 4 of 23 runs (profiles/r06_hang_hunt.txt: the chip never finishes a step), in 0 of 24 with this form forbidden (variant bit 28), in 0
+// in 4 of 23 runs (profiles/r06_hang_hunt.txt: the chip never finishes a step), in 0 of 24 with this form forbidden (U2_CV_STREAMK_FORBID), in 0
 // of 40 with those streams off, and still in 3 of 30 with the stream-K launches of different streams ordered behind each other by
 // events - one launch of this form beside kernels of another stream is enough.  What the argument above misses is not understood.
 // The product path (layers/functional.py:streamk_region) asks for this form only where no branch stream has work in flight and
-// passes bit 28 elsewhere; callers with several streams must do the same.
+// passes U2_CV_STREAMK_FORBID elsewhere; callers with several streams must do the same.
 constexpr int SK_MAX_GROUPS = 512;
 constexpr size_t SK_WS_LIMIT = (size_t)64 << 20;
 bool sk_scratch(hipStream_t s, ConvArgs& a, size_t need_bytes) {
@@ -902,7 +902,7 @@ int launch_cfg(ConvArgs& a, int N, int per_cu, int tiny_grid, hipStream_t s, int
       if (auto once_guard = attr_set_sk.first()) {
         (void)hipFuncSetAttribute((const void*)conv_tile_kernel<WCH, WPX, RING, false, true, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       }
-      g_last_conv_kernel += 400;  // 5xx: the stream-K form of configuration xx
+      g_last_conv_kernel += U2_K_STREAMK - U2_K_TILE;  // 5xx: the stream-K form of configuration xx
 #ifdef U2_TILE_TRACE
       tile_trace_begin((int)Gs, s);
 #endif
@@ -935,18 +935,19 @@ int launch_cfg(ConvArgs& a, int N, int per_cu, int tiny_grid, hipStream_t s, int
 
 }  // namespace
 
-// variant bits 12-15 select the tile configuration: 0 = automatic, 1 = 256ch x 256px ring 4, 2 = 256 x 256 ring 5,
+// Tile configurations (U2_CV_TILE_CFG of the conv word): 0 = automatic, 1 = 256ch x 256px ring 4, 2 = 256 x 256 ring 5,
 // 3 = 128ch x 256px (ring 3, two groups per CU), 4 = 256ch x 128px (ring 3, two groups per CU), 5 = 128ch x 256px ring 4,
 // 6 = 64ch x 512px ring 4 (layers with <= 64 output channels: no MFMA spent on absent channels),
 // 7 = 256 x 256 with whole K tiles (64 channels, 128-byte rows) in a ring of 2 (C % 64 == 0; the long-row 1x1 layers),
-// 15 = never (conv_igemm.hip kernels only); bit 16: 8 work-groups only (tests: forces several tiles per work-group).
+// 15 = never (conv_igemm.hip kernels only).
 // Tried and removed (numbers in profiles/r02_conv_ablation.txt, r02_conv_pingpong.txt): a j-split schedule
 // with every LDS read 12+ MFMAs ahead of its use (+0 %), and a ping-pong schedule with the two wave groups half a sequence
 // apart (-8 %).
-int launch_conv_tile(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
-  int sel = (variant >> 12) & 15;
-  const int tiny = (variant >> 16) & 1;
-  if (sel == 15) return 0;
+int launch_conv_tile(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s) {
+  int sel = v.tile_cfg;
+  const int tiny = v.tiny;
+  const int sk = (int)v.streamk;  // launch_cfg's `sk`
+  if (sel == U2_CV_TILE_CFG_NEVER) return 0;
   if ((C & 31) || (N & 7) || (a.out_ld & 7) || a.ntaps < 1 || a.M >= (1 << 24) || a.M < 1) return 0;
   // the accumulating epilogue exists for configuration 4 (256ch x 128px: the 1x1 conv3 of a residual block), no statistics
   if (a.accumulate && (a.stats || a.remap_out || (sel != 0 && sel != 4) || N < 128)) return 0;
@@ -991,15 +992,14 @@ int launch_conv_tile(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
     const int nks = a.ntaps * (C >> 6);
     const long long T7 = (long long)((a.M + 255) / 256) * ((N + 255) / 256);
     if (nks * (T7 < 256 ? 1 : T7 / 256) < 3) return 0;   // a work-group needs ring + 1 stages over all its tiles
-    g_last_conv_kernel = 107;
-    const int sk7 = ((variant >> 28) & 1) ? 0 : ((variant >> 27) & 1) ? 2 : 1;
-    return launch_cfg<4, 2, 2, false, 2>(a, N, 1, tiny, s, sk7);
+    g_last_conv_kernel = U2_K_TILE + 7;
+    return launch_cfg<4, 2, 2, false, 2>(a, N, 1, tiny, s, sk);
   }
   int ring = (sel == 2) ? 5 : (sel == 1 || sel == 5 || sel == 6) ? 4 : 3;
   if (nkh < ring) {
     // a work-group only needs RING half tiles over ALL the tiles it walks; in automatic mode fall back to the ring-3
     // configurations (K >= 64 with two or more tiles per work-group, K >= 96 otherwise)
-    if ((variant >> 12 & 15) != 0) return 0;
+    if (v.tile_cfg != 0) return 0;
     if (a.accumulate && N <= 128) return 0;  // the accumulating epilogue exists for configuration 4 only
     sel = (N <= 128) ? 3 : 4;
     ring = 3;
@@ -1008,10 +1008,9 @@ int launch_conv_tile(ConvArgs& a, int N, int C, int variant, hipStream_t s) {
     const long long min_tiles = (T >> 3) / 64;  // 512 work-groups: 64 per XCD
     if (nkh * min_tiles < ring) return 0;
   }
-  g_last_conv_kernel = 100 + sel;
-  // stream-K form (equal shares of the (tile, half K tile) sequence): automatic where whole tiles fill the last round badly;
-  // variant bit 27 forces it, bit 28 forbids it.  g_last_conv_kernel: 500 + configuration.
-  const int sk = ((variant >> 28) & 1) ? 0 : ((variant >> 27) & 1) ? 2 : 1;
+  g_last_conv_kernel = U2_K_TILE + sel;
+  // stream-K form (equal shares of the (tile, half K tile) sequence): automatic where whole tiles fill the last round badly
+  // (v.streamk).  g_last_conv_kernel: 500 + configuration.
   switch (sel) {
     case 1: return launch_cfg<4, 2, 4>(a, N, 1, tiny, s, sk);
     case 2: return launch_cfg<4, 2, 5>(a, N, 1, tiny, s, sk);

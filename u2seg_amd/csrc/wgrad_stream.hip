@@ -440,14 +440,15 @@ int launch_wgrad_stream(const bf16_t* x, const bf16_t* dy, float* dw, long long 
 // yn / k1..k3 (optional): dy is the gradient in front of a batch normalisation's apply step, evaluated on the fly (AP above).
 int launch_wdgrad_stream(const bf16_t* x, const bf16_t* dy, const bf16_t* wt, bf16_t* dx, float* dw, long long dw_sn, int dw_sc,
                          int n_valid, int c_valid, const bf16_t* zero, int M, int C, int x_ld, int N, int dy_ld, int wt_ld,
-                         int dx_ld, int force, int tiny, hipStream_t s, const bf16_t* yn, const float* k1, const float* k2,
+                         int dx_ld, const FusedBwdVariant& v, hipStream_t s, const bf16_t* yn, const float* k1, const float* k2,
                          const float* k3) {
   if ((C & 7) || (N & 7) || (x_ld & 7) || (dy_ld & 7) || (wt_ld & 7) || (dx_ld & 7) || M < 1 || n_valid < 1 || c_valid < 1) return 0;
   if (dx_ld < C || wt_ld < N) return 0;
   if ((unsigned long long)M * (unsigned)x_ld * 2ull >= 0xffffffffull || (unsigned long long)M * (unsigned)dy_ld * 2ull >= 0xffffffffull) return 0;
   const bool small = N <= 256 && C <= 64, wide = N > 256 && N <= 512 && C <= 128;
   if (!small && !wide) return 0;
-  if (!(force & 1) && (M < 200000 || n_valid <= 128)) return 0;
+  if (!v.force && (M < 200000 || n_valid <= 128)) return 0;
+  const int tiny = v.tiny;
   WsArgs a;
   a.x = x; a.dy = dy; a.dw = dw; a.dw_sn = dw_sn; a.dw_sc = dw_sc; a.n_valid = n_valid; a.c_valid = c_valid; a.zero = zero;
   a.M = M; a.N = N; a.C = C; a.x_ld = x_ld; a.dy_ld = dy_ld;
@@ -460,10 +461,10 @@ int launch_wdgrad_stream(const bf16_t* x, const bf16_t* dy, const bf16_t* wt, bf
     // work-group per CU, 40 KB stages, ring of 4); code 2761
     if (!k1 || !k2 || !k3) return 0;
     // N <= 512 (res3 tails, 128 input channels = two c-tiles that each stage and transform dz and y): 72 KB stages, ring of 2;
-    // code 2763.  Only on request (force bit 2): see the measurement in DESIGN.md 5.0 item 8
-    if (wide) return (force & 4) ? launch_ws<8, 1, 4, 4, true, true>(a, 1, tiny, 2763, s) : 0;
+    // code 2763.  Only on request (U2_WD_BN_WIDE): see the measurement in DESIGN.md 5.0 item 8
+    if (wide) return v.bn_wide ? launch_ws<8, 1, 4, 4, true, true>(a, 1, tiny, 2763, s) : 0;
     if (!small) return 0;
-    if (force & 2) return launch_ws<4, 1, 4, 4, true, true>(a, 2, tiny, 2762, s);   // two 4-wave work-groups per CU, ring of 2
+    if (v.bn_two_groups) return launch_ws<4, 1, 4, 4, true, true>(a, 2, tiny, 2762, s);   // two 4-wave work-groups per CU, ring of 2
     return launch_ws<8, 1, 2, 4, true, true>(a, 1, tiny, 2761, s);
   }
   if (small) return launch_ws<4, 1, 4, 4, true>(a, 2, tiny, 2751, s);

@@ -212,8 +212,9 @@ def join_aux_stream(device, index=0):
 # stream-K launches: 0 of 20).  Until it is, the product path asks for the stream-K form only where no branch stream has work in
 # flight: inside the bottom-up backbone (forward: nothing else has been launched yet; backward: the heads' streams have been
 # joined by the FPN's gradient fan-in), and anywhere when the branch streams are off (set_stream_overlap(False)).  Elsewhere the
-# calls carry variant bit 28 (whole tiles).  U2_STREAMK_EVERYWHERE=1 restores the old behaviour.
-_NO_STREAMK = 1 << 28
+# calls carry U2_CV_STREAMK_FORBID of the conv word (include/u2seg_hip.h: whole tiles).  U2_STREAMK_EVERYWHERE=1 restores the old
+# behaviour.
+_NO_STREAMK = _hip.K.CV_STREAMK_FORBID
 _SK_REGION = [0]
 
 
