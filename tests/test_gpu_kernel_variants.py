@@ -402,6 +402,7 @@ def test_deferred_batch_norm_gradient_guards(F):
     that consumer's gradient - the tensor hook on the conv output raises inside that backward pass instead of letting the
     convolution see a sum without the normalisation's part; (iii) entries a failed backward left behind are dropped (and
     reported) by the next FlatSGD.zero_grad, and a clean pass afterwards still takes the fused launch."""
+    from u2seg_amd.layers import deferred
     from u2seg_amd.layers.modules import BatchNorm2d, Conv2d
     from u2seg_amd.solver import FlatSGD
 
@@ -414,8 +415,9 @@ def test_deferred_batch_norm_gradient_guards(F):
         conv.train()
         opt = FlatSGD(conv, lr=0.1)
         x = nhwc(bf(torch.randn((2, 64, 33, 21), generator=g)))
-        ph = F._lazy_placeholder(x.device)
+        ph = deferred.post(deferred.BN_APPLY, x.device, (1,), (None, None, None))
         assert float(ph.float().abs().sum()) == 0.0 and ph.numel() == 1
+        assert deferred.take(deferred.BN_APPLY, ph) == (None, None, None) and not any(deferred.pending().values())
         # (ii) second consumer of the conv output
         opt.zero_grad()
         xd = x.clone().requires_grad_(True)
@@ -425,9 +427,10 @@ def test_deferred_batch_norm_gradient_guards(F):
         out = F.batch_norm_act(y, stats, n.weight, n.bias, n.running_mean, n.running_var, sync=False)
         with pytest.raises(RuntimeError, match="second consumer"):
             (out.float().sum() + y.float().sum()).backward()
-        assert not F._LAZY_GRADS
+        assert not any(deferred.pending().values())
         # (iii) a stale entry is reported by the next zero_grad, then the path works again
-        F._LAZY_GRADS[(x.device.index, ph.data_ptr())] = (ph, None, None, None)
+        deferred.post(deferred.BN_APPLY, x.device, (1,), (None, None, None))
+        assert deferred.pending()[deferred.BN_APPLY] == 1
         with pytest.raises(RuntimeError, match="never consumed"):
             opt.zero_grad()
         opt.zero_grad()
@@ -439,7 +442,7 @@ def test_deferred_batch_norm_gradient_guards(F):
         assert float(xd.grad.float().abs().max()) >= 0 and torch.isfinite(conv.weight.grad).all()
     finally:
         F.FUSED_BWD_MIN_PIXELS = old_min
-        F._LAZY_GRADS.clear()
+        deferred.drain()
         os.environ.pop("U2_WDGRAD_VARIANT") if old_env is None else os.environ.__setitem__("U2_WDGRAD_VARIANT", old_env)
 
 

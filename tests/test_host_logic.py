@@ -643,6 +643,46 @@ def test_fan_out_handles_sum_gradients_on_cpu():
     assert torch.allclose(feats["p2"].grad, torch.full((2, 2), 7.0)) and torch.allclose(feats["p3"].grad, torch.full((2, 2), 2.0))
 
 
+def test_fan_out_takes_a_deferred_roi_gather_on_cpu(monkeypatch):
+    """One gradient of a fan-out node is the placeholder of a deferred ROIAlign gather (layers/deferred.py): the node takes the
+    entry, folds the other readers' gradients (at most four per pass) down to the at most two addends the gather accepts and
+    returns the gather's map.  The gather itself (a HIP launch) is replaced: it answers its addends' sum + 10."""
+    import torch
+
+    from u2seg_amd.layers import deferred
+    from u2seg_amd.layers import functional as F
+
+    deferred.drain()
+    seen = []
+
+    def gather(shapes, scales, sets, device, level=None, addends=()):
+        seen.append((level, len(addends)))
+        return [sum(addends) + 10]
+
+    monkeypatch.setattr(F, "_roi_gather", gather)
+    shared = {"shapes": [(3, 4)], "scales": (1.0,), "pend": [], "device": torch.device("cpu")}
+
+    class Tap(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, t):
+            return t.view_as(t)
+
+        @staticmethod
+        def backward(ctx, g):
+            return deferred.post(deferred.ROI_GATHER, g.device, g.shape, (shared, 0))
+
+    x = torch.randn(3, 4).bfloat16().requires_grad_(True)
+    a, b, c, d = F.fan_out(x, 4)
+    ((a * 1.0 + b * 2.0 + c * 3.0).sum() + Tap.apply(d).sum()).backward()
+    assert seen == [(0, 1)] and not any(deferred.pending().values())
+    assert torch.equal(x.grad, torch.full_like(x, 16.0))
+    # without the fold nothing is pending, and the placeholder-free path is the plain sum
+    x.grad = None
+    a, b = F.fan_out(x, 2)
+    (a * 1.0 + b * 2.0).sum().backward()
+    assert seen == [(0, 1)] and torch.equal(x.grad, torch.full_like(x, 3.0))
+
+
 def test_topk_segment_chooser():
     """layers/functional.py:_topk_segments - long rows are cut into equal segments only when they tile the row exactly, stay
     several times longer than k and do not exceed the chip's work-group slots."""

@@ -8,6 +8,7 @@ layout (``[Cout][kh*kw][Cin]`` bf16) on the fly.
 
 Every function here launches HIP kernels; none has a CPU or ATen compute fallback.
 """
+import collections
 import ctypes
 import math
 
@@ -19,6 +20,7 @@ import torch.distributed as dist
 from torch.autograd import Function
 
 from .. import _hip
+from . import deferred
 
 BF16 = torch.bfloat16
 
@@ -401,8 +403,9 @@ class _Conv2dFn(Function):
         if wgrad_dst is not None and wgrad_dst.numel() == weight.numel() and wgrad_dst.is_contiguous():
             ctx.arena = wgrad_dst if tuple(wgrad_dst.shape) == tuple(weight.shape) else wgrad_dst.view(weight.shape)
         ctx.param = param
-        # the bias gradient goes straight into the bias' arena slice as well (u2_colsum_add)
-        ctx.bias_dst = param_ref[2] if param_ref is not None and len(param_ref) > 2 and bias is not None else None
+        # the bias gradient goes straight into the bias' arena slice as well (u2_colsum_add), if the kernels can add into it
+        bdst = param_ref[2] if param_ref is not None and len(param_ref) > 2 and bias is not None else None
+        ctx.bias_dst = bdst if bdst is not None and bdst.is_contiguous() and bdst.dtype == torch.float32 and bdst.numel() == n else None
         ctx.set_materialize_grads(False)  # no zero tensor for the (non-differentiable) statistics output
         if want_stats:
             ctx.mark_non_differentiable(stats)
@@ -414,129 +417,146 @@ class _Conv2dFn(Function):
             return (None,) * 10
         x, weight, out = ctx.saved_tensors
         stride, pad, relu, has_bias = ctx.cfg
-        n, cin, kh, kw = weight.shape
-        b, h, w_, cp = x.shape
-        _, ho, wo, npad = dout.shape
-        lazy = _LAZY_GRADS.pop((dout.device.index, dout.data_ptr()), None) if _LAZY_GRADS else None
-        if lazy is not None:
-            # the gradient is still (dz, y, coefficients) of the batch normalisation behind this layer
-            _ph, lz_dz, lz_y, lz_k = lazy
-            assert not relu and not has_bias and kh == 1 and kw == 1 and stride == 1 and pad == 0
-            dst = ctx.wgrad_dst
-            wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
-            dx = torch.empty_like(x)
-            if dst is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _hip.call_status(
-                    "u2_conv1x1_bwd_fused_bn", x, lz_dz, lz_y, lz_k[2], lz_k[3], lz_k[4], wd, dx, dst, b * h * w_, cp, cp, npad, npad,
-                    npad, cp, n, cin, cin, 1, 0) == 0:
-                return dx, None, None, None, None, None, None, None, None, None
-            dout = torch.empty_like(lz_y)   # not served after all: the apply step as its own launch, then the usual paths
-            _hip.call("u2_norm_bwd_apply", lz_dz, None, lz_y, lz_k[2], lz_k[3], lz_k[4], dout, None, 1, b * h * w_, npad, npad, 0,
-                      None, None)
-            dx = None
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        # the shapes, read once for all helpers: x [b, h, w_, cp], weight [n, cin, kh, kw], dout [b, ho, wo, npad]
+        geom = (*x.shape, *weight.shape, *dout.shape[1:], stride, pad)
+        lazy = deferred.take(deferred.BN_APPLY, dout)
+        if lazy is not None:   # the gradient is still (dz, y, coefficients) of the batch normalisation behind this layer
+            dx, dout = _conv_bwd_lazy_bn(ctx, geom, x, weight, *lazy)
+            if dx is not None:
+                return (dx,) + (None,) * 9
         dout = dout.contiguous()
-        bias_done = False
-        if relu:
-            dz = torch.empty_like(dout)
-            bdst = ctx.bias_dst if (has_bias and ctx.needs_input_grad[2]) else None
-            if bdst is not None and bdst.is_contiguous() and bdst.dtype == torch.float32 and bdst.numel() == n:
-                # ReLU backward and the bias gradient (into its arena slice) in one pass over dout / out
-                _hip.call("u2_relu_bwd_colsum", dout, out, dz, bdst, zeros_f32((npad,), dout.device), b * ho * wo, npad, npad, n)
-                bias_done = True
+        dz, bias_done = _conv_bwd_relu(ctx, geom, dout, out) if relu else (dout, False)
+        dx, fused = _conv_bwd_data(ctx, geom, x, weight, dz) if need_dx else (None, False)
+        dw = _conv_bwd_weight(ctx, geom, x, weight, dz) if need_dw and not fused else None
+        db = _conv_bwd_bias(ctx, geom, dz) if has_bias and need_db and not bias_done else None
+        return (dx, dw, db) + (None,) * 7
+
+
+def _conv_bwd_lazy_bn(ctx, geom, x, weight, lz_dz, lz_y, lz_k):
+    """The norm behind the layer left its apply step dout = k1 dz + k2 y + k3 (lz_k rows 2-4) to this backward: (dx, None) when one
+    launch formed both gradients from the operands, else (None, dout) - the step as its own launch, then the usual paths."""
+    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
+    m = b * h * w_
+    assert not ctx.cfg[2] and not ctx.cfg[3] and kh == 1 and kw == 1 and stride == 1 and pad == 0
+    wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
+    dx = torch.empty_like(x)
+    if ctx.wgrad_dst is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _hip.call_status(
+            "u2_conv1x1_bwd_fused_bn", x, lz_dz, lz_y, lz_k[2], lz_k[3], lz_k[4], wd, dx, ctx.wgrad_dst, m, cp, cp, npad, npad,
+            npad, cp, n, cin, cin, 1, 0) == 0:
+        return dx, None
+    dout = torch.empty_like(lz_y)   # not served after all
+    _hip.call("u2_norm_bwd_apply", lz_dz, None, lz_y, lz_k[2], lz_k[3], lz_k[4], dout, None, 1, m, npad, npad, 0, None, None)
+    return None, dout
+
+
+def _conv_bwd_relu(ctx, geom, dout, out):
+    """ReLU backward -> (dz, whether the bias gradient was added to its arena slice in the same pass over dout / out)"""
+    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
+    dz = torch.empty_like(dout)
+    if ctx.bias_dst is not None and ctx.needs_input_grad[2]:
+        _hip.call("u2_relu_bwd_colsum", dout, out, dz, ctx.bias_dst, zeros_f32((npad,), dout.device), b * ho * wo, npad, npad, n)
+        return dz, True
+    _hip.call("u2_relu_bwd", dout, out, dz, b * ho * wo * npad)
+    return dz, False
+
+
+def _conv_bwd_data(ctx, geom, x, weight, dz):
+    """-> (dx, whether the launch that formed it accumulated the weight gradient as well)"""
+    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
+    dst = ctx.wgrad_dst
+    if dst is not None and ctx.needs_input_grad[1] and kh == 1 and kw == 1 and stride == 1 and pad == 0 and n > 128 \
+            and b * h * w_ >= FUSED_BWD_MIN_PIXELS:
+        # both gradients of an expanding 1x1 layer in one pass over dz (u2_conv1x1_bwd_fused: dz is the large operand); the
+        # launcher answers 1 for a shape it does not serve
+        assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == n * cin
+        wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
+        dx = torch.empty_like(x)
+        if _hip.call_status("u2_conv1x1_bwd_fused", x, dz, wd, dx, dst, b * h * w_, cp, cp, npad, npad, npad, cp, n, cin, cin, 1,
+                            0) == 0:
+            return dx, True
+    # conv1 of a bottleneck behind an identity block: the data gradient g1 is formed, summed with the residual path's gradient,
+    # masked and reduced in one launch (u2_conv_dgrad_tail); what autograd carries to the previous block's tail is a placeholder,
+    # (dz, sums) wait in the tail's state
+    dx = _tail_launch(ctx, geom, dz, x, weight)
+    if dx is not None:
+        return dx, False
+    dx = torch.empty_like(x)
+    if ho == 1 and wo == 1 and pad == 0 and h == kh and w_ == kw and kh * kw > 1:
+        # "fully connected" conv (box head fc1): every input pixel meets exactly one tap, so the data gradient
+        # is the plain GEMM dx[b, (kh,kw,c)] = dz[b, :] . W[:, (kh,kw,c)]
+        wt = weight_fc_dgrad_layout(weight, cp, npad, ctx.param)
+        _hip.call("u2_conv_igemm", dz, wt, dx, None, None, 1, b, 1, npad, npad, b, 1, kh * kw * cp, kh * kw * cp,
+                  1, 1, 0, 0, 1, 1, 0, 0, ctx.variant)
+    else:
+        wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
+        _hip.call("u2_conv_igemm", dz, wd, dx, None, None, b, ho, wo, npad, npad, h, w_, cp, cp, kh, kw,
+                  kh - 1 - pad, kw - 1 - pad, 1, stride, 0, 0, ctx.variant)
+    return dx, False
+
+
+def _conv_bwd_weight(ctx, geom, x, weight, dz):
+    """The weight gradient: accumulated into the optimizer's arena on the side stream (-> None), or returned for autograd."""
+    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
+    dst, arena = ctx.wgrad_dst, ctx.arena
+
+    def scratch():   # in the kernel's layout, zeroed by the pool of the stream this runs on
+        dwk = zeros_f32((npad, kh * kw, cp), x.device)
+        _hip.call("u2_conv_wgrad", x, dz, dwk, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride, 0)
+        return dwk
+
+    if dst is not None:
+        assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == n * cin
+
+        def launch():
+            _hip.call("u2_conv_wgrad_into", x, dz, dst, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride,
+                      n, cin, cin, 1, 1, 0)
+    elif arena is not None and _WGRAD_SIDE:
+        # multi-tap filters: kernel-layout scratch, then accumulated into the arena slice by one transposing kernel (the strided
+        # torch add took 70-170 us per 3x3 layer, 1.3 ms per step) - all of it on the side stream
+        def launch():
+            dwk = scratch()
+            if kh * kw * (cp + 1) * 4 <= 64 * 1024 and arena.is_contiguous():
+                _hip.call("u2_wgrad_permute_add", dwk, arena, n, cin, kh * kw, cp)
             else:
-                _hip.call("u2_relu_bwd", dout, out, dz, dout.numel())
-        else:
-            dz = dout
-        dx = dw = db = None
-        fused = False
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and ctx.wgrad_dst is not None and kh == 1 and kw == 1 \
-                and stride == 1 and pad == 0 and n > 128 and b * h * w_ >= FUSED_BWD_MIN_PIXELS:
-            # both gradients of an expanding 1x1 layer in one pass over dz (u2_conv1x1_bwd_fused: dz is the large operand); the
-            # launcher answers 1 for a shape it does not serve
-            dst = ctx.wgrad_dst
-            assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == n * cin
-            wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
-            dx = torch.empty_like(x)
-            fused = _hip.call_status("u2_conv1x1_bwd_fused", x, dz, wd, dx, dst, b * h * w_, cp, cp, npad, npad, npad, cp, n, cin,
-                                     cin, 1, 0) == 0
-        if fused:
-            pass
-        elif ctx.needs_input_grad[0] and _tail_launch(ctx, dz, x, weight, relu, stride, pad):
-            # conv1 of a bottleneck behind an identity block: the data gradient g1 is formed, summed with the residual path's
-            # gradient, masked and reduced in one launch (u2_conv_dgrad_tail); what autograd carries to the previous block's
-            # tail is a placeholder, (dz, sums) wait in the tail's state
-            dx = ctx.tail.placeholder
-        elif ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            if ho == 1 and wo == 1 and pad == 0 and h == kh and w_ == kw and kh * kw > 1:
-                # "fully connected" conv (box head fc1): every input pixel meets exactly one tap, so the data gradient
-                # is the plain GEMM dx[b, (kh,kw,c)] = dz[b, :] . W[:, (kh,kw,c)]
-                wt = weight_fc_dgrad_layout(weight, cp, npad, ctx.param)
-                _hip.call("u2_conv_igemm", dz, wt, dx, None, None, 1, b, 1, npad, npad, b, 1, kh * kw * cp, kh * kw * cp,
-                          1, 1, 0, 0, 1, 1, 0, 0, ctx.variant)
-            else:
-                wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
-                _hip.call("u2_conv_igemm", dz, wd, dx, None, None, b, ho, wo, npad, npad, h, w_, cp, cp, kh, kw,
-                          kh - 1 - pad, kw - 1 - pad, 1, stride, 0, 0, ctx.variant)
-        if ctx.needs_input_grad[1] and not fused:
-            dst = ctx.wgrad_dst
-            arena = ctx.arena
-            if dst is not None:
-                assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == n * cin
-
-                def launch():
-                    _hip.call("u2_conv_wgrad_into", x, dz, dst, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride,
-                              n, cin, cin, 1, 1, 0)
-
-                _run_wgrad(x.device, (x, dz), launch)
-            elif arena is not None and _WGRAD_SIDE:
-                # multi-tap filters: kernel-layout scratch, then permuted into the arena slice - all of it on the side stream
-                def launch():
-                    # scratch from the (per-stream) zero pool, accumulated into the arena by one transposing kernel: the
-                    # strided torch add took 70-170 us per 3x3 layer, 1.3 ms per step
-                    dwk = zeros_f32((npad, kh * kw, cp), x.device)
-                    _hip.call("u2_conv_wgrad", x, dz, dwk, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride, 0)
-                    if kh * kw * (cp + 1) * 4 <= 64 * 1024 and arena.is_contiguous():
-                        _hip.call("u2_wgrad_permute_add", dwk, arena, n, cin, kh * kw, cp)
-                    else:
-                        arena.add_(dwk[:n, :, :cin].view(n, kh, kw, cin).permute(0, 3, 1, 2))
-
-                _run_wgrad(x.device, (x, dz), launch)
-            else:
-                dwk = zeros_f32((npad, kh * kw, cp), x.device)
-                _hip.call("u2_conv_wgrad", x, dz, dwk, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride, 0)
-                dw = dwk[:n, :, :cin].view(n, kh, kw, cin).permute(0, 3, 1, 2)
-        if has_bias and ctx.needs_input_grad[2] and not bias_done:
-            bdst = ctx.bias_dst
-            if bdst is not None and bdst.is_contiguous() and bdst.dtype == torch.float32 and bdst.numel() == n:
-                _hip.call("u2_colsum_add", dz, bdst, b * ho * wo, npad, npad, n)
-            else:
-                sums = zeros_f32((1, 2, npad), x.device)
-                _hip.call("u2_colstats", dz, sums, 1, b * ho * wo, npad, npad)
-                db = sums[0, 0, :n]
-        return dx, dw, db, None, None, None, None, None, None, None
+                arena.add_(dwk[:n, :, :cin].view(n, kh, kw, cin).permute(0, 3, 1, 2))
+    else:
+        return scratch()[:n, :, :cin].view(n, kh, kw, cin).permute(0, 3, 1, 2)
+    _run_wgrad(x.device, (x, dz), launch)
+    return None
 
 
-def _tail_launch(ctx, dz, x, weight, relu, stride, pad):
-    """_Conv2dFn.backward: launch the fused data gradient + tail reduce if this layer was marked for it in the forward pass, the
-    other consumer's gradient has been posted and the kernel serves the shape.  False: the caller takes the two launches."""
+def _conv_bwd_bias(ctx, geom, dz):
+    """The bias gradient: added into the bias' arena slice (-> None), or returned for autograd."""
+    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
+    if ctx.bias_dst is not None:
+        _hip.call("u2_colsum_add", dz, ctx.bias_dst, b * ho * wo, npad, npad, n)
+        return None
+    sums = zeros_f32((1, 2, npad), dz.device)
+    _hip.call("u2_colstats", dz, sums, 1, b * ho * wo, npad, npad)
+    return sums[0, 0, :n]
+
+
+def _tail_launch(ctx, geom, dz, x, weight):
+    """_conv_bwd_data: launch the fused data gradient + tail reduce if this layer was marked for it in the forward pass, the
+    other consumer's gradient has been posted and the kernel serves the shape; returns the placeholder autograd carries instead of
+    dx.  None: the caller takes the two launches."""
     tail = ctx.tail
     if tail is None or not TAIL_BWD_FUSE or tail.g2 is None or tail.result is not None:
-        return False
-    n, cin, kh, kw = weight.shape
-    b, h, w_, cp = x.shape
-    if relu or kh != 1 or kw != 1 or stride != 1 or pad != 0 or tuple(tail.g2.shape) != tuple(x.shape) \
-            or tuple(tail.y.shape) != tuple(x.shape) or not tail.g2.is_contiguous() or dz.shape[3] != n:
-        return False
+        return None
+    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
+    if ctx.cfg[2] or kh != 1 or kw != 1 or stride != 1 or pad != 0 or tuple(tail.g2.shape) != tuple(x.shape) \
+            or tuple(tail.y.shape) != tuple(x.shape) or not tail.g2.is_contiguous() or npad != n:
+        return None
     wd = weight_dgrad_layout(weight, cp, n, ctx.param)
     dzt = torch.empty_like(tail.y)
     sums = zeros_f32((2, cp), x.device)
     if _hip.call_status("u2_conv_dgrad_tail", dz, wd, tail.g2, tail.y, tail.bits, tail.mean, tail.invstd, dzt, sums, b, h, w_, n, n,
                         cp, cp, ctx.variant) != 0:
-        return False   # declined (shape, fill rule, switched off by the variant bits): nothing was written
-    ph = _lazy_placeholder(x.device, _TAIL_LAZY).expand(x.shape)
-    _TAIL_LAZY[(ph.device.index, ph.data_ptr())] = (ph, tail)
-    tail.result, tail.placeholder = (dzt, sums), ph
-    return True
+        return None   # declined (shape, fill rule, switched off by the variant bits): nothing was written
+    ph = deferred.post(deferred.TAIL, x.device, x.shape, tail)
+    tail.result = (dzt, sums)
+    return ph
 
 
 def _conv_bias(bias, round_bias):
@@ -637,8 +657,6 @@ class _StemConvFn(Function):
         b = len(images)
         ho, wo = (hpad + 6 - 7) // 2 + 1, (wpad + 6 - 7) // 2 + 1
         kp = _StemConvFn.KP
-        import ctypes
-
         col = torch.empty((b * ho * wo, kp), dtype=BF16, device=weight.device)
         is_u8 = images[0].dtype == torch.uint8
         for img in images:
@@ -689,11 +707,11 @@ class _BatchNormActFn(Function):
 
     @staticmethod
     def forward(ctx, y, stats, gamma, beta, running_mean, running_var, residual, relu, momentum, eps, grad_dst=None,
-                twin=False, sync=True, res_up=False, lazy_ok=False, tail=None, res_tail=None):
+                twin=False, sync=True, res_up=False, lazy_ok=None, tail=None, res_tail=None):
         _check_act(y)
         b, h, w, c = y.shape
         m = b * h * w
-        ctx.lazy_ok = lazy_ok
+        ctx.lazy_ok = lazy_ok   # None, or the _LazyLink between this node's backward and the guard hook on y
         world = _world() if sync else 1
         count, count_dev = float(m), None
         if world > 1:
@@ -780,18 +798,16 @@ class _BatchNormActFn(Function):
         coef = torch.empty((5, c), dtype=torch.float32, device=y.device)
         direct = ctx.grad_dst is not None
         dgamma, dbeta = ctx.grad_dst if direct else (coef[0], coef[1])
-        if ctx.lazy_ok and LAZY_BN_APPLY and (fuse or (not relu and not has_res)):
+        if ctx.lazy_ok is not None and LAZY_BN_APPLY and (fuse or (not relu and not has_res)):
             # the producing 1x1 conv evaluates the apply step dx = k1 dz + k2 y + k3 on its staged rows (u2_conv1x1_bwd_fused_bn,
             # round 5): only the coefficients (and dgamma / dbeta) are computed here, dx is never stored.  What autograd carries
             # to the conv is a one-element placeholder expanded to the shape; _Conv2dFn.backward finds the operands by its address.
             _hip.call("u2_bn_finalize_bwd", sums, count, ctx.count_dev, gamma, mean, invstd, local, dgamma, dbeta, coef[2], coef[3],
                       coef[4], c, int(direct))
-            ph = _lazy_placeholder(y.device).expand(y.shape)
-            _LAZY_GRADS[(ph.device.index, ph.data_ptr())] = (ph, dz if fuse else dout, y, coef)
-            if isinstance(ctx.lazy_ok, dict):
-                ctx.lazy_ok["key"] = (ph.device.index, ph.data_ptr())   # what _lazy_guard must see arrive at the conv output
-            return ph, None, (None if direct else dgamma), (None if direct else dbeta), None, None, (dz if fuse else None), \
-                None, None, None, None, None, None, None, None, None, None
+            ph = deferred.post(deferred.BN_APPLY, y.device, y.shape, (dz if fuse else dout, y, coef))
+            ctx.lazy_ok.posted = ph   # what _lazy_guard must see arrive at the conv output
+            return (ph, None, (None if direct else dgamma), (None if direct else dbeta), None, None, (dz if fuse else None)) \
+                + (None,) * 10
         dx = torch.empty_like(y)
         # finalize (coefficients of dx, dgamma / dbeta) + apply in one launch (round 4); coef[2:5] is scratch for the channel
         # counts the one-launch form does not serve
@@ -808,7 +824,7 @@ class _BatchNormActFn(Function):
                 _hip.call("u2_fpn_upsample_add_bwd", dout, dres, b, h, w, c)
         if direct:
             dgamma = dbeta = None
-        return dx, None, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None, None, None
+        return (dx, None, dgamma, dbeta, None, None, dres) + (None,) * 10
 
 
 def batch_norm_act(y, stats, gamma, beta, running_mean, running_var, residual=None, relu=False, momentum=0.1,
@@ -820,11 +836,11 @@ def batch_norm_act(y, stats, gamma, beta, running_mean, running_var, residual=No
     gd, bd = grad_slot(gamma), grad_slot(beta)
     grad_dst = (gd, bd) if gd is not None and bd is not None else None
     twin = (3 if twin == 3 else int(bool(twin))) if torch.is_grad_enabled() else 0
-    lazy_ok = bool(getattr(y, "_u2_lazy_ok", False)) and y.requires_grad and torch.is_grad_enabled()
-    if lazy_ok:
+    lazy_ok = None
+    if getattr(y, "_u2_lazy_ok", False) and y.requires_grad and torch.is_grad_enabled():
         # the conv output must reach its convolution's backward as the placeholder itself: a second consumer of y, or anything
         # else that makes autograd form a sum, would silently drop the deferred gradient - fail there and then instead
-        lazy_ok = {"key": None}
+        lazy_ok = _LazyLink()
         y.register_hook(functools.partial(_lazy_guard, lazy_ok))
     # a residual block's tail with exactly two handles: the next block's conv1 may form this tail's (dz, sums) in its data-gradient
     # launch (_TailState); a tail whose residual is such a block's second handle posts its residual gradient there
@@ -1302,12 +1318,10 @@ def rpn_losses(labels, match, gt_boxes, anchors_per_level, num_anchors, normaliz
 # --------------------------------------------------------------------------------------------
 # ROI ops
 # --------------------------------------------------------------------------------------------
-def _level_arrays(feats, scales):
-    import ctypes
-
-    nl = len(feats)
-    hs = (ctypes.c_int * nl)(*[f.shape[1] for f in feats])
-    ws = (ctypes.c_int * nl)(*[f.shape[2] for f in feats])
+def _level_arrays(shapes, scales):
+    nl = len(shapes)
+    hs = (ctypes.c_int * nl)(*[s[1] for s in shapes])
+    ws = (ctypes.c_int * nl)(*[s[2] for s in shapes])
     sc = (ctypes.c_float * nl)(*scales)
     return hs, ws, sc
 
@@ -1327,16 +1341,29 @@ def _roi_group(rois, levels, b, nl):
     return order, seg
 
 
+# what a ROIAlign node's backward leaves for the gather pass; event: the point of its stream at which the four tensors are complete
+_RoiSet = collections.namedtuple("_RoiSet", "rois order seg dout out_size grad_scale event", defaults=(None,))
+
+
+def _roi_sets_join(sets):
+    """The current stream waits for the sets left by ROIAlign nodes that ran on another stream (the mask head's) and keeps their
+    tensors alive."""
+    if not sets or not sets[0].dout.is_cuda:
+        return
+    here = torch.cuda.current_stream(sets[0].dout.device)
+    for st in sets:
+        if st.event is not None:
+            here.wait_event(st.event)
+            for t in st[:4]:
+                t.record_stream(here)
+
+
 def _roi_gather(shapes, scales, sets, device, level=None, addends=()):
-    """sets: [(rois, order, seg, dout, P, gscale)] (at most 4) -> per-level bf16 gradient maps, each written once.
+    """sets: [_RoiSet] (at most 4) -> per-level bf16 gradient maps, each written once.
     level = l: that level's map only (a one-element list), with up to two more bf16 gradient maps of its shape (`addends`: what
     the map's other readers produced) added in fp32 before the rounding (u2_roi_align_bwd_gather_sum)."""
-    import ctypes
-
     nl, ns = len(shapes), len(sets)
-    hs = (ctypes.c_int * nl)(*[s[1] for s in shapes])
-    ws = (ctypes.c_int * nl)(*[s[2] for s in shapes])
-    sc = (ctypes.c_float * nl)(*scales)
+    hs, ws, sc = _level_arrays(shapes, scales)
     lv = range(nl) if level is None else [level]
     gbuf = {l: torch.empty(shapes[l], dtype=BF16, device=device) for l in lv}
     ptrs = (ctypes.c_void_p * nl)(*[gbuf[l].data_ptr() if l in gbuf else None for l in range(nl)])
@@ -1369,13 +1396,11 @@ class _FanOutFn(Function):
     @staticmethod
     def backward(ctx, *grads):
         lazy = None
-        if _ROI_LAZY:   # one of the gradients may be the placeholder of a deferred ROIAlign gather (roi_grad_tap, round 6)
-            for g in grads:
-                if g is not None:
-                    ent = _ROI_LAZY.pop((g.device.index, g.data_ptr()), None)
-                    if ent is not None:
-                        assert lazy is None
-                        lazy, grads = ent, tuple(h for h in grads if h is not g)
+        for g in grads:   # one of the gradients may be the placeholder of a deferred ROIAlign gather (roi_grad_tap, round 6)
+            ent = deferred.take(deferred.ROI_GATHER, g) if g is not None else None
+            if ent is not None:
+                assert lazy is None
+                lazy, grads = ent, tuple(h for h in grads if h is not g)
         gs = [g.contiguous() for g in grads if g is not None]
         if not gs and lazy is None:
             return None, None
@@ -1394,13 +1419,7 @@ class _FanOutFn(Function):
             # the ROI poolers' gradient of this map is formed HERE, with the other readers' gradients added inside the gather
             # (fp32, one rounding): the separate u2_add_n pass read the gathered map back and the other two again
             shared, level = lazy
-            here = torch.cuda.current_stream(shared["device"])
-            for entry in shared["pend"]:
-                ev = entry[6] if len(entry) > 6 else None
-                if ev is not None:
-                    here.wait_event(ev)
-                    for t in entry[:4]:
-                        t.record_stream(here)
+            _roi_sets_join(shared["pend"])
             if any(g.dtype != BF16 for g in gs):
                 gs = [g.to(BF16) for g in gs]
             out = _roi_gather(shared["shapes"], shared["scales"], shared["pend"], shared["device"], level, gs)[0]
@@ -1442,26 +1461,15 @@ class _RoiGradTapFn(Function):
         st = ctx.state
         grads = list(gfeats)
         pend, st.pending = st.pending, []
-        if st.defer and ROI_SUM_FOLD and pend and len(pend) <= 4 and all(g is None for g in grads) and pend[0][3].is_cuda:
+        if st.defer and ROI_SUM_FOLD and pend and len(pend) <= 4 and all(g is None for g in grads) and pend[0].dout.is_cuda:
             # every tapped map is a fan_out handle: hand its _FanOutFn.backward a zero placeholder and let IT run the level's
             # gather, with the gradients of the map's other readers as addends (u2_roi_align_bwd_gather_sum)
-            dev = pend[0][3].device
+            dev = pend[0].dout.device
             shared = {"shapes": st.shapes, "scales": st.scales, "pend": pend, "device": dev}
-            out = []
-            for l, shape in enumerate(st.shapes):
-                ph = _lazy_placeholder(dev, _ROI_LAZY).expand(shape)
-                _ROI_LAZY[(dev.index, ph.data_ptr())] = (shared, l)
-                out.append(ph)
-            return (None, *out)
-        here = torch.cuda.current_stream(pend[0][3].device) if pend and pend[0][3].is_cuda else None
-        for entry in pend:  # a set left by a ROIAlign that ran on another stream (the mask head's): wait for it, keep it alive
-            ev = entry[6] if len(entry) > 6 else None
-            if ev is not None and here is not None:
-                here.wait_event(ev)
-                for t in entry[:4]:
-                    t.record_stream(here)
+            return (None, *[deferred.post(deferred.ROI_GATHER, dev, shape, (shared, l)) for l, shape in enumerate(st.shapes)])
+        _roi_sets_join(pend)
         for i in range(0, len(pend), 4):
-            gbuf = _roi_gather(st.shapes, st.scales, pend[i : i + 4], pend[i][3].device)
+            gbuf = _roi_gather(st.shapes, st.scales, pend[i : i + 4], pend[i].dout.device)
             grads = [g if old is None else old + g for old, g in zip(grads, gbuf)]
         return (None, *grads)
 
@@ -1480,21 +1488,17 @@ def roi_grad_tap(feats):
 
 
 FUSED_BWD_MIN_PIXELS = int(os.environ.get("U2_FUSED_BWD_MIN_PIXELS", "200000"))
-# the batch-norm backward apply step of an expanding 1x1 layer evaluated inside that layer's fused backward launch (0: separate)
+# Three backward folds hand autograd a zero placeholder and leave the gradient to the node that receives it (layers/deferred.py):
+# - the batch-norm backward apply step of an expanding 1x1 layer evaluated inside that layer's fused backward launch (0: separate)
 LAZY_BN_APPLY = os.environ.get("U2_LAZY_BN_APPLY", "1") != "0"
-_LAZY_GRADS = {}   # (device, placeholder address) -> (placeholder, dz, y, coefficients [5][C]: rows 2-4 = k1, k2, k3)
-
-
-# the ROIAlign gather of a tapped FPN map deferred to the map's _FanOutFn.backward (round 6): (device, placeholder address) ->
-# (shared state of the tap's backward, level); U2_ROI_SUM_FOLD=0: the tap gathers on the spot and u2_add_n sums afterwards
+# - the ROIAlign gather of a tapped FPN map deferred to the map's _FanOutFn.backward (round 6); U2_ROI_SUM_FOLD=0: the tap gathers
+#   on the spot and u2_add_n sums afterwards
 ROI_SUM_FOLD = os.environ.get("U2_ROI_SUM_FOLD", "1") != "0"
-_ROI_LAZY = {}
-# The backward reduce of a residual block's tail folded into the next block's conv1 data gradient (u2_conv_dgrad_tail;
-# U2_TAIL_BWD_FUSE=0: two launches).  The lazy placeholders run in the other direction here: the conv hands autograd a placeholder
-# for its input gradient, and the tail's backward, which receives it, finds (dz, sums) in its own state.
+# - the backward reduce of a residual block's tail folded into the next block's conv1 data gradient (u2_conv_dgrad_tail;
+#   U2_TAIL_BWD_FUSE=0: two launches).  The placeholder runs in the other direction here: the conv hands autograd a placeholder for
+#   its input gradient, and the tail's backward, which receives it, finds (dz, sums) in its own state.
 TAIL_BWD_FUSE = os.environ.get("U2_TAIL_BWD_FUSE", "1") != "0"
 _TAIL_SHAPES = ((64, 256), (128, 512), (256, 1024))   # (conv1 output channels, block width) the kernel serves
-_TAIL_LAZY = {}    # (device, placeholder address) -> (placeholder, _TailState)
 
 
 def set_tail_bwd_fuse(on):
@@ -1506,11 +1510,8 @@ def set_tail_bwd_fuse(on):
 class _TailState:
     """What a residual block's tail (_BatchNormActFn: residual, ReLU, two handles) shares with the two consumers of its output:
     its saved tensors for the conv1 that may run its reduce; g2, the residual gradient the next tail posts; result, the
-    (dz, sums) that conv1 formed, waiting for this tail's backward together with the placeholder autograd was handed."""
-    __slots__ = ("y", "bits", "mean", "invstd", "g2", "result", "placeholder")
-
-    def __init__(self):
-        self.y = self.bits = self.mean = self.invstd = self.g2 = self.result = self.placeholder = None
+    (dz, sums) that conv1 formed, waiting for this tail's backward (the placeholder autograd was handed is posted with this state)."""
+    y = bits = mean = invstd = g2 = result = None
 
 
 def _tail_take(tail, dout, dout2, dout3, y):
@@ -1518,90 +1519,69 @@ def _tail_take(tail, dout, dout2, dout3, y):
     placeholder and `dout2` the gradient it summed, untouched; None for the two-launch path.  Anything else that involves a
     placeholder (one that arrives at another layer, in another position or summed with a further gradient; a result whose
     placeholder never arrives) would drop a gradient silently and raises instead."""
-    grads = (dout, dout2, dout3)
-    hits = [i for i, g in enumerate(grads) if g is not None and (g.device.index, g.data_ptr()) in _TAIL_LAZY] if _TAIL_LAZY else []
+    hits = [i for i, g in enumerate((dout, dout2, dout3)) if g is not None and deferred.holds(deferred.TAIL, g)]
     pending = tail is not None and tail.result is not None
     if not hits and not pending:
         if tail is not None:
             tail.g2 = None
         return None
-    ent = _TAIL_LAZY.pop((dout.device.index, dout.data_ptr()), None) if hits == [0] else None
-    ok = ent is not None and pending and ent[1] is tail and dout2 is not None and dout3 is None and tail.g2 is not None \
+    posted = deferred.take(deferred.TAIL, dout) if hits == [0] else None
+    ok = pending and posted is tail and dout2 is not None and dout3 is None and tail.g2 is not None \
         and dout2.data_ptr() == tail.g2.data_ptr() and tuple(dout2.shape) == tuple(y.shape) and tuple(dout.shape) == tuple(y.shape)
     if not ok:
-        n = len(_TAIL_LAZY) + (1 if ent is not None else 0)
-        _TAIL_LAZY.clear()
+        n = deferred.drain()[deferred.TAIL] + (1 if posted is not None else 0)
         if tail is not None:
-            tail.g2 = tail.result = tail.placeholder = None
+            tail.g2 = tail.result = None
         raise RuntimeError("a residual tail's gradient formed by the next block's conv1 did not arrive as posted (placeholder in "
                            "positions %s, result pending: %s): a further consumer of the block output, or a changed gradient; "
                            "%d deferred tail gradients dropped - set U2_TAIL_BWD_FUSE=0 for such graphs" % (hits, pending, n))
     done = tail.result
-    tail.g2 = tail.result = tail.placeholder = None
+    tail.g2 = tail.result = None
     return done
 
 
-_LAZY_POOL = {}    # device index -> [zero-filled bf16 pool, next slot]: placeholders are ZEROS, so that a sum autograd forms with
-                   # one by accident is numerically the other addend (and is then caught by _lazy_guard / the checks below)
-_LAZY_SLOTS = 64
+class _LazyLink:
+    """Between a _BatchNormActFn node that may defer its apply step and the guard hook on its input: the placeholder that the node's
+    backward posted (None: it did not defer)."""
+    posted = None
 
 
-def _lazy_placeholder(device, registry=None):
-    registry = _LAZY_GRADS if registry is None else registry
-    ent = _LAZY_POOL.get(device.index)
-    if ent is None:
-        ent = _LAZY_POOL[device.index] = [torch.zeros(_LAZY_SLOTS, dtype=BF16, device=device), 0]
-    for _ in range(_LAZY_SLOTS):
-        slot = ent[0][ent[1] : ent[1] + 1]
-        ent[1] = (ent[1] + 1) % _LAZY_SLOTS
-        key = (device.index, slot.data_ptr())
-        if key not in _LAZY_GRADS and key not in _ROI_LAZY and key not in _TAIL_LAZY:
-            return slot
-    n = len(_LAZY_GRADS) + len(_ROI_LAZY) + len(_TAIL_LAZY)
-    _LAZY_GRADS.clear()
-    _ROI_LAZY.clear()
-    _TAIL_LAZY.clear()
-    raise RuntimeError("%d deferred gradients were not consumed by their consumers" % n)
-
-
-def _lazy_guard(state, grad):
+def _lazy_guard(link, grad):
     """Tensor hook on a conv output whose batch normalisation defers its backward apply step: the gradient autograd delivers
-    must be the placeholder that normalisation registered (`state["key"]`, None when it did not defer), untouched."""
-    key, state["key"] = state["key"], None
-    if key is not None and (grad.device.index, grad.data_ptr()) != key:
-        pend = len(_LAZY_GRADS)
-        _LAZY_GRADS.clear()
+    must be the placeholder that normalisation posted, untouched."""
+    posted, link.posted = link.posted, None
+    if posted is not None and not deferred.holds(deferred.BN_APPLY, grad, posted):
         raise RuntimeError("a convolution output with a deferred batch-norm gradient has a second consumer (autograd summed "
                            "the placeholder with another gradient); %d deferred gradients dropped - set U2_LAZY_BN_APPLY=0 "
-                           "for graphs that re-use conv outputs" % pend)
+                           "for graphs that re-use conv outputs" % sum(deferred.drain().values()))
     return None
+
+
+def _drain_deferred():
+    """Nothing of a finished (or failed) backward pass stays referenced: the deferred gradients, and the shared upsample gradient
+    of the semantic head.  Returns what was still deferred, per kind."""
+    global _UP2_BWD_LAST
+    _UP2_BWD_LAST = None
+    return deferred.drain()
 
 
 def reset_deferred_gradients(strict=True):
     """Start of a training step (solver.FlatSGD.zero_grad): nothing deferred may be left over from an earlier backward pass -
     one that raised midway leaves entries behind, which must not meet the addresses of the next pass."""
-    global _UP2_BWD_LAST
-    _UP2_BWD_LAST = None
-    if _LAZY_GRADS or _ROI_LAZY or _TAIL_LAZY:
-        n = len(_LAZY_GRADS) + len(_ROI_LAZY) + len(_TAIL_LAZY)
-        _LAZY_GRADS.clear()
-        _ROI_LAZY.clear()
-        _TAIL_LAZY.clear()
-        if strict:
-            raise RuntimeError("%d deferred gradients of an earlier backward pass were never consumed" % n)
+    n = sum(_drain_deferred().values())
+    if n and strict:
+        raise RuntimeError("%d deferred gradients of an earlier backward pass were never consumed" % n)
 
 
 def assert_no_deferred_gradients():
-    """After a backward pass: every deferred batch-norm gradient must have been consumed by its convolution."""
-    global _UP2_BWD_LAST
-    _UP2_BWD_LAST = None   # the shared upsample gradient of the semantic head: nothing of this pass stays referenced
-    if _LAZY_GRADS or _ROI_LAZY or _TAIL_LAZY:
-        n, m, t = len(_LAZY_GRADS), len(_ROI_LAZY), len(_TAIL_LAZY)
-        _LAZY_GRADS.clear()
-        _ROI_LAZY.clear()
-        _TAIL_LAZY.clear()
+    """After a backward pass: every deferred gradient must have been consumed by the node it was left to."""
+    left = _drain_deferred()
+    if any(left.values()):
         raise RuntimeError("%d deferred batch-norm gradients were not consumed by their convolutions, %d deferred ROIAlign "
-                           "gathers not by their fan-out nodes, %d residual-tail gradients not by their tails" % (n, m, t))
+                           "gathers not by their fan-out nodes, %d residual-tail gradients not by their tails"
+                           % (left[deferred.BN_APPLY], left[deferred.ROI_GATHER], left[deferred.TAIL]))
+
+
 ROI_ORDER_MIN = int(os.environ.get("U2_ROI_ORDER_MIN", "1000000000"))
 
 
@@ -1616,15 +1596,13 @@ class _ROIAlignFn(Function):
 
     @staticmethod
     def forward(ctx, rois, levels, out_size, scales, grad_scale, tap, *feats):
-        import ctypes
-
         nl = len(feats)
         for f in feats:
             _check_act(f)
         c = feats[0].shape[3]
         r = rois.shape[0]
         ptrs = (ctypes.c_void_p * nl)(*[f.data_ptr() for f in feats])
-        hs, ws, sc = _level_arrays(feats, scales)
+        hs, ws, sc = _level_arrays([f.shape for f in feats], scales)
         out = torch.empty((r, out_size, out_size, c), dtype=BF16, device=rois.device)
         order = _roi_process_order(rois, levels, feats[0].shape[0], nl) if r >= ROI_ORDER_MIN else None
         _hip.call("u2_roi_align_fwd", ptrs, hs, ws, sc, nl, rois.contiguous(), levels.contiguous(), order, out, r, c, out_size,
@@ -1636,8 +1614,6 @@ class _ROIAlignFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes
-
         rois, levels = ctx.saved_tensors
         out_size, scales, grad_scale, shapes = ctx.cfg
         nl = len(shapes)
@@ -1645,23 +1621,21 @@ class _ROIAlignFn(Function):
         r, c = rois.shape[0], shapes[0][3]
         none = (None,) * 6
         if ROI_ALIGN_BWD_ATOMIC:
-            hs = (ctypes.c_int * nl)(*[s[1] for s in shapes])
-            ws = (ctypes.c_int * nl)(*[s[2] for s in shapes])
-            sc = (ctypes.c_float * nl)(*scales)
+            hs, ws, sc = _level_arrays(shapes, scales)
             gbuf = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in shapes]
             ptrs = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbuf])
             _hip.call("u2_roi_align_bwd", ptrs, hs, ws, sc, nl, rois.contiguous(), levels.contiguous(), dout.contiguous(),
                       r, c, out_size, out_size, float(grad_scale))
             return (*none, *[g.to(BF16) for g in gbuf])
         order, seg = _roi_group(rois, levels, b, nl)
-        entry = (rois, order, seg, dout, out_size, grad_scale)
+        entry = _RoiSet(rois, order, seg, dout, out_size, grad_scale)
         tap = ctx.tap
         if tap is not None:  # deferred: the tap's backward gathers all pending sets at once
             tap.scales = scales
             if dout.is_cuda:  # the tap may run on another stream than this node: mark the point its inputs are complete at
                 ev = torch.cuda.Event()
                 ev.record()
-                entry = entry + (ev,)
+                entry = entry._replace(event=ev)
             tap.pending.append(entry)
             return (*none, *([None] * nl))
         return (*none, *_roi_gather(shapes, scales, [entry], dout.device))
