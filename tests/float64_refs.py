@@ -1,7 +1,9 @@
-"""Float64 reference helpers of tests/test_gpu_optim_resample_float64.py, tests/test_gpu_conv_float64.py and
-tests/test_gpu_inference_tails_float64.py, in a plain module so that the CPU tests of
+"""Float64 reference helpers of tests/test_gpu_optim_resample_float64.py, tests/test_gpu_conv_float64.py,
+tests/test_gpu_inference_tails_float64.py and tests/test_gpu_box_decisions_float64.py, in a plain module so that the CPU tests of
 tests/test_float64_refs_host.py check exactly what the GPU tests use.  Plain torch ops only; nothing here touches the HIP
 library.  Every function works on whatever device its inputs live on."""
+import math
+
 import torch
 import torch.nn.functional as TF
 
@@ -529,3 +531,351 @@ def mask_prob_case(n, side, c, k, seed=0):
     cls[0] = 0
     cls[-1] = k - 1
     return x, w, b, cls, ax, aw
+
+
+# ---- box decisions (tests/test_gpu_box_decisions_float64.py) ----
+def _inter_union(a, b):
+    """Areas of intersection and union of every pair, [len(a), len(b)] float64 (structures/boxes.py:312-358)."""
+    a, b = a.to(F64).cpu(), b.to(F64).cpu()
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    w = (torch.minimum(a[:, None, 2], b[None, :, 2]) - torch.maximum(a[:, None, 0], b[None, :, 0])).clamp(min=0)
+    h = (torch.minimum(a[:, None, 3], b[None, :, 3]) - torch.maximum(a[:, None, 1], b[None, :, 1])).clamp(min=0)
+    inter = w * h
+    return inter, area_a[:, None] + area_b[None, :] - inter
+
+
+def iou_ref(gt, cand):
+    """pairwise_iou (structures/boxes.py:312-358), [G, n], formed in float64 and rounded once to fp32; 0 where the boxes do not
+    intersect.
+
+    Exactness for integer coordinates below 2^11: every side is an integer below 2^11, every area, intersection and union an
+    integer below 2^23 - all fp32 numbers, whatever the order of the subtractions and the one product, so an fp32 routine
+    divides the exact integers `inter` and `union` and, dividing correctly rounded, returns RN32(inter / union).  Here the
+    quotient of the same two integers is rounded to float64 first and then to fp32; for a quotient of two p-bit numbers a
+    first rounding to q >= 2 p + 2 bits cannot change the second (the quotient is no midpoint of two p-bit numbers, and it
+    lies no nearer to one than 2^-(2p+1) relative), and 53 >= 2 * 24 + 2.  So float32(float64(inter) / float64(union)) IS the
+    value a correct fp32 routine returns, bit for bit: an approximate division is a failure, not a tolerance question."""
+    inter, union = _inter_union(gt, cand)
+    return torch.where(inter > 0, inter / union, torch.zeros((), dtype=F64)).float()
+
+
+def match_ref(gt, cand, lo, hi, allow_low_quality):
+    """Matcher (modeling/matcher.py:62-127) with thresholds [lo, hi] and labels [0, -1, 1] on iou_ref(gt, cand), for one image.
+    Returns (match [n] int64: the FIRST ground truth attaining the candidate's maximum; labels [n] int8: v < lo -> 0, v < hi -> -1,
+    else 1, v the fp32 maximum and lo, hi rounded to fp32 as the kernel receives them; mval [n] fp32).  Low-quality matches as the
+    reference has them: every candidate whose IoU with a ground truth EQUALS that ground truth's maximum over the candidates is
+    positive - so a ground truth that overlaps nothing (maximum 0) makes every candidate it does not overlap positive.
+    No ground truth: match 0, label 0, value 0."""
+    n = cand.shape[0]
+    if gt.shape[0] == 0:
+        return torch.zeros(n, dtype=torch.int64), torch.zeros(n, dtype=torch.int8), torch.zeros(n, dtype=torch.float32)
+    iou = iou_ref(gt, cand)
+    mval = iou.max(dim=0).values
+    rows = torch.arange(gt.shape[0])[:, None].expand_as(iou)
+    match = torch.where(iou == mval[None], rows, torch.full_like(rows, gt.shape[0])).min(dim=0).values
+    lo32, hi32 = torch.tensor(lo, dtype=torch.float32), torch.tensor(hi, dtype=torch.float32)
+    labels = torch.where(mval < lo32, 0, torch.where(mval < hi32, -1, 1)).to(torch.int8)
+    if allow_low_quality:
+        best = iou.max(dim=1).values
+        labels[(iou == best[:, None]).any(dim=0)] = 1
+    return match, labels, mval
+
+
+def nms_iou_ref(boxes):
+    """The IoU the NMS decides on (torchvision's nms, layers/nms.py:5-20): inter / union without the `inter > 0` guard of
+    pairwise_iou, so two zero-area boxes give 0 / 0 = NaN, which is not greater than any threshold.  float64, rounded to fp32
+    (iou_ref's argument)."""
+    inter, union = _inter_union(boxes, boxes)
+    return (inter / union).float()
+
+
+def nms_ref(boxes_sorted, groups, thr, max_keep):
+    """Greedy NMS within groups (layers/nms.py:5-20) over boxes already sorted by descending score: the positions kept, in order,
+    at most max_keep.  A later box of the same group is suppressed when RN32(iou) > float32(thr).
+    Only for thresholds whose fp32 value is at or below the decimal - 0.5 (exact), 0.65 (fp32 0.64999998), 0.7 (0.69999999):
+    then no RN32(iou) lies between the double and the fp32 threshold, and a routine comparing in either precision decides alike.
+    0.3 (fp32 0.30000001) is no such threshold: an IoU of exactly 3/10 rounds to that fp32 number, which exceeds the double 0.3."""
+    n = boxes_sorted.shape[0]
+    iou = nms_iou_ref(boxes_sorted)
+    groups = groups.cpu().long()
+    thr32 = torch.tensor(thr, dtype=torch.float32)
+    assert float(thr32) <= thr, "threshold outside the contract of nms_ref"
+    dead = torch.zeros(n, dtype=torch.bool)
+    later = torch.arange(n)
+    keep = []
+    for i in range(n):
+        if len(keep) >= max_keep:
+            break
+        if dead[i]:
+            continue
+        keep.append(i)
+        dead |= (iou[i] > thr32) & (groups == groups[i]) & (later > i)
+    return keep
+
+
+def levels_ref(boxes, min_level, max_level, canonical_size=224, canonical_level=4):
+    """assign_boxes_to_levels (modeling/poolers.py:23-59) in float64: floor(canonical_level + log2(sqrt(area) / canonical_size
+    + 1e-8)) clamped to [min_level, max_level], minus min_level.
+
+    Boundaries.  A box with sqrt(area) = 224 * 2^k lands on the upper side: in float64 the 1e-8 lifts the logarithm just above
+    k.  In fp32 area and its root are exact, s / 224 = 2^k exactly, and 1e-8 (2^-26.6) is below half an ulp of 2^k for k >= -2
+    (ulp 2^(k-23), half of it >= 2^-26 = 1.49e-8), so the sum rounds back to 2^k, whose log2 is k exactly: floor(4 + k) = 4 + k
+    as well.  For s = 28 (k = -3, half an ulp 7.5e-9) the sum rounds one ulp up and the logarithm stays at or just above -3:
+    level 1 either way."""
+    b = boxes.to(F64).cpu()
+    s = ((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])).sqrt()
+    lv = torch.floor(canonical_level + torch.log2(s / canonical_size + 1e-8))
+    return lv.clamp(min_level, max_level).long() - min_level
+
+
+def apply_deltas_ref(src, deltas, weights, clamp, sizes=None, img=None):
+    """Box2BoxTransform.apply_deltas (modeling/box_regression.py:78-116) and, with `sizes` [n_images, 2] (h, w), Boxes.clip
+    (structures/boxes.py:172-181) to the size of image img[i] (image 0 without `img`), in float64.  `clamp` is an operand the
+    fp32 operation holds in fp32 (the reference clamps an fp32 tensor with it), so it is rounded to fp32 first.  torch.clamp
+    keeps NaN, so a NaN delta gives NaN corners; the clip keeps NaN too.  Returns (unclipped [n, 4], clipped [n, 4] or None)."""
+    s, d = src.to(F64).cpu(), deltas.to(F64).cpu()
+    clamp = float(torch.tensor(clamp, dtype=torch.float32))
+    w, h = s[:, 2] - s[:, 0], s[:, 3] - s[:, 1]
+    cx, cy = s[:, 0] + 0.5 * w, s[:, 1] + 0.5 * h
+    dx, dy = d[:, 0] / weights[0], d[:, 1] / weights[1]
+    dw, dh = torch.clamp(d[:, 2] / weights[2], max=clamp), torch.clamp(d[:, 3] / weights[3], max=clamp)
+    pcx, pcy = dx * w + cx, dy * h + cy
+    pw, ph = torch.exp(dw) * w, torch.exp(dh) * h
+    raw = torch.stack([pcx - 0.5 * pw, pcy - 0.5 * ph, pcx + 0.5 * pw, pcy + 0.5 * ph], dim=1)
+    if sizes is None:
+        return raw, None
+    sz = sizes.to(F64).cpu()
+    sz = sz[img.cpu().long()] if img is not None else sz[:1].expand(raw.shape[0], 2)
+    hi = torch.stack([sz[:, 1], sz[:, 0], sz[:, 1], sz[:, 0]], dim=1)
+    return raw, torch.minimum(torch.clamp(raw, min=0), hi)
+
+
+def _crop_axis(lo, hi, p, size):
+    """One axis of the ROIAlign behind crop_and_resize: [p, size] float64, row b the summed bilinear weights on the `size` pixels of
+    the g = ceil((hi - lo) / p) samples of bin b, and g.  aligned=True: the ROI is shifted by -0.5; sample i of bin b sits at
+    lo - 0.5 + b bin + (i + 0.5) bin / g; a sample outside [-1, size] contributes nothing (but counts); otherwise it is clamped
+    to [0, size - 1] and split between floor and floor + 1."""
+    lo, hi = float(lo) - 0.5, float(hi) - 0.5
+    bin_ = (hi - lo) / p
+    g = int(math.ceil((hi - lo) / p))
+    out = torch.zeros((p, size), dtype=F64)
+    for b in range(p):
+        for i in range(max(g, 0)):
+            c = lo + b * bin_ + (i + 0.5) * bin_ / g
+            if c < -1.0 or c > size:
+                continue
+            c = max(c, 0.0)
+            low = int(c)
+            if low >= size - 1:
+                out[b, size - 1] += 1.0
+            else:
+                out[b, low] += 1.0 - (c - low)
+                out[b, low + 1] += c - low
+    return out, g
+
+
+def mask_crop_ref(masks, rois, p):
+    """BitMasks.crop_and_resize (structures/masks.py:191-218) before the decision, in float64: ROIAlign(p, scale 1, sampling
+    ratio 0, aligned) of mask rois[r, 0] inside box rois[r, 1:5] = (x1, y1, x2, y2).  The sampling grid has ceil(roi side / p)
+    points per bin and axis, the average divides by max(gh gw, 1) whether or not a sample fell outside, and an ROI without
+    extent has no samples: 0.  Returns [R, p, p] float64 averages; the target is `>= 0.5`."""
+    m = masks.to(F64).cpu()
+    r_ = rois.to(F64).cpu()
+    out = torch.zeros((r_.shape[0], p, p), dtype=F64)
+    for r in range(r_.shape[0]):
+        wy, gh = _crop_axis(r_[r, 2], r_[r, 4], p, m.shape[1])
+        wx, gw = _crop_axis(r_[r, 1], r_[r, 3], p, m.shape[2])
+        if gh > 0 and gw > 0:
+            out[r] = wy @ m[int(r_[r, 0])] @ wx.t() / (gh * gw)
+    return out
+
+
+# one ground truth and candidates whose IoU with it is exactly 1/2, 3/10, 7/10, 1, 0, 2/10, 4/10, 6/10, 8/10 and 0 (touching)
+EDGE_GT = torch.tensor([[0.0, 0.0, 10.0, 10.0]])
+EDGE_CAND = torch.tensor([[0.0, 0.0, 10.0, 5.0], [0.0, 0.0, 10.0, 3.0], [0.0, 0.0, 10.0, 7.0], [0.0, 0.0, 10.0, 10.0], [20.0, 20.0, 30.0, 30.0],
+                          [0.0, 0.0, 10.0, 2.0], [0.0, 0.0, 10.0, 4.0], [0.0, 0.0, 10.0, 6.0], [0.0, 0.0, 10.0, 8.0], [10.0, 0.0, 20.0, 10.0]])
+BOX_BIG = [0.0, 0.0, 2047.0, 2047.0]   # overlaps every box of the integer cases: what a padding row must not be read as
+
+
+def int_boxes(n, g, span=96, side=64, min_side=1):
+    """n random boxes with integer corners in [0, span + side], sides min_side .. side: overlaps, equal IoUs and exact ties are
+    common."""
+    xy = torch.randint(0, span, (n, 2), generator=g)
+    wh = torch.randint(min_side, side + 1, (n, 2), generator=g)
+    return torch.cat([xy, xy + wh], dim=1).float()
+
+
+def level_boundary_boxes():
+    """Boxes whose sqrt(area) is exactly s in {28, 56, 112, 224, 448, 896} - square, s/2 x 2 s and s/4 x 4 s, e.g. 56 x 224 -, squares
+    of side s (1 + 2^-10) and s (1 - 2^-10) (fp32 numbers; 2^-10 moves the logarithm by 1.4e-3, far beyond fp32 error), and two
+    boxes without area.  Origins are small integers, so every corner is an fp32 number.  [44, 4] fp32."""
+    rows = []
+    for i, s in enumerate((28.0, 56.0, 112.0, 224.0, 448.0, 896.0)):
+        x, y = 3.0 + i, 5.0 + 2 * i
+        for w, h in ((s, s), (s / 2, 2 * s), (4 * s, s / 4), (s * (1 + 2.0 ** -10), s * (1 + 2.0 ** -10)),
+                     (s * (1 - 2.0 ** -10), s * (1 - 2.0 ** -10)), (s * (1 + 2.0 ** -10), s), (s, s * (1 - 2.0 ** -10))):
+            rows.append([x, y, x + w, y + h])
+    rows += [[5.0, 5.0, 5.0, 9.0], [7.0, 7.0, 7.0, 7.0]]
+    b = torch.tensor(rows, dtype=F64)
+    assert torch.equal(b, b.float().to(F64))
+    return b.float()
+
+
+def _grid_boxes(n, x0=0, y0=400, per_row=30, pitch=20, side=10):
+    """n disjoint side x side boxes on a grid (they do not even touch)."""
+    i = torch.arange(n)
+    x, y = x0 + (i % per_row) * pitch, y0 + (i // per_row) * pitch
+    return torch.stack([x, y, x + side, y + side], dim=1).float()
+
+
+def nms_ladder(n, lead=0):
+    """`lead` isolated boxes, then a one-dimensional ladder of 10 x 10 boxes shifted by 3: neighbours have IoU 7/13 > 0.5, second
+    neighbours 4/16 - every second box of the ladder survives at 0.5, and which parity does flips with `lead`."""
+    b = torch.zeros((n, 4))
+    for i in range(n):
+        b[i] = torch.tensor([3.0 * i, 0.0, 3.0 * i + 10, 10.0]) if i >= lead else torch.tensor([20.0 * i, 100.0, 20.0 * i + 10, 110.0])
+    return b
+
+
+def _victims(x, y):
+    """Eleven boxes that each overlap A = (x, y, x + 100, y + 100) with IoU > 0.5 and one another with IoU <= 0.5 (asserted by the
+    host test): A grown by 90 to one side (IoU 100/190) four times, A grown by 20 all round (100^2 / 140^2), 51 % strips of A at
+    its four sides and through its middle both ways."""
+    a = [x, y, x + 100, y + 100]
+    out = [[x - 90, y, x + 100, y + 100], [x, y, x + 190, y + 100], [x, y - 90, x + 100, y + 100], [x, y, x + 100, y + 190],
+           [x - 20, y - 20, x + 120, y + 120],
+           [x, y, x + 51, y + 100], [x + 49, y, x + 100, y + 100], [x, y, x + 100, y + 51], [x, y + 49, x + 100, y + 100],
+           [x + 24, y, x + 75, y + 100], [x, y + 24, x + 100, y + 75]]
+    return torch.tensor(a, dtype=torch.float32), torch.tensor(out, dtype=torch.float32)
+
+
+def nms_lazy_column_case():
+    """300 boxes, threshold 0.5, one group.  A background of disjoint boxes, and two plots:
+    - position 3 holds A; its only victims sit at 130 .. 140 (eleven boxes that do not suppress one another) and at 200 (a copy
+      of the box at 130): a box kept in block 0 whose suppression row matters in block 2 and block 3 only;
+    - position 4 holds a strip that covers 56 % of a second box A' at position 5, so A' is suppressed; 150 .. 155 hold six boxes
+      that A' would suppress and the strip does not: they must all survive.
+    Returns (boxes [300, 4], expected suppressed positions)."""
+    b = _grid_boxes(300)
+    a, v = _victims(100, 100)
+    b[3] = a
+    b[130:141] = v
+    b[200] = v[0]
+    a2, v2 = _victims(500, 100)
+    b[4] = torch.tensor([500.0, 122.0, 600.0, 178.0])
+    b[5] = a2
+    b[150:156] = v2[torch.tensor([0, 1, 2, 3, 5, 6])]
+    return b, list(range(130, 141)) + [200, 5]
+
+
+def nms_helper_stride_case():
+    """400 boxes (seven blocks), threshold 0.5, all disjoint except that position 390 (block 6) overlaps the box at position 200
+    and position 395 the box at position 5 (IoU 7/13 each).  Every earlier box is kept, so 200 is also the 201st entry of the
+    kept list: while block 5 is resolved, the 192 helper threads gather the rows of the 320 boxes kept before it for block 6's
+    column, and entry 200 is reached only by a thread's second stride.  (With n = 300 no helper ever takes a second stride: the
+    last column is gathered when 192 boxes are kept.)  Returns (boxes [400, 4], suppressed positions)."""
+    b = _grid_boxes(400)
+    b[390] = b[200] + torch.tensor([3.0, 0.0, 3.0, 0.0])
+    b[395] = b[5] + torch.tensor([3.0, 0.0, 3.0, 0.0])
+    return b, [390, 395]
+
+
+NMS_EDGE_PAIRS = {0.5: ((10, 5), (10, 6)), 0.7: ((10, 7), (10, 8)), 0.65: ((20, 13), (20, 14))}
+
+
+def nms_threshold_pairs(thr):
+    """Four boxes: a square of side s and an s x k part of it with IoU k / s EXACTLY the threshold (1/2, 7/10, 13/20: not suppressed,
+    RN32(k / s) equals the fp32 threshold), then, 100 further right, the same square and a part one pixel taller (suppressed)."""
+    (s, k), (_, k1) = NMS_EDGE_PAIRS[thr]
+    return torch.tensor([[0, 0, s, s], [0, 0, s, k], [100, 0, 100 + s, s], [100, 0, 100 + s, k1]], dtype=torch.float32)
+
+
+CROP_H, CROP_W, CROP_MASKS = 100, 104, 3
+
+
+def mask_crop_exact_case(p, h=CROP_H, w=CROP_W, n_masks=CROP_MASKS, seed=0, per_side=None):
+    """Exact inputs of the mask crop: random binary masks [n_masks, h, w] and ROIs [R, 5] (mask index, x1, y1, x2, y2) with sides in
+    {p, 2 p, 3 p, 1.5 p} (1, 2, 3, 2 samples per bin and axis, spaced 1, 1, 1, 0.75) and corners that are multiples of 1/4.
+    Every sample coordinate is then a multiple of 1/8 below 2^8, every bilinear weight one of 1/8, every product one of 1/64 and
+    every bin sum one of 1/64 below 9: fp32 numbers in any order.  With integer corners the samples of the 2 p and 3 p ROIs sit ON
+    pixel centres, so their bin averages are k/4 and k/9 (the tests assert that 1/4, 2/4, 3/4, 4/9 and 5/9 occur).
+    Besides per_side inside ROIs of every side (the first half on integer corners) and 2 p x 3 p ones: ROIs hanging over each of
+    the four borders, ROIs wholly outside (left / above, right / below), an ROI without extent and one without width."""
+    g = torch.Generator().manual_seed(1000 * p + seed)
+    if per_side is None:
+        per_side = 40 if p == 1 else 10      # p = 1: one bin per ROI, so more ROIs for the same variety of averages
+    masks = (torch.rand((n_masks, h, w), generator=g) < 0.5).to(torch.uint8)
+    rois = []
+
+    def rnd(limit, integer):
+        v = float(torch.randint(0, max(int(limit), 0) + 1, (1,), generator=g))
+        return v if integer else min(v + float(torch.randint(0, 4, (1,), generator=g)) / 4, float(limit))
+
+    for sw_, sh_ in ((1.0, 1.0), (2.0, 2.0), (3.0, 3.0), (1.5, 1.5), (2.0, 3.0), (1.5, 1.0)):
+        rw, rh = sw_ * p, sh_ * p
+        for i in range(per_side):
+            integer = i < per_side // 2 and rw == int(rw) and rh == int(rh)
+            x, y = rnd(w - rw, integer), rnd(h - rh, integer)
+            rois.append([float(torch.randint(0, n_masks, (1,), generator=g)), x, y, x + rw, y + rh])
+    s = 2.0 * p
+    rois += [[0.0, -p - 0.25, 8.0, -p - 0.25 + s, 8.0 + s], [1.0, w - p + 0.25, 4.0, w - p + 0.25 + s, 4.0 + s],
+             [float(n_masks - 1), 6.0, -p - 0.5, 6.0 + s, -p - 0.5 + s], [0.0, 2.0, h - p + 0.5, 2.0 + s, h - p + 0.5 + s],
+             [1.0, -0.75, -0.75, -0.75 + 3 * p, -0.75 + 3 * p],
+             [0.0, -3.0 * p - 5, 10.0, -p - 5.0, 10.0 + s], [1.0, 10.0, -3.0 * p - 5, 10.0 + s, -p - 5.0],
+             [float(n_masks - 1), w + 3.0, h + 3.0, w + 3.0 + s, h + 3.0 + s],
+             [0.0, 10.0, 10.0, 10.0, 10.0], [1.0, 10.0, 10.0, 10.0, 10.0 + s]]
+    r = torch.tensor(rois, dtype=F64)
+    assert torch.equal(r, r.float().to(F64)) and torch.equal(r * 4, torch.round(r * 4))
+    return masks, r.float()
+
+
+def mask_crop_batch_case(p=7):
+    """35 images (the batched launcher takes 32 per launch: two chunks) in two sizes with two bitmaps each; images 0, 5, 31, 32 and
+    34 have ROIs (the exact-input kind, a border overhang among them), the other thirty none.
+    Returns (list of masks [2, h_i, w_i] uint8, rois [R, 5], roi_image [R] int32, sorted)."""
+    masks, rois, img = [], [], []
+    for i in range(35):
+        h, w = ((40, 44), (33, 29))[i % 2]
+        m, r = mask_crop_exact_case(p, h, w, 2, seed=100 + i, per_side=1)
+        masks.append(m)
+        if i in (0, 5, 31, 32, 34):
+            rois.append(r)
+            img += [i] * r.shape[0]
+    return masks, torch.cat(rois), torch.tensor(img, dtype=torch.int32)
+
+
+def mask_crop_random_case(seed=5, p=28, n=24, h=45, w=53):
+    """Random inputs of the mask crop: four h x w bitmaps of salt-and-pepper noise (flat regions would put whole runs of bins on
+    exactly 1/2 - two of four samples inside -, which is the exact-input case's business) and n ROIs with arbitrary fp32 corners,
+    a few of them hanging over the borders."""
+    g = torch.Generator().manual_seed(seed)
+    masks = (torch.rand((4, h, w), generator=g) < 0.5).to(torch.uint8)
+    x = torch.rand(n, generator=g) * (w + 4) - 4
+    y = torch.rand(n, generator=g) * (h + 4) - 4
+    bw = torch.minimum(2 + torch.rand(n, generator=g) * (w - 2), w + 4 - x)    # at most 4 pixels past any border: in the strip
+    bh = torch.minimum(2 + torch.rand(n, generator=g) * (h - 2), h + 4 - y)    # beyond it every sample is 0 or a clamped copy
+    idx = torch.randint(0, 4, (n,), generator=g).float()
+    return masks, torch.stack([idx, x, y, x + bw, y + bh], dim=1).float()
+
+
+def delta_random_case(n, seed, weights):
+    """Random inputs of the delta decode: source boxes of 2 .. 300 pixels a side, deltas N(0, 1) x weights / 2 on the centre and
+    N(0, 1) x weights on the sizes with some size deltas far above the clamp (x 3 and more of it) and some near -20 after the
+    division by the weight; image index in 0 .. 2."""
+    g = torch.Generator().manual_seed(seed)
+    xy = torch.rand((n, 2), generator=g) * 600 - 50
+    wh = 2 + torch.rand((n, 2), generator=g) * 298
+    src = torch.cat([xy, xy + wh], dim=1).float()
+    wt = torch.tensor(weights)
+    d = torch.randn((n, 4), generator=g) * wt * torch.tensor([0.5, 0.5, 1.0, 1.0])
+    big = torch.rand((n, 2), generator=g)
+    d[:, 2:] = torch.where(big > 0.9, (4 + 10 * torch.rand((n, 2), generator=g)) * wt[2:], d[:, 2:])
+    d[:, 2:] = torch.where(big < 0.1, (-20 + torch.randn((n, 2), generator=g)) * wt[2:], d[:, 2:])
+    img = torch.randint(0, 3, (n,), generator=g).to(torch.int32)
+    return src, d.float(), img
+
+
+CASCADE_WEIGHTS = [(10.0, 10.0, 5.0, 5.0), (20.0, 20.0, 10.0, 10.0), (30.0, 30.0, 15.0, 15.0)]
+SCALE_CLAMP = math.log(1000.0 / 16)
+DELTA_SIZES = [[64.0, 80.0], [50.0, 77.0], [333.0, 500.0]]   # (h, w) of three images

@@ -300,3 +300,209 @@ def test_mask_prob_ref_equals_conv2d_float64_and_channel_pick(n, side, c, k):
         ulp = 2.0 ** (torch.floor(torch.log2(a.clamp(min=2.0 ** -20))) - 7)
         half = (a >= 1) & (torch.remainder(a / ulp, 1.0) == 0.5)
         assert int(half.sum()) >= 3 and float(((a >= 1) & (a <= 8)).double().mean()) > 0.3
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# box decisions (tests/test_gpu_box_decisions_float64.py): each reference against the oracle's restatement of the same reference
+# routine - in float64 where the oracle takes it, else in fp32 on exact inputs, where the two precisions must agree bit for bit
+# ----------------------------------------------------------------------------------------------------------------------------
+EDGE_GT, EDGE_CAND = R.EDGE_GT, R.EDGE_CAND
+
+
+def test_iou_ref_equals_the_oracle_in_both_precisions():
+    """Integer boxes: iou_ref == oracle.pairwise_iou run in fp32 (exact operands, one correctly rounded division) and == the fp32
+    rounding of the oracle run in float64, bit for bit; fractional boxes: within one fp32 ulp of the float64 oracle."""
+    from oracle import ops as O
+
+    g = torch.Generator().manual_seed(1)
+    gt, cand = R.int_boxes(37, g), R.int_boxes(1000, g)
+    cand[:20] = gt[:20]                          # IoU 1
+    cand[20] = torch.tensor([2000.0, 2000.0, 2047.0, 2047.0])
+    ref = R.iou_ref(gt, cand)
+    assert ref.dtype == torch.float32 and ref.shape == (37, 1000)
+    assert torch.equal(ref, O.pairwise_iou(gt, cand)) and torch.equal(ref, O.pairwise_iou(gt.double(), cand.double()).float())
+    assert float(ref.max()) == 1.0 and float(ref[:, 20].max()) == 0.0 and 0.1 < float((ref > 0).float().mean()) < 0.9
+    edge = R.iou_ref(EDGE_GT, EDGE_CAND)[0]
+    want = torch.tensor([0.5, 0.3, 0.7, 1.0, 0.0, 0.2, 0.4, 0.6, 0.8, 0.0], dtype=torch.float32)   # touching boxes: 0
+    assert torch.equal(edge, want)
+    frac = torch.rand((50, 4), generator=g) * 50
+    frac[:, 2:] += frac[:, :2]
+    assert float((R.iou_ref(frac[:10], frac) - O.pairwise_iou(frac[:10].double(), frac.double())).abs().max()) <= 2.0 ** -24
+
+
+@pytest.mark.parametrize("lo,hi", [(0.3, 0.7), (0.5, 0.5)])
+@pytest.mark.parametrize("allow", [False, True])
+def test_match_ref_equals_the_oracle_matcher(lo, hi, allow):
+    """match_ref == oracle.matcher on oracle.pairwise_iou, fp32 and float64 (integer boxes): random boxes with many tied maxima,
+    identical ground truths (first index), IoUs exactly on 0.3 / 0.5 / 0.7 - RN32(3/10) == float32(0.3), so that candidate is NOT
+    below lo -, a ground truth that overlaps nothing (the low-quality rule then marks every candidate positive), no ground truth."""
+    from oracle import ops as O
+
+    g = torch.Generator().manual_seed(2)
+    gt, cand = R.int_boxes(6, g), R.int_boxes(700, g)
+    gt[4] = gt[1]
+    cases = [(gt, cand), (EDGE_GT, EDGE_CAND), (torch.cat([gt, torch.tensor([[1000.0, 1000.0, 1010.0, 1010.0]])]), cand),
+             (gt[:0], cand)]
+    for gi, ci in cases:
+        m, lab, val = R.match_ref(gi, ci, lo, hi, allow)
+        for dt in (torch.float32, torch.float64):
+            mq = O.pairwise_iou(gi.to(dt), ci.to(dt))
+            om, ol = O.matcher(mq.float(), [lo, hi], [0, -1, 1], allow)
+            assert torch.equal(m, om) and torch.equal(lab, ol), (gi.shape, dt)
+        if gi.shape[0]:
+            assert torch.equal(val, O.pairwise_iou(gi, ci).max(dim=0).values)
+    m, lab, _ = R.match_ref(EDGE_GT, EDGE_CAND, lo, hi, False)
+    if (lo, hi) == (0.3, 0.7):
+        assert lab.tolist() == [-1, -1, 1, 1, 0, 0, -1, -1, 1, 0]       # 3/10 is not below 0.3, 7/10 not below 0.7
+    else:
+        assert lab.tolist() == [1, 0, 1, 1, 0, 0, 0, 1, 1, 0]           # 1/2 is not below 0.5
+    m, lab, _ = R.match_ref(gt, cand, lo, hi, False)
+    assert not bool((m == 4).any()) and bool((m == 1).any())              # the identical pair: the first index
+    if allow:
+        assert bool((R.match_ref(cases[2][0], cand, lo, hi, True)[1] == 1).all())
+
+
+def test_nms_ref_equals_the_oracle_nms():
+    """nms_ref == oracle.ops.nms (the C restatement, fp32) on integer boxes: random grouped boxes at 0.5 / 0.65 / 0.7, every
+    construction the GPU test uses, and max_keep as a prefix of the unlimited result.  The constructions' own claims (which
+    positions die and why) are asserted here as well."""
+    from oracle import ops as O
+
+    def both(boxes, groups, thr, max_keep=None):
+        n = boxes.shape[0]
+        keep = R.nms_ref(boxes, groups, thr, n if max_keep is None else max_keep)
+        want = O.nms(boxes, torch.arange(n, 0, -1).float(), thr, groups).tolist()
+        assert keep == want[: len(keep)] and (max_keep is not None or len(keep) == len(want)), (n, thr)
+        return keep
+
+    g = torch.Generator().manual_seed(3)
+    for thr in (0.5, 0.65, 0.7):
+        b = R.int_boxes(300, g, span=32, min_side=40)
+        grp = torch.randint(0, 3, (300,), generator=g)
+        full = both(b, grp, thr)
+        assert 20 < len(full) < 280
+        assert both(b, grp, thr, 37) == full[:37]
+        pairs = R.nms_threshold_pairs(thr)
+        assert both(pairs, torch.zeros(4, dtype=torch.int64), thr) == [0, 1, 2]
+    zero = torch.zeros(300, dtype=torch.int64)
+    assert both(R.nms_ladder(300), zero, 0.5) == list(range(0, 300, 2))
+    assert both(R.nms_ladder(300, 1), zero, 0.5) == [0] + list(range(1, 300, 2))
+    b, dead = R.nms_lazy_column_case()
+    assert both(b, zero, 0.5) == [i for i in range(300) if i not in dead]
+    iou = R.nms_iou_ref(b)
+    for v in list(range(130, 141)):                 # suppressed by position 3 and by nothing else
+        assert [i for i in range(v) if float(iou[i, v]) > 0.5] == [3], v
+    assert [i for i in range(200) if float(iou[i, 200]) > 0.5] == [3, 130]
+    assert float(iou[4, 5]) > 0.5
+    for v in range(150, 156):                       # position 5 would suppress them; nothing else does
+        assert [i for i in range(v) if float(iou[i, v]) > 0.5] == [5], v
+    b, dead = R.nms_helper_stride_case()
+    assert both(b, torch.zeros(400, dtype=torch.int64), 0.5) == [i for i in range(400) if i not in dead]
+    iou = R.nms_iou_ref(b)
+    assert [i for i in range(390) if float(iou[i, 390]) > 0.5] == [200] and [i for i in range(395) if float(iou[i, 395]) > 0.5] == [5]
+    same = torch.tensor([[5.0, 5.0, 25.0, 30.0]]).repeat(129, 1)
+    assert both(same, torch.zeros(129, dtype=torch.int64), 0.5) == [0]
+    assert both(same, torch.arange(129) % 3, 0.5) == [0, 1, 2]
+    flat = torch.tensor([[10.0, 10.0, 10.0, 20.0]] * 3 + [[5.0, 5.0, 5.0, 5.0]] * 2 + [[8.0, 8.0, 12.0, 22.0]])
+    assert both(flat, torch.zeros(6, dtype=torch.int64), 0.5) == list(range(6))     # 0 / 0 suppresses nothing
+    assert both(R._grid_boxes(300), zero, 0.5, 100) == list(range(100))
+
+
+def test_levels_ref_equals_the_oracle_on_float64_inputs_and_at_the_boundaries():
+    """levels_ref == oracle.assign_boxes_to_levels on the same boxes cast to float64, and on the boundary boxes also == the oracle
+    in fp32; the boundary boxes land on the upper side."""
+    from oracle import ops as O
+
+    b = R.level_boundary_boxes()
+    g = torch.Generator().manual_seed(4)
+    rnd = torch.rand((500, 4), generator=g) * 900
+    rnd[:, 2:] = rnd[:, :2] + torch.rand((500, 2), generator=g) ** 3 * 1200
+    for lo, hi in ((2, 5), (1, 6)):
+        for boxes in (b, rnd):
+            assert torch.equal(R.levels_ref(boxes, lo, hi), O.assign_boxes_to_levels(boxes.double(), lo, hi))
+        assert torch.equal(R.levels_ref(b, lo, hi), O.assign_boxes_to_levels(b, lo, hi))
+    lv = R.levels_ref(b, 1, 6) + 1
+    assert lv[0:42:7].tolist() == lv[1:42:7].tolist() == lv[2:42:7].tolist() == [1, 2, 3, 4, 5, 6]     # on the boundary: upper side
+    assert lv[3:42:7].tolist() == lv[5:42:7].tolist() == [1, 2, 3, 4, 5, 6]
+    assert lv[4:42:7].tolist() == lv[6:42:7].tolist() == [1, 1, 2, 3, 4, 5]                             # just below
+    assert lv[42:].tolist() == [1, 1]
+
+
+def test_apply_deltas_ref_vs_the_oracle():
+    """apply_deltas_ref against oracle.apply_deltas + clip_boxes (fp32 only): bit for bit on exact inputs (zero deltas, whole
+    translations, boxes beyond the image), within fp32 error on random ones, and NaN where the oracle has NaN."""
+    from oracle import ops as O
+
+    g = torch.Generator().manual_seed(6)
+    src = torch.randint(-40, 400, (60, 2), generator=g).float() / 2
+    src = torch.cat([src, src + torch.randint(1, 200, (60, 2), generator=g).float() / 2], dim=1)
+    for wt in R.CASCADE_WEIGHTS:
+        km = torch.randint(-3, 4, (60, 2), generator=g).float()
+        d = torch.cat([km * torch.tensor(wt[:2]), torch.zeros((60, 2))], dim=1)
+        raw, clipped = R.apply_deltas_ref(src, d, wt, R.SCALE_CLAMP, torch.tensor(R.DELTA_SIZES[:1]))
+        o_raw = O.apply_deltas(d, src, wt)
+        assert torch.equal(raw, o_raw.double()) and torch.equal(clipped, O.clip_boxes(o_raw, R.DELTA_SIZES[0]).double())
+        w_, h_ = src[:, 2] - src[:, 0], src[:, 3] - src[:, 1]
+        assert torch.equal(raw.float(), src + torch.stack([km[:, 0] * w_, km[:, 1] * h_] * 2, dim=1))
+        s2, d2, img = R.delta_random_case(400, 7, wt)
+        raw, clipped = R.apply_deltas_ref(s2, d2, wt, R.SCALE_CLAMP, torch.tensor(R.DELTA_SIZES), img)
+        o_raw = O.apply_deltas(d2, s2, wt)
+        assert float(((o_raw.double() - raw).abs() / raw.abs().clamp(min=1)).max()) < 1e-5
+        assert float(raw.abs().max()) > 3000 and float((d2[:, 2:] / torch.tensor(wt[2:])).min()) < -19
+        for i in range(3):
+            sel = img == i
+            assert float((O.clip_boxes(o_raw[sel], R.DELTA_SIZES[i]).double() - clipped[sel]).abs().max()) < 1e-3
+            assert float(clipped[sel].min()) == 0.0 and float(clipped[sel][:, 0::2].max()) == R.DELTA_SIZES[i][1]
+        for c in range(4):
+            d3 = d2[:8].clone()
+            d3[c, c] = float("nan")
+            raw, clipped = R.apply_deltas_ref(s2[:8], d3, wt, R.SCALE_CLAMP, torch.tensor(R.DELTA_SIZES[:1]))
+            o_raw = O.apply_deltas(d3, s2[:8], wt)
+            assert torch.equal(torch.isnan(raw), torch.isnan(o_raw)) and int(torch.isnan(raw).any(dim=1).sum()) == 1
+            assert bool(torch.isnan(raw[c, c % 2::2]).all())
+
+
+@pytest.mark.parametrize("p", [1, 7, 28])
+def test_mask_crop_ref_equals_the_oracle_on_exact_inputs(p):
+    """mask_crop_ref >= 0.5 == oracle.crop_and_resize_masks (the C ROIAlign in fp32) on the exact-input case, where fp32 has no
+    rounding; the fp32 averages themselves agree to the last bit of the one division; the case's claims hold: bin sums are fp32
+    numbers, averages exactly 1/4, 2/4, 3/4, 4/9 and 5/9 occur, outside and empty ROIs give 0."""
+    from oracle import ops as O
+
+    masks, rois = R.mask_crop_exact_case(p)
+    avg = R.mask_crop_ref(masks, rois, p)
+    assert avg.shape == (rois.shape[0], p, p)
+    want = O.roi_align(masks[:, None].float(), rois, p, 1.0)[:, 0]
+    assert torch.equal(avg.float(), want)
+    for r in range(rois.shape[0]):     # the C routine takes one mask per ROI row in crop_and_resize_masks: feed it that way
+        got = O.crop_and_resize_masks(masks[int(rois[r, 0])][None].bool(), rois[r: r + 1, 1:], p)
+        assert torch.equal(got[0], avg[r] >= 0.5), r
+    sums = avg * 36           # every grid has 1, 4, 6 or 9 samples a bin... times 36: an integer multiple of 1/64 when exact
+    assert torch.equal(sums * 64, torch.round(sums * 64))
+    seen = set(avg.flatten().tolist())
+    for v in (0.25, 0.5, 0.75, 4.0 / 9, 5.0 / 9):
+        assert v in seen, (p, v)
+    assert not bool(avg[-5:].any()) and bool(avg[-10:-5].any())
+    assert 0.2 < float((avg >= 0.5).double().mean()) < 0.8
+
+
+def test_mask_crop_batch_case_layout():
+    masks, rois, img = R.mask_crop_batch_case()
+    assert len(masks) == 35 and len({tuple(m.shape) for m in masks}) == 2
+    assert sorted(set(img.tolist())) == [0, 5, 31, 32, 34] and img.tolist() == sorted(img.tolist()) and rois.shape[0] == img.numel()
+
+
+def test_mask_crop_random_case_margin_on_the_cpu():
+    """The random-input crop: the share of pixels whose float64 average lies within 4 x max |fp32 form - float64| of 0.5 is below
+    0.1 %, and the reference's own fp32 form decides like float64 everywhere else."""
+    from oracle import ops as O
+
+    masks, rois = R.mask_crop_random_case()
+    avg = R.mask_crop_ref(masks, rois, 28)
+    v32 = O.roi_align(masks[:, None].float(), rois, 28, 1.0)[:, 0].double()
+    margin = 4 * float((v32 - avg).abs().max())
+    assert 0 < margin < 1e-4      # a few ulps of a coordinate near 50 (3.8e-6 each) times a slope of at most 1 per pixel
+    near = (avg - 0.5).abs() < margin
+    assert float(near.double().mean()) <= 1e-3
+    assert torch.equal((v32 >= 0.5)[~near], (avg >= 0.5)[~near])
+    assert 0.2 < float((avg >= 0.5).double().mean()) < 0.8

@@ -804,8 +804,9 @@ __global__ void apply_deltas_kernel(const float* __restrict__ src, const float* 
   const float cx = s[0] + 0.5f * w, cy = s[1] + 0.5f * h;
   const float dx = d[0] / wx, dy = d[1] / wy;
   float dw = d[2] / ww, dh = d[3] / wh;
-  dw = fminf(dw, clamp);
-  dh = fminf(dh, clamp);
+  // torch.clamp(max=) of the reference keeps NaN (fminf would return the clamp: a diverged size delta decoded as a finite box)
+  dw = dw > clamp ? clamp : dw;
+  dh = dh > clamp ? clamp : dh;
   const float pcx = dx * w + cx, pcy = dy * h + cy;
   const float pw = expf(dw) * w, ph = expf(dh) * h;
   float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
@@ -850,8 +851,8 @@ __global__ __launch_bounds__(256) void rpn_decode_kernel(const RpnDecodeArgs a) 
     const float cx = s[0] + 0.5f * w, cy = s[1] + 0.5f * h;
     const float dx = d0 / a.wx, dy = d1 / a.wy;
     float dw = d2 / a.ww, dh = d3 / a.wh;
-    dw = fminf(dw, a.clamp);
-    dh = fminf(dh, a.clamp);
+    dw = dw > a.clamp ? a.clamp : dw;   // keeps NaN, as above: the finite test below has to see it
+    dh = dh > a.clamp ? a.clamp : dh;
     const float pcx = dx * w + cx, pcy = dy * h + cy;
     const float pw = expf(dw) * w, ph = expf(dh) * h;
     x1 = pcx - 0.5f * pw; y1 = pcy - 0.5f * ph; x2 = pcx + 0.5f * pw; y2 = pcy + 0.5f * ph;
