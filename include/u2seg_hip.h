@@ -394,6 +394,29 @@ int u2_rpn_loss_level(const void* obj, const void* dlt, const void* labels, cons
                       int Atot, int lvl_off, int G, float gscale, void* stream);
 int u2_box_reg_l1(const void* pred, const float* prop, const float* gtb, const void* labels, void* dpred, float* loss,
                   int R, int LP, int bg_label, float wx, float wy, float ww, float wh, float gscale, void* stream);
+/* FastRCNNOutputLayers.sigmoid_cross_entropy_loss (roi_heads/fast_rcnn.py:386-422) in the layout of u2_softmax_ce: logits bf16
+ * [R][LP], NC = K + 1 valid columns of which the last is the background (it takes no part), labels int64.  Per foreground
+ * column c < NC - 1, with t = (labels[r] == c) and w = class_weight[c] (fp32 [>= NC - 1]; NULL = 1, the federated mask otherwise):
+ * loss_sum += w (max(x, 0) - x t + log1p(exp(-|x|))),  dlogits = (sigmoid(x) - t) w gscale; dlogits is exactly 0 in the
+ * background column, in the pad columns (whatever they hold) and where w == 0.  counters (NULL = none): the five counts of
+ * u2_softmax_ce_stats, same definition (argmax over all NC valid logits).  One float atomic per work-group; R == 0 launches
+ * nothing. */
+int u2_sigmoid_ce(const void* logits, const void* labels, const float* class_weight, void* dlogits, float* loss_sum, int R,
+                  int NC, int LP, float gscale, int* counters, int bg_label, void* stream);
+/* The box heads' other regression losses (modeling/box_regression.py:310-369) over foreground rows (0 <= label < bg_label),
+ * class agnostic: pred bf16 [R][LP] with 4 valid columns.  kind U2_BOXLOSS_SMOOTH_L1: smooth-L1 with beta > 0 on
+ * pred - get_deltas(prop, gtb).  GIOU / DIOU / CIOU: the loss of layers/losses.py (GIoU: 1 - I/(U + eps) + (C - U)/(C + eps),
+ * eps = 1e-7 throughout) on apply_deltas(pred, prop) (box_regression.py:78-116: deltas / weights, dw and dh clamped at
+ * scale_clamp from above) against gtb; dpred is the gradient through the decode (0 through a clamped dw / dh; CIoU's alpha
+ * constant), times gscale, and 0 in background rows and in columns >= 4.  loss is accumulated.  An unknown kind, or smooth-L1
+ * with beta <= 0 (u2_box_reg_l1 serves that), returns -1. */
+#define U2_BOXLOSS_SMOOTH_L1 0
+#define U2_BOXLOSS_GIOU 1
+#define U2_BOXLOSS_DIOU 2
+#define U2_BOXLOSS_CIOU 3
+int u2_box_reg_loss(int kind, const void* pred, const float* prop, const float* gtb, const void* labels, void* dpred,
+                    float* loss, int R, int LP, int bg_label, float wx, float wy, float ww, float wh, float beta,
+                    float scale_clamp, float gscale, void* stream);
 
 /* ---- ROI bookkeeping (roi.hip) -----------------------------------------------------------------
  * layers/roi_align.py:49-65 via modeling/poolers.py:206-263; structures/masks.py:191-218; modeling/poolers.py:23-59;

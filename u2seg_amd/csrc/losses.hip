@@ -632,6 +632,232 @@ __global__ __launch_bounds__(256) void box_reg_l1_kernel(const bf16_t* __restric
   if (threadIdx.x == 0) atomicAdd(loss, s);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Per-class sigmoid cross-entropy (fast_rcnn.py:386-422): logits [R][LP] bf16, NC valid columns, the last of them the
+// background, which takes no part; labels int64; cw fp32 [NC - 1] or NULL (= 1): the federated mask.
+//   loss_sum += sum_{r, c < NC-1} cw[c] (max(x,0) - x t + log1p(exp(-|x|))),  dlogits = (sigmoid(x) - t) cw[c] gscale
+// with one e = exp(-|x|) serving both: sigmoid(x) = 1 / (1 + e) for x >= 0 and e / (1 + e) below.
+//
+// One wave per row, rows walked with the grid's stride; no value crosses lanes except the loss (one atomic per work-group)
+// and, with STATS, the row's argmax over the NC valid logits (CeCounts, as in softmax_ce_kernel).  Where LP % 8 == 0 a lane
+// moves 16-byte pieces of the row, and up to LP = 1024 it keeps the weights of its two pieces in registers across rows.
+// ------------------------------------------------------------------------------------------------
+struct SigRow {
+  float loss = 0.f;
+  float mxv = -INFINITY;   // the lane's largest valid logit so far and the lowest column holding it
+  int mxc = 0x7fffffff;
+};
+
+// one column: x = logit, c its column, t the row's label, w the column's weight (ignored for c >= K)
+template <bool STATS>
+__device__ __forceinline__ float sig_column(float x, int c, int t, int K, int NC, float w, float gscale, SigRow& row) {
+  if constexpr (STATS) {
+    if (c < NC && x > row.mxv) { row.mxv = x; row.mxc = c; }  // (columns arrive in rising order: the first maximum stays)
+  }
+  if (c >= K) return 0.f;   // background and pads: no loss, gradient exactly 0 whatever they hold
+  const float tt = c == t ? 1.f : 0.f;
+  const float e = __expf(-fabsf(x));
+  const float inv = 1.f / (1.f + e);
+  const float sg = x >= 0.f ? inv : e * inv;
+  row.loss += w * (fmaxf(x, 0.f) - x * tt + log1pf(e));
+  return (sg - tt) * w * gscale;
+}
+
+template <bool STATS>
+__device__ __forceinline__ void sig_piece(const bf16_t* __restrict__ zr, bf16_t* __restrict__ dr, int c0, int t, int K, int NC,
+                                          const float (&w)[8], float gscale, SigRow& row) {
+  bf16_t raw[8], ov[8];
+  *reinterpret_cast<uint4*>(raw) = *reinterpret_cast<const uint4*>(zr + c0);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ov[e] = f2bf(sig_column<STATS>(bf2f(raw[e]), c0 + e, t, K, NC, w[e], gscale, row));
+  *reinterpret_cast<uint4*>(dr + c0) = *reinterpret_cast<const uint4*>(ov);
+}
+
+__device__ __forceinline__ void sig_weights(const float* __restrict__ cw, int c0, int K, float (&w)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) w[e] = (c0 + e < K) ? (cw ? cw[c0 + e] : 1.f) : 0.f;
+}
+
+template <bool STATS>
+__global__ __launch_bounds__(256) void sigmoid_ce_kernel(const bf16_t* __restrict__ logits, const long long* __restrict__ labels,
+                                                         const float* __restrict__ cw, bf16_t* __restrict__ dlogits,
+                                                         float* __restrict__ loss_sum, int R, int NC, int LP, float gscale,
+                                                         int* __restrict__ counters, int bg) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63;
+  const int K = NC - 1;
+  const int row0 = blockIdx.x * 4 + (threadIdx.x >> 6), rstep = gridDim.x * 4;
+  const int chunks = LP >> 3;
+  const bool vec = (LP & 7) == 0, resident = vec && chunks <= 128;
+  float w[2][8];
+  if (resident) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) sig_weights(cw, (it * 64 + lane) * 8, K, w[it]);
+  }
+  CeCounts cnt;
+  float loss_acc = 0.f;
+  for (int r = row0; r < R; r += rstep) {
+    const bf16_t* zr = logits + (size_t)r * LP;
+    bf16_t* dr = dlogits + (size_t)r * LP;
+    const int t = (int)labels[r];
+    SigRow row;
+    if (resident) {
+#pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int ch = it * 64 + lane;
+        if (ch < chunks) sig_piece<STATS>(zr, dr, ch * 8, t, K, NC, w[it], gscale, row);
+      }
+    } else if (vec) {
+      for (int ch = lane; ch < chunks; ch += 64) {
+        float wc[8];
+        sig_weights(cw, ch * 8, K, wc);
+        sig_piece<STATS>(zr, dr, ch * 8, t, K, NC, wc, gscale, row);
+      }
+    } else {
+      for (int c = lane; c < LP; c += 64) {
+        const float wc = c < K ? (cw ? cw[c] : 1.f) : 0.f;
+        dr[c] = f2bf(sig_column<STATS>(bf2f(zr[c]), c, t, K, NC, wc, gscale, row));
+      }
+    }
+    loss_acc += row.loss;
+    if constexpr (STATS) {
+      const float mx = wave_max(row.mxv);
+      cnt.add(wave_imin(row.mxv == mx ? row.mxc : 0x7fffffff), t, bg);
+    }
+  }
+  const float s = block_sum_256(loss_acc, red);
+  if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss_sum, s);
+  if constexpr (STATS) cnt.send_group(counters);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The box heads' regression losses other than plain L1 (box_regression.py:310-369), class agnostic, one thread per row.
+// SMOOTH_L1 (beta > 0): on pred - get_deltas(prop, gt).  GIOU / DIOU / CIOU: the box is decoded as apply_deltas does
+// (box_regression.py:78-116), the loss of layers/losses.py:5-133 is evaluated against gt (GIoU: 1 - I/(U + eps) + (C - U)/(C + eps))
+// and its gradient is taken back through the decode by hand: d/dx1 .. d/dy2 of the loss, then centre / size, then the deltas.
+// torch's max / min hand half the gradient to each side of a tie; tie() does the same.  A clamped dw / dh passes nothing.
+// ------------------------------------------------------------------------------------------------
+constexpr float BOXLOSS_EPS = 1e-7f;
+
+__device__ __forceinline__ float tie(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }  // d max(a, b) / da
+
+template <int KIND>
+__device__ __forceinline__ float iou_family_loss(const float* b, const float* g, float* gb) {
+  const float x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
+  const float x1g = g[0], y1g = g[1], x2g = g[2], y2g = g[3];
+  // intersection, zero unless both overlaps are strictly positive
+  const float iw = fminf(x2, x2g) - fmaxf(x1, x1g), ih = fminf(y2, y2g) - fmaxf(y1, y1g);
+  const bool hit = ih > 0.f && iw > 0.f;
+  const float I = hit ? iw * ih : 0.f;
+  const float m = hit ? 1.f : 0.f;
+  const float dI[4] = {-ih * tie(x1, x1g) * m, -iw * tie(y1, y1g) * m, ih * tie(x2g, x2) * m, iw * tie(y2g, y2) * m};
+  const float bw = x2 - x1, bh = y2 - y1;
+  const float dA[4] = {-bh, -bw, bh, bw};
+  // smallest enclosing box
+  const float cw = fmaxf(x2, x2g) - fminf(x1, x1g), ch = fmaxf(y2, y2g) - fminf(y1, y1g);
+  const float dcw[4] = {-tie(x1g, x1), 0.f, tie(x2, x2g), 0.f};
+  const float dch[4] = {0.f, -tie(y1g, y1), 0.f, tie(y2, y2g)};
+  if constexpr (KIND == U2_BOXLOSS_GIOU) {
+    const float U = bw * bh + (x2g - x1g) * (y2g - y1g) - I;
+    const float C = cw * ch;
+    const float iou = I / (U + BOXLOSS_EPS), mis = (C - U) / (C + BOXLOSS_EPS);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float dU = dA[q] - dI[q], dC = dcw[q] * ch + cw * dch[q];
+      gb[q] = -(dI[q] - iou * dU) / (U + BOXLOSS_EPS) + ((dC - dU) - mis * dC) / (C + BOXLOSS_EPS);
+    }
+    return 1.f - iou + mis;
+  } else {
+    const float un = bw * bh + (x2g - x1g) * (y2g - y1g) - I + BOXLOSS_EPS;
+    const float iou = I / un;
+    const float diag = cw * cw + ch * ch + BOXLOSS_EPS;
+    const float ex = (x2 + x1) / 2.f - (x1g + x2g) / 2.f, ey = (y2 + y1) / 2.f - (y1g + y2g) / 2.f;
+    const float dist = ex * ex + ey * ey;
+    const float term = dist / diag;
+    const float ddist[4] = {ex, ey, ex, ey};
+    float av = 0.f, dvw = 0.f, dvh = 0.f;   // CIoU: alpha v and alpha dv/d(width, height) of the decoded box
+    if constexpr (KIND == U2_BOXLOSS_CIOU) {
+      const float k = 4.f / (3.14159265358979323846f * 3.14159265358979323846f);
+      const float ratio = bw / bh;
+      const float da = atanf((x2g - x1g) / (y2g - y1g)) - atanf(ratio);
+      const float v = k * da * da;
+      const float alpha = v / (1.f - iou + v + BOXLOSS_EPS);   // a constant of the gradient (no_grad in the reference)
+      const float dvdr = -2.f * k * da / (1.f + ratio * ratio);
+      av = alpha * v;
+      dvw = alpha * dvdr / bh;
+      dvh = -alpha * dvdr * ratio / bh;
+    }
+    const float dshape[4] = {-dvw, -dvh, dvw, dvh};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float dU = dA[q] - dI[q], ddiag = 2.f * (cw * dcw[q] + ch * dch[q]);
+      gb[q] = -(dI[q] - iou * dU) / un + (ddist[q] - term * ddiag) / diag + dshape[q];
+    }
+    return 1.f - iou + term + av;
+  }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void box_reg_loss_kernel(const bf16_t* __restrict__ pred, const float* __restrict__ prop,
+                                                           const float* __restrict__ gtb, const long long* __restrict__ labels,
+                                                           bf16_t* __restrict__ dpred, float* __restrict__ loss, int R, int LP,
+                                                           int bg_label, float wx, float wy, float ww, float wh, float beta,
+                                                           float scale_clamp, float gscale) {
+  __shared__ float red[4];
+  float l = 0.f;
+  for (int r = blockIdx.x * 256 + threadIdx.x; r < R; r += gridDim.x * 256) {
+    float gd[4] = {0.f, 0.f, 0.f, 0.f};
+    const long long lab = labels[r];
+    if (lab >= 0 && lab < bg_label) {
+      const float* p = prop + (size_t)r * 4;
+      const float* g = gtb + (size_t)r * 4;
+      float d[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) d[q] = bf2f(pred[(size_t)r * LP + q]);
+      if constexpr (KIND == U2_BOXLOSS_SMOOTH_L1) {
+        float tgt[4];
+        get_deltas(p, g, wx, wy, ww, wh, tgt);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float df = d[q] - tgt[q], n = fabsf(df);
+          l += n < beta ? 0.5f * n * n / beta : n - 0.5f * beta;
+          gd[q] = n < beta ? df / beta : (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f));
+        }
+      } else {
+        const float pw = p[2] - p[0], ph = p[3] - p[1];
+        const float cx = p[0] + 0.5f * pw, cy = p[1] + 0.5f * ph;
+        const float dx = d[0] / wx, dy = d[1] / wy;
+        float dw = d[2] / ww, dh = d[3] / wh;
+        const bool open_w = dw <= scale_clamp, open_h = dh <= scale_clamp;   // clamp(max =) passes the gradient up to equality
+        dw = fminf(dw, scale_clamp);
+        dh = fminf(dh, scale_clamp);
+        const float pcx = dx * pw + cx, pcy = dy * ph + cy;
+        const float bw = expf(dw) * pw, bh = expf(dh) * ph;
+        const float b[4] = {pcx - 0.5f * bw, pcy - 0.5f * bh, pcx + 0.5f * bw, pcy + 0.5f * bh};
+        float gb[4];
+        l += iou_family_loss<KIND>(b, g, gb);
+        gd[0] = (gb[0] + gb[2]) * pw / wx;
+        gd[1] = (gb[1] + gb[3]) * ph / wy;
+        gd[2] = open_w ? 0.5f * (gb[2] - gb[0]) * bw / ww : 0.f;
+        gd[3] = open_h ? 0.5f * (gb[3] - gb[1]) * bh / wh : 0.f;
+      }
+    }
+    bf16_t* gp = dpred + (size_t)r * LP;
+    const bf16_t head[8] = {f2bf(gd[0] * gscale), f2bf(gd[1] * gscale), f2bf(gd[2] * gscale), f2bf(gd[3] * gscale), 0, 0, 0, 0};
+    if ((LP & 7) == 0) {   // 16-byte stores: the four gradients and four zeros, then zeros
+      uint4* gv = reinterpret_cast<uint4*>(gp);
+      gv[0] = *reinterpret_cast<const uint4*>(head);
+      for (int c = 1; c < LP / 8; ++c) gv[c] = make_uint4(0, 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) gp[c] = head[c];
+      for (int c = 4; c < LP; ++c) gp[c] = 0;
+    }
+  }
+  const float s = block_sum_256(l, red);
+  if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss, s);
+}
+
 }  // namespace
 
 extern "C" int u2_semseg_upsample_ce(const void* logits, const void* target, float* grad_acc, float* loss_sum,
@@ -750,6 +976,44 @@ extern "C" int u2_box_reg_l1(const void* pred, const float* prop, const float* g
   if (g > 1024) g = 1024;
   hipLaunchKernelGGL(box_reg_l1_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, prop, gtb,
                      (const long long*)labels, (bf16_t*)dpred, loss, R, LP, bg_label, wx, wy, ww, wh, gscale);
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int u2_sigmoid_ce(const void* logits, const void* labels, const float* class_weight, void* dlogits,
+                             float* loss_sum, int R, int NC, int LP, float gscale, int* counters, int bg_label, void* stream) {
+  if (NC < 2 || LP < NC) return -1;
+  if (R <= 0) return 0;
+  int grid = (R + 3) / 4;
+  if (grid > 1024) grid = 1024;  // the waves loop over rows: at most 1024 loss atomics per launch
+  if (counters)
+    hipLaunchKernelGGL(sigmoid_ce_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits,
+                       (const long long*)labels, class_weight, (bf16_t*)dlogits, loss_sum, R, NC, LP, gscale, counters, bg_label);
+  else
+    hipLaunchKernelGGL(sigmoid_ce_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits,
+                       (const long long*)labels, class_weight, (bf16_t*)dlogits, loss_sum, R, NC, LP, gscale, (int*)nullptr, 0);
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int u2_box_reg_loss(int kind, const void* pred, const float* prop, const float* gtb, const void* labels, void* dpred,
+                               float* loss, int R, int LP, int bg_label, float wx, float wy, float ww, float wh, float beta,
+                               float scale_clamp, float gscale, void* stream) {
+  if (kind < U2_BOXLOSS_SMOOTH_L1 || kind > U2_BOXLOSS_CIOU || LP < 4) return -1;
+  if (kind == U2_BOXLOSS_SMOOTH_L1 && !(beta > 0.f)) return -1;  // beta == 0 is u2_box_reg_l1
+  if (R <= 0) return 0;
+  int g = (R + 255) / 256;
+  if (g > 1024) g = 1024;
+#define U2_BOXLOSS_LAUNCH(KIND)                                                                                              \
+  hipLaunchKernelGGL(box_reg_loss_kernel<KIND>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, prop, gtb, \
+                     (const long long*)labels, (bf16_t*)dpred, loss, R, LP, bg_label, wx, wy, ww, wh, beta, scale_clamp, gscale)
+  switch (kind) {
+    case U2_BOXLOSS_SMOOTH_L1: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_SMOOTH_L1); break;
+    case U2_BOXLOSS_GIOU: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_GIOU); break;
+    case U2_BOXLOSS_DIOU: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_DIOU); break;
+    default: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_CIOU); break;
+  }
+#undef U2_BOXLOSS_LAUNCH
   U2_CHECK_LAUNCH();
   return 0;
 }

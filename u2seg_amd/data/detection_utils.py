@@ -1,5 +1,5 @@
 """Image reading and annotation handling of the input pipeline (detectron2/data/detection_utils.py:60-211, 257-331,
-382-455, 486-520, 629-655; structures/boxes.py:15-131 for BoxMode)."""
+382-455, 486-520, 547-567, 629-655; structures/boxes.py:15-131 for BoxMode)."""
 import enum
 
 import numpy as np
@@ -9,6 +9,7 @@ from PIL import Image
 from ..structures import BitMasks, Boxes, Instances
 from . import polygon, rle
 from . import transforms as T
+from .catalog import DatasetCatalog, MetadataCatalog
 
 _EXIF_ORIENT = 274  # exif 'Orientation' tag
 
@@ -165,3 +166,37 @@ def build_augmentation(cfg, is_train):
     if is_train and inp.RANDOM_FLIP != "none":
         policy.append(T.RandomFlip(horizontal=inp.RANDOM_FLIP == "horizontal", vertical=inp.RANDOM_FLIP == "vertical"))
     return policy
+
+
+def class_image_count(dataset_dicts, num_classes):
+    """[{"id": i + 1, "image_count": n}] over the contiguous classes 0 .. num_classes - 1: n = the number of distinct images with
+    at least one non-crowd annotation of class i (the form of LVIS's metadata field of that name)."""
+    counts = [0] * num_classes
+    for record in dataset_dicts:
+        for c in {int(a["category_id"]) for a in record.get("annotations", []) if a.get("iscrowd", 0) == 0}:
+            counts[c] += 1
+    return [{"id": i + 1, "image_count": n} for i, n in enumerate(counts)]
+
+
+def get_fed_loss_cls_weights(dataset_names, freq_weight_power=1.0):
+    """image_count ** freq_weight_power per class, sorted by class id, from the metadata's `class_image_count`
+    (detection_utils.py:547-567).
+
+    Extension: the reference's COCO registration never sets that field, so there the federated loss cannot run on U2Seg's
+    datasets.  Here a missing field is computed once from the dataset dicts (class_image_count above) and stored in the
+    metadata."""
+    if isinstance(dataset_names, str):
+        dataset_names = [dataset_names]
+    assert len(dataset_names), "the federated loss needs DATASETS.TRAIN"
+    per_dataset = []
+    for name in dataset_names:
+        meta = MetadataCatalog.get(name)
+        if meta.get("class_image_count") is None:
+            dicts = DatasetCatalog.get(name)  # (also fills thing_classes where the loader sets it)
+            meta.class_image_count = class_image_count(dicts, len(meta.thing_classes))
+        per_dataset.append(meta.class_image_count)
+    for name, entry in zip(dataset_names[1:], per_dataset[1:]):  # check_metadata_consistency("class_image_count", ...)
+        if entry != per_dataset[0]:
+            raise ValueError("Datasets have different metadata 'class_image_count': '%s' and '%s'" % (dataset_names[0], name))
+    class_freq = torch.tensor([c["image_count"] for c in sorted(per_dataset[0], key=lambda x: x["id"])])
+    return class_freq.float() ** freq_weight_power

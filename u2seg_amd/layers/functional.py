@@ -1192,6 +1192,71 @@ def box_reg_l1_loss(pred, proposals, gt_boxes, labels, bg_label, weights, normal
     return _BoxRegL1Fn.apply(pred, proposals, gt_boxes, labels, bg_label, weights, float(normalizer))
 
 
+class _SigmoidCEFn(Function):
+    """FastRCNNOutputLayers.sigmoid_cross_entropy_loss (roi_heads/fast_rcnn.py:386-422): BCE-with-logits over the K foreground
+    columns, times the federated class mask where given, summed, / rows."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, num_classes, class_weight=None, counters=None):
+        r, lp = logits.shape
+        d = torch.empty_like(logits)
+        loss = zeros_f32((1,), logits.device)
+        if class_weight is not None:
+            assert class_weight.dtype == torch.float32 and class_weight.numel() >= num_classes - 1
+            class_weight = class_weight.contiguous()
+        if counters is not None:
+            _check_counters(counters, 5, logits.device)
+        _hip.call("u2_sigmoid_ce", logits.contiguous(), labels.contiguous(), class_weight, d, loss, r, num_classes, lp,
+                  1.0 / max(r, 1), counters, num_classes - 1)
+        ctx.save_for_backward(d)
+        return loss[0] / max(r, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        return d * g, None, None, None, None
+
+
+def sigmoid_cross_entropy(logits, labels, num_classes, class_weight=None, counters=None):
+    """num_classes counts the background (K + 1 valid columns, as softmax_cross_entropy takes it); class_weight fp32 [K] or None;
+    counters as softmax_cross_entropy's."""
+    return _SigmoidCEFn.apply(logits, labels, num_classes, class_weight, counters)
+
+
+BOX_REG_LOSS_KINDS = {"smooth_l1": _hip.K.BOXLOSS_SMOOTH_L1, "giou": _hip.K.BOXLOSS_GIOU, "diou": _hip.K.BOXLOSS_DIOU,
+                      "ciou": _hip.K.BOXLOSS_CIOU}
+
+
+class _BoxRegLossFn(Function):
+    """smooth-L1 with beta > 0 and the IoU-family losses on the decoded box (modeling/box_regression.py:310-369) over foreground
+    rows, summed, / normalizer."""
+
+    @staticmethod
+    def forward(ctx, kind, pred, proposals, gt_boxes, labels, bg_label, weights, normalizer, beta, scale_clamp):
+        r, lp = pred.shape
+        d = torch.empty_like(pred)
+        loss = zeros_f32((1,), pred.device)
+        _hip.call("u2_box_reg_loss", BOX_REG_LOSS_KINDS[kind], pred.contiguous(), proposals.contiguous(), gt_boxes.contiguous(),
+                  labels.contiguous(), d, loss, r, lp, bg_label, weights[0], weights[1], weights[2], weights[3], beta,
+                  scale_clamp, 1.0 / normalizer)
+        ctx.save_for_backward(d)
+        return loss[0] / normalizer
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        return (None, d * g) + (None,) * 8
+
+
+def box_reg_loss(kind, pred, proposals, gt_boxes, labels, bg_label, weights, normalizer, beta=0.0,
+                 scale_clamp=math.log(1000.0 / 16)):
+    """kind: smooth_l1 (beta > 0; beta == 0 is box_reg_l1_loss), giou, diou or ciou."""
+    if kind not in BOX_REG_LOSS_KINDS:
+        raise ValueError("Invalid box regression loss type '%s' (one of %s)" % (kind, ", ".join(BOX_REG_LOSS_KINDS)))
+    return _BoxRegLossFn.apply(kind, pred, proposals, gt_boxes, labels, bg_label, weights, float(normalizer), float(beta),
+                               float(scale_clamp))
+
+
 class _MaskPredictBCEFn(Function):
     """1x1 predictor restricted to the gt-class channel + BCE-with-logits(mean)
     (roi_heads/mask_head.py:258 + :33-112)."""

@@ -21,6 +21,7 @@ from ..utils.events import stage_counters as _stage_counters
 from ..utils.events import step_counters as _step_counters
 from ..utils.registry import Registry
 from .batched import BatchList, PaddedTargets, check_finite, device_constant, device_upload, image_index, proposals_from_list
+from .box_losses import BOX_REG_LOSS_TYPES, fed_loss_classes_mask
 from .sampling import subsample_labels
 
 ROI_HEADS_REGISTRY = Registry("ROI_HEADS")
@@ -121,7 +122,8 @@ class FastRCNNOutputLayers(nn.Module):
     @configurable
     def __init__(self, input_shape, *, box2box_weights, num_classes, test_score_thresh=0.0, test_nms_thresh=0.5,
                  test_topk_per_image=100, cls_agnostic_bbox_reg=False, smooth_l1_beta=0.0,
-                 box_reg_loss_type="smooth_l1", loss_weight=1.0):
+                 box_reg_loss_type="smooth_l1", loss_weight=1.0, use_fed_loss=False, use_sigmoid_ce=False,
+                 get_fed_loss_cls_weights=None, fed_loss_num_classes=50):
         super().__init__()
         if isinstance(input_shape, int):
             input_shape = ShapeSpec(channels=input_shape)
@@ -136,15 +138,29 @@ class FastRCNNOutputLayers(nn.Module):
         for layer in [self.cls_score, self.bbox_pred]:
             nn.init.constant_(layer.bias, 0)
         self.box2box_weights = tuple(box2box_weights)
-        assert box_reg_loss_type == "smooth_l1" and smooth_l1_beta == 0.0
+        if box_reg_loss_type not in BOX_REG_LOSS_TYPES:
+            raise ValueError("Invalid box regression loss type '%s' (MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE is one of %s)"
+                             % (box_reg_loss_type, ", ".join(BOX_REG_LOSS_TYPES)))
+        self.box_reg_loss_type, self.smooth_l1_beta = box_reg_loss_type, float(smooth_l1_beta)
         self.test_score_thresh, self.test_nms_thresh = test_score_thresh, test_nms_thresh
         self.test_topk_per_image = test_topk_per_image
         if isinstance(loss_weight, float):
             loss_weight = {"loss_cls": loss_weight, "loss_box_reg": loss_weight}
         self.loss_weight = loss_weight
+        self.use_fed_loss, self.use_sigmoid_ce = use_fed_loss, use_sigmoid_ce
+        self.fed_loss_num_classes = fed_loss_num_classes
+        if self.use_fed_loss:  # fast_rcnn.py:259-265 (the buffer exists only with the option: the default state dict keeps its keys)
+            assert self.use_sigmoid_ce, "Please use sigmoid cross entropy loss with federated loss"
+            fed_loss_cls_weights = get_fed_loss_cls_weights()
+            assert len(fed_loss_cls_weights) == self.num_classes, (
+                "Please check the provided fed_loss_cls_weights. Their size should match num_classes")
+            self.register_buffer("fed_loss_cls_weights", fed_loss_cls_weights.float())
 
     @classmethod
     def from_config(cls, cfg, input_shape):
+        from ..data.detection_utils import get_fed_loss_cls_weights
+
+        head = cfg.MODEL.ROI_BOX_HEAD
         return {
             "input_shape": input_shape,
             "box2box_weights": cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS,
@@ -156,6 +172,11 @@ class FastRCNNOutputLayers(nn.Module):
             "test_topk_per_image": cfg.TEST.DETECTIONS_PER_IMAGE,
             "box_reg_loss_type": cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE,
             "loss_weight": {"loss_box_reg": cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT},
+            "use_fed_loss": head.USE_FED_LOSS,
+            "use_sigmoid_ce": head.USE_SIGMOID_CE,
+            "get_fed_loss_cls_weights": lambda: get_fed_loss_cls_weights(
+                dataset_names=cfg.DATASETS.TRAIN, freq_weight_power=head.FED_LOSS_FREQ_WEIGHT_POWER),
+            "fed_loss_num_classes": head.FED_LOSS_NUM_CLASSES,
         }
 
     def forward(self, x):
@@ -175,9 +196,19 @@ class FastRCNNOutputLayers(nn.Module):
         if r == 0:
             z = scores.float().sum() * 0.0
             return {"loss_cls": z, "loss_box_reg": deltas.float().sum() * 0.0}
-        loss_cls = F.softmax_cross_entropy(scores, gt_classes, self.num_classes + 1, _stage_counters())
-        loss_box = F.box_reg_l1_loss(deltas, proposal_boxes, gt_boxes, gt_classes, self.num_classes,
-                                     self.box2box_weights, max(r, 1.0))
+        if self.use_sigmoid_ce:
+            fed = None
+            if self.use_fed_loss:
+                fed = fed_loss_classes_mask(gt_classes, self.fed_loss_num_classes, self.num_classes, self.fed_loss_cls_weights)
+            loss_cls = F.sigmoid_cross_entropy(scores, gt_classes, self.num_classes + 1, fed, _stage_counters())
+        else:
+            loss_cls = F.softmax_cross_entropy(scores, gt_classes, self.num_classes + 1, _stage_counters())
+        if self.box_reg_loss_type == "smooth_l1" and self.smooth_l1_beta == 0.0:
+            loss_box = F.box_reg_l1_loss(deltas, proposal_boxes, gt_boxes, gt_classes, self.num_classes,
+                                         self.box2box_weights, max(r, 1.0))
+        else:
+            loss_box = F.box_reg_loss(self.box_reg_loss_type, deltas, proposal_boxes, gt_boxes, gt_classes, self.num_classes,
+                                      self.box2box_weights, max(r, 1.0), self.smooth_l1_beta, _SCALE_CLAMP)
         losses = {"loss_cls": loss_cls, "loss_box_reg": loss_box}
         return {k: v * self.loss_weight.get(k, 1.0) for k, v in losses.items()}
 
@@ -201,7 +232,10 @@ class FastRCNNOutputLayers(nn.Module):
     def predict_probs(self, predictions, proposals, split=True):
         """split=False: the [sum R_i, K+1] probabilities of the whole batch in one tensor."""
         scores, _ = predictions
-        probs = torch.softmax(scores[:, : self.num_classes + 1].float(), dim=-1)
+        if self.use_sigmoid_ce:  # fast_rcnn.py:565-566
+            probs = scores[:, : self.num_classes + 1].float().sigmoid()
+        else:
+            probs = torch.softmax(scores[:, : self.num_classes + 1].float(), dim=-1)
         if not split:
             return probs
         return probs.split([len(p) for p in proposals], dim=0)
