@@ -17,7 +17,7 @@ def forced(conv=None, wgrad=None):
             else:
                 os.environ[k] = str(v)
         # the kernel tests see the library's own dispatch: the product path's rule of where the stream-K form may run
-        # (layers/functional.py:streamk_region - only the bottom-up backbone asks for it) is tested in test_streamk_region_rule
+        # (layers/streams.py:streamk_region - only the bottom-up backbone asks for it) is tested in test_streamk_region_rule
         from u2seg_amd.layers import functional as _fn
         with _fn.streamk_region():
             yield

@@ -645,7 +645,7 @@ def test_conv_accumulating_epilogue(F, shape):
 
 
 def test_streamk_region_rule(F):
-    """Where the product path lets a convolution take the stream-K form (layers/functional.py:streamk_region): inside the region
+    """Where the product path lets a convolution take the stream-K form (layers/streams.py:streamk_region): inside the region
     (the bottom-up backbone) the library's fill rule decides - fpn_output4's shape takes configuration 501, forward and data
     gradient -, outside it the call carries U2_CV_STREAMK_FORBID and runs whole tiles (K_TILE + 1) while the branch streams are on, and the
     rule is off when they are off (set_stream_overlap(False)) or U2_STREAMK_EVERYWHERE=1; results agree either way."""

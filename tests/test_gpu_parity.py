@@ -2002,7 +2002,7 @@ def test_sgd_trajectory_vs_reference(F, fixed_order_statistics, branch):
 
 def test_semantic_head_launched_in_pieces_equals_whole_launch(F, fixed_order_statistics, monkeypatch):
     """PanopticFPN.forward (training) hands the semantic head to the ROI heads in pieces that are launched - on the head's own
-    stream - from inside the samplers' torch.no_grad() regions (layers/functional.py:defer_pieces, meta_arch/panoptic_fpn.py:90-138
+    stream - from inside the samplers' torch.no_grad() regions (layers/streams.py:queue_branch_pieces, meta_arch/panoptic_fpn.py:90-138
     has one call): same weights, batch and sampling keys with U2_SEM_PIECES=1 / 0 give the same ten losses and the same
     gradients - in particular the head's and, through the FPN maps, the backbone's (a piece launched without a graph would
     leave them at zero / without the head's share)."""
@@ -2010,6 +2010,7 @@ def test_semantic_head_launched_in_pieces_equals_whole_launch(F, fixed_order_sta
     from tests.test_gpu_bookkeeping import KeyRecorder
     from u2seg_amd.config import get_cfg
     from u2seg_amd.data import make_synthetic_batch
+    from u2seg_amd.layers import streams
     from u2seg_amd.modeling import build_model, set_key_source
     from u2seg_amd.solver import build_optimizer
 
@@ -2033,7 +2034,7 @@ def test_semantic_head_launched_in_pieces_equals_whole_launch(F, fixed_order_sta
         try:
             opt.zero_grad()
             losses = model(batch)
-            assert not F._deferred_pieces
+            assert not streams._branch_pieces
             sum(losses.values()).backward()
         finally:
             set_key_source(None)
@@ -2204,6 +2205,7 @@ def test_multi_stream_step_equals_single_stream(F, monkeypatch):
     the FPN maps (bf16) must equal the single-stream run to 1e-2 / a few bf16 ulp, three times in a row."""
     from u2seg_amd.config import get_cfg
     from u2seg_amd.data import make_synthetic_batch
+    from u2seg_amd.layers import streams
     from u2seg_amd.modeling import build_model
     from u2seg_amd.solver import build_optimizer
 
@@ -2230,7 +2232,7 @@ def test_multi_stream_step_equals_single_stream(F, monkeypatch):
     monkeypatch.setattr(model, "_backbone_features", frozen)
 
     def run(multi):
-        monkeypatch.setattr(F, "_WGRAD_SIDE", multi)
+        monkeypatch.setattr(streams, "_WGRAD_SIDE", multi)
         monkeypatch.setenv("U2_AUX_STREAM", "1" if multi else "0")
         opt.zero_grad()
         torch.manual_seed(11)

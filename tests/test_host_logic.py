@@ -684,7 +684,7 @@ def test_fan_out_takes_a_deferred_roi_gather_on_cpu(monkeypatch):
 
 
 def test_topk_segment_chooser():
-    """layers/functional.py:_topk_segments - long rows are cut into equal segments only when they tile the row exactly, stay
+    """layers/select.py:_topk_segments - long rows are cut into equal segments only when they tile the row exactly, stay
     several times longer than k and do not exceed the chip's work-group slots."""
     from u2seg_amd.layers.functional import _topk_segments
 

@@ -35,7 +35,7 @@ orig = _hip.call
 
 def spy(name, *a):
     if name == "u2_weight_layout":
-        site = [f for f in traceback.extract_stack()[:-1] if "u2seg_amd" in f.filename and "functional.py" not in f.filename]
+        site = [f for f in traceback.extract_stack()[:-1] if "u2seg_amd" in f.filename and os.path.basename(f.filename) not in ("functional.py", "weights.py")]
         where = "%s:%d" % (os.path.relpath(site[-1].filename, ROOT), site[-1].lineno) if site else "?"
         calls[(tuple(a[2:]), where)] += 1
     return orig(name, *a)

@@ -758,7 +758,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv_tile_kernel(const Conv
 // in 4 of 23 runs (profiles/r06_hang_hunt.txt: the chip never finishes a step), in 0 of 24 with this form forbidden (U2_CV_STREAMK_FORBID), in 0
 // of 40 with those streams off, and still in 3 of 30 with the stream-K launches of different streams ordered behind each other by
 // events - one launch of this form beside kernels of another stream is enough.  What the argument above misses is not understood.
-// The product path (layers/functional.py:streamk_region) asks for this form only where no branch stream has work in flight and
+// The product path (layers/streams.py:streamk_region) asks for this form only where no branch stream has work in flight and
 // passes U2_CV_STREAMK_FORBID elsewhere; callers with several streams must do the same.
 constexpr int SK_MAX_GROUPS = 512;
 constexpr size_t SK_WS_LIMIT = (size_t)64 << 20;

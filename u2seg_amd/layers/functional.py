@@ -7,11 +7,14 @@ consumer is told the logical width).  Parameters stay fp32 in the reference layo
 layout (``[Cout][kh*kw][Cin]`` bf16) on the fly.
 
 Every function here launches HIP kernels; none has a CPU or ATen compute fallback.
+
+This module holds the differentiable layers whose backward passes talk to each other through layers/deferred.py (conv, stem,
+norms, pooling, resampling, fan-out, ROIAlign) and is the one name the rest of the package calls the layers by: the zero pool and
+the weight layouts (weights.py), the streams (streams.py), the head losses (losses.py) and the selection wrappers (select.py)
+are imported here by name.  Functions are re-exported, mutable state never: a switch lives in exactly one module.
 """
 import collections
 import ctypes
-import math
-
 import functools
 import os
 
@@ -20,318 +23,37 @@ import torch.distributed as dist
 from torch.autograd import Function
 
 from .. import _hip
-from . import deferred
-
-BF16 = torch.bfloat16
-
-
-def ceil32(n):
-    return (n + 31) // 32 * 32
-
-
-def _world():
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-
-
-class _ZeroPool:
-    """Small zero-initialised fp32 scratch tensors (statistics, split-K gradient accumulators) carved out of 16 MB
-    chunks: one fill kernel per chunk instead of one per tensor.  Slices are handed out once and never recycled."""
-
-    CHUNK = 1 << 22
-
-    def __init__(self):
-        self.chunks = {}  # (device, stream) -> [chunk, offset]: a chunk is filled on, and only handed out to, one stream
-
-    def take(self, shape, device):
-        numel = 1
-        for d in shape:
-            numel *= d
-        if numel * 2 > self.CHUNK or numel == 0:
-            return torch.zeros(shape, dtype=torch.float32, device=device)
-        n = (numel + 63) // 64 * 64
-        key = (device, torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0)
-        ent = self.chunks.get(key)
-        if ent is None or ent[1] + n > self.CHUNK:
-            ent = self.chunks[key] = [torch.zeros(self.CHUNK, dtype=torch.float32, device=device), 0]
-        v = ent[0][ent[1] : ent[1] + numel].view(shape)
-        ent[1] += n
-        return v
-
-
-_zero_pool = _ZeroPool()
-
-
-def zeros_f32(shape, device):
-    return _zero_pool.take(tuple(shape), torch.device(device))
-
-
-def release_library_scratch():
-    """Frees the device memory libu2seg_hip.so owns (stream-K hand-over slots, weight-gradient partial tiles: include/u2seg_hip.h
-    u2_release_scratch); it is allocated again by the next launch that needs it.  Call it next to torch.cuda.empty_cache()."""
-    return _hip.call_nostream("u2_release_scratch")
-
-
-def _check_act(x):
-    assert x.is_cuda and x.dtype == BF16 and x.is_contiguous() and x.dim() == 4 and x.shape[3] % 32 == 0, (
-        "expected contiguous NHWC bf16 activation with C %% 32 == 0, got %s %s" % (tuple(x.shape), x.dtype)
-    )
-
+from . import deferred, streams
+from .losses import (BOX_REG_LOSS_KINDS, box_reg_l1_loss, box_reg_loss, count_labels_i8, mask_predict_bce_loss,  # noqa: F401
+                     mask_predict_prob, rpn_losses, sem_seg_loss, sigmoid_cross_entropy, softmax_cross_entropy)
+from .select import (_TOPK_MAX_K, _topk_rows_sorted, _topk_segments, apply_deltas, assign_levels, batched_nms,  # noqa: F401
+                     iou_match, mask_crop, rpn_decode, sem_seg_upsample, topk_rows, topk_rows_multi)
+from .streams import (_NO_STREAMK, _conv_variant, _run_wgrad, _world, aux_stream, clear_branch_pieces,  # noqa: F401
+                      flush_branch_pieces, issue_branch_piece, join_all_streams, join_aux_stream, join_wgrad_stream,
+                      producer_streams, queue_branch_pieces, set_stream_overlap, streamk_region)
+from .weights import (BF16, _check_act, _conv_bias, _weight_layout, ceil32, grad_slot, release_library_scratch,  # noqa: F401
+                      weight_dgrad_layout, weight_fc_dgrad_layout, weight_fwd_layout, zeros_f32)
 
 # --------------------------------------------------------------------------------------------
-# weight layouts
+# switches (tests and A/B runs assign them on this module; they are read at call time)
 # --------------------------------------------------------------------------------------------
-def _weight_layout(w, cp, npad, mode, owner=None):
-    """bf16 kernel layout of an fp32 [N, Cin, KH, KW] weight.  `owner` is the nn.Parameter whose memory `w` is (w itself or a
-    reshaped view of it).  Parameters owned by solver.FlatSGD keep their layouts: the optimizer rewrites all of them in
-    one launch right after each step (u2_weight_layout_batched), so the training passes launch no layout kernels.  A cached
-    layout is trusted only while the parameter's autograd version and the optimizer's step stamp are unchanged."""
-    n, cin, kh, kw = w.shape
-    t = kh * kw
-    shape = (n, t, cp) if mode == 0 else ((cp, t, npad) if mode == 1 else (t * cp, 1, npad))
-    tcache = getattr(owner, "_u2_step_layouts", None) if owner is not None else None
-    if tcache is not None:
-        # a derived weight that lives for one pass (the RPN's concatenated predictor, used on five levels): layouts kept on the
-        # tensor itself; the caller never modifies it in place
-        key = (n, cin, t, cp, npad, mode)
-        out = tcache.get(key)
-        if out is None:
-            out = tcache[key] = torch.empty(shape, dtype=BF16, device=w.device)
-            _hip.call("u2_weight_layout", w.detach().float().contiguous(), out, n, cin, t, cp, npad, mode)
-        return out
-    stamp_ref = getattr(owner, "_u2_stamp", None) if owner is not None else None
-    if mode != 0 and cp != cin:
-        stamp_ref = None  # the batched transposer has no all-zero output rows; such layouts are built on the fly
-    ent = None
-    if stamp_ref is not None:
-        cache = owner.__dict__.setdefault("_u2_layouts", {})
-        key = (n, cin, t, cp, npad, mode)
-        ent = cache.get(key)
-        if ent is not None and ent[1] == owner._version and ent[2] == stamp_ref[0]:
-            return ent[0]
-    elif owner is not None and not torch.is_grad_enabled():
-        # inference without an optimizer: the weights only change through torch (load_state_dict, copy_), which bumps the
-        # version counter - one layout launch per weight for the whole evaluation instead of one per forward pass
-        ecache = owner.__dict__.setdefault("_u2_eval_layouts", {})
-        key = (n, cin, t, cp, npad, mode)
-        hit = ecache.get(key)
-        if hit is not None and hit[1] == owner._version and hit[2] == owner.data_ptr():
-            return hit[0]
-        out = torch.empty(shape, dtype=BF16, device=w.device)
-        _hip.call("u2_weight_layout", w.detach().float().contiguous(), out, n, cin, t, cp, npad, mode)
-        ecache[key] = (out, owner._version, owner.data_ptr())
-        return out
-    out = ent[0] if ent is not None else torch.empty(shape, dtype=BF16, device=w.device)
-    _hip.call("u2_weight_layout", w.detach().float().contiguous(), out, n, cin, t, cp, npad, mode)
-    if stamp_ref is not None:
-        if ent is None:
-            ent = cache[key] = [out, owner._version, stamp_ref[0]]
-            owner._u2_layout_register(owner, key, ent)
-        else:
-            ent[1], ent[2] = owner._version, stamp_ref[0]
-    return out
-
-
-def weight_fwd_layout(w, cp, owner=None):
-    """[N, Cin, KH, KW] fp32 -> [N, KH*KW, cp] bf16 (channels zero padded to cp)."""
-    return _weight_layout(w, cp, 0, 0, owner)
-
-
-def weight_dgrad_layout(w, cp, npad, owner=None):
-    """[N, Cin, KH, KW] fp32 -> [cp, KH*KW, npad] bf16 with the filter flipped in both spatial axes."""
-    return _weight_layout(w, cp, npad, 1, owner)
-
-
-def weight_fc_dgrad_layout(w, cp, npad, owner=None):
-    """[N, Cin, KH, KW] fp32 -> [KH*KW*cp, 1, npad] bf16: dx[(kh,kw,c)] = sum_n dz[n] W[n, c, kh, kw]."""
-    return _weight_layout(w, cp, npad, 2, owner)
-
-
-# --------------------------------------------------------------------------------------------
-# weight gradients on a second stream
-# --------------------------------------------------------------------------------------------
-# Nothing in the backward pass reads a weight gradient, so the wgrad kernels of all convolutions run on a side stream:
-# they overlap with the data-gradient convs and - more usefully, MFMA work beside HBM-bound work - with the norm /
-# ROI backward passes of the main stream, and one fills the other's partially occupied tail rounds.  The side stream
-# waits for the main stream at every launch (its operands are produced there); the main stream waits for the side stream
-# once, in a callback that autograd runs when the backward pass ends (so `.grad` is complete when backward() returns),
-# and wherever gradients are consumed earlier (solver.FlatSGD: the all-reduce of the arena's tail starts inside backward).
-_WGRAD_SIDE = os.environ.get("U2_WGRAD_SIDE_STREAM", "1") != "0"
-_AUX_ENABLED = True
-
-
-def set_stream_overlap(on):
-    """Switch the side stream (weight gradients) and the second compute stream (semantic head) on / off at run time; off =
-    every kernel of the step in one stream, one after the other (bench.py times its kernels that way)."""
-    global _WGRAD_SIDE, _AUX_ENABLED
-    _WGRAD_SIDE = bool(on) and os.environ.get("U2_WGRAD_SIDE_STREAM", "1") != "0"
-    _AUX_ENABLED = bool(on)
-_side_streams = {}
-_side_dirty = {}
-
-
-def _side_stream(device):
-    s = _side_streams.get(device)
-    if s is None:
-        s = _side_streams[device] = torch.cuda.Stream(device=device, priority=int(os.environ.get("U2_SIDE_PRIORITY", "0")))
-    return s
-
-
-_aux_streams = {}
-
-
-def _cuda_device(device):
-    device = torch.device(device)
-    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
-
-
-def aux_stream(device, index=0):
-    """A further compute stream for an independent branch of the model (None when switched off: U2_AUX_STREAM=0).
-    index 0: the semantic head; index 1: the mask head beside the box cascade."""
-    if not _AUX_ENABLED or os.environ.get("U2_AUX_STREAM", "1") == "0":
-        return None
-    key = (_cuda_device(device), index)
-    s = _aux_streams.get(key)
-    if s is None:
-        s = _aux_streams[key] = torch.cuda.Stream(device=key[0], priority=int(os.environ.get("U2_AUX_PRIORITY", "0")))
-    return s
-
-
-def join_aux_stream(device, index=0):
-    """The current stream waits for everything queued on that further compute stream."""
-    if not torch.cuda.is_available() or torch.device(device).type != "cuda":
-        return
-    s = _aux_streams.get((_cuda_device(device), index))
-    if s is not None:
-        torch.cuda.current_stream(s.device).wait_stream(s)
-
-
-# ---- where the stream-K form of the tile kernel may be used (round 6) ----
-# Recorded in profiles/r06_hang_hunt.txt: the driver's bench command hung in 4 of 23 runs (the chip never finished; the host sat in the
-# step's first synchronisation), in 0 of 24 with the stream-K form forbidden, in 0 of 40 with the branch streams (semantic head, mask
-# head) switched off, and still in 3 of 30 with the stream-K launches of different streams ordered behind each other by events.  So
-# ONE stream-K launch - whose owners spin for peers that the dispatcher has yet to place on a CU, conv_tile.hip - can stall for good
-# while kernels of a branch stream compete for the CUs; the mechanism is not understood (the weight-gradient side stream beside
-# stream-K launches: 0 of 20).  Until it is, the product path asks for the stream-K form only where no branch stream has work in
-# flight: inside the bottom-up backbone (forward: nothing else has been launched yet; backward: the heads' streams have been
-# joined by the FPN's gradient fan-in), and anywhere when the branch streams are off (set_stream_overlap(False)).  Elsewhere the
-# calls carry U2_CV_STREAMK_FORBID of the conv word (include/u2seg_hip.h: whole tiles).  U2_STREAMK_EVERYWHERE=1 restores the old
-# behaviour.
-_NO_STREAMK = _hip.K.CV_STREAMK_FORBID
-_SK_REGION = [0]
-
-
-class streamk_region:
-    """with streamk_region(): the convolutions created inside (and their backward passes) may take the stream-K form."""
-
-    def __enter__(self):
-        _SK_REGION[0] += 1
-
-    def __exit__(self, *exc):
-        _SK_REGION[0] -= 1
-        return False
-
-
-def _several_ranks():
-    import torch.distributed as dist
-
-    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-
-
-def _conv_variant():
-    if os.environ.get("U2_STREAMK_EVERYWHERE", "0") == "1" or "U2_CONV_VARIANT" in os.environ:
-        return 0   # (U2_CONV_VARIANT: tests and A/B runs steer the library's dispatch themselves; it only applies to variant 0)
-    if _several_ranks():
-        # the gradient exchange of the arena's tail (RCCL kernels on their own stream, solver/build.py:begin_all_reduce_tail) runs
-        # beside the backbone's backward pass: another stream competing for the CUs - never measured, so not risked
-        return _NO_STREAMK
-    if _SK_REGION[0] > 0 or not _AUX_ENABLED or os.environ.get("U2_AUX_STREAM", "1") == "0":
-        return 0
-    return _NO_STREAMK
-
-
-# ---- an independent branch issued in pieces where the main chain is host-bound (round 6) ----
-# The proposal bookkeeping of the ROI heads (match / relabel / sample between the cascade stages: ~40 tiny launches and one host
-# synchronisation each) leaves the chip idle for 0.6-1.3 ms at a time while the host catches up (tools/step_idle.py: 3.7 ms of a 58 ms
-# step).  A branch that only shares the FPN maps with it - the semantic head - is therefore not launched as a whole beside the RPN
-# but handed over as a list of pieces; the bookkeeping code calls issue_deferred_piece() right before it becomes host-bound, and the
-# piece's kernels (on the branch's own stream) run while the host synchronises and launches the small stuff.
-_deferred_pieces = []
-
-
-def defer_pieces(pieces):
-    """Queue closures (each launches one piece of an independent branch on that branch's stream)."""
-    _deferred_pieces.extend(pieces)
-
-
-def issue_deferred_piece(n=1):
-    """Launch the next n queued pieces (no-op when nothing is queued)."""
-    while n > 0 and _deferred_pieces:
-        _deferred_pieces.pop(0)()
-        n -= 1
-
-
-def flush_deferred():
-    """Launch whatever is still queued (the owner of the branch calls this before it joins the branch's stream)."""
-    issue_deferred_piece(len(_deferred_pieces))
-
-
-def clear_deferred():
-    """Drop queued pieces (a forward pass that raised midway must not leave its pieces to the next one)."""
-    del _deferred_pieces[:]
-
-
-def join_all_streams():
-    """The current stream waits for the side stream and every further compute stream: used where gradients are consumed
-    (optimizer step, gradient all-reduce - also the one of the arena's tail that starts inside the backward pass, when
-    the heads' parameter gradients may still be in flight on the streams their branches ran on)."""
-    join_wgrad_stream()
-    for (dev, _index), s in _aux_streams.items():
-        torch.cuda.current_stream(dev).wait_stream(s)
-
-
-def producer_streams(device):
-    """Every stream of this module that may hold gradient-producing work for `device` (weight-gradient side stream, the
-    further compute streams); the caller adds the stream it runs the step on."""
-    device = _cuda_device(device)
-    out = [s for dev, s in _side_streams.items() if _cuda_device(dev) == device]
-    out += [s for (dev, _index), s in _aux_streams.items() if dev == device]
-    return out
-
-
-def join_wgrad_stream(device=None):
-    """Make the current stream wait for every weight-gradient launch issued so far."""
-    for dev, s in _side_streams.items():
-        if device is None or dev == torch.device(device):
-            _side_dirty[dev] = False
-            torch.cuda.current_stream(dev).wait_stream(s)
-
-
-def _run_wgrad(device, operands, launch):
-    """launch() (kernel launches + torch ops) on the side stream; `operands` were produced on the current stream."""
-    if not _WGRAD_SIDE:
-        launch()
-        return
-    main = torch.cuda.current_stream(device)
-    side = _side_stream(device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        launch()
-    for t in operands:
-        t.record_stream(side)  # their memory may be released on the main stream while the side stream still reads it
-    _side_dirty[device] = True
-
-    def _join():  # runs when the backward pass has finished (queued once per launch: the first one to run does the work)
-        if _side_dirty.get(device):
-            _side_dirty[device] = False
-            torch.cuda.current_stream(device).wait_stream(side)  # the stream backward() was called on
-
-    torch.autograd.Variable._execution_engine.queue_callback(_join)
-
-
-# --------------------------------------------------------------------------------------------
-# convolution / linear
-# --------------------------------------------------------------------------------------------
-_DET_STATS = False
+_DET_STATS = False   # set_deterministic_stats()
+STEM_TAIL_FUSE = os.environ.get("U2_STEM_TAIL_FUSE", "1") != "0"   # the stem's norm -> ReLU -> max pool as one pass (stem_tail_ok)
+FUSED_BWD_MIN_PIXELS = int(os.environ.get("U2_FUSED_BWD_MIN_PIXELS", "200000"))
+# Three backward folds hand autograd a zero placeholder and leave the gradient to the node that receives it (layers/deferred.py):
+# - the batch-norm backward apply step of an expanding 1x1 layer evaluated inside that layer's fused backward launch (0: separate)
+LAZY_BN_APPLY = os.environ.get("U2_LAZY_BN_APPLY", "1") != "0"
+# - the ROIAlign gather of a tapped FPN map deferred to the map's _FanOutFn.backward (round 6); U2_ROI_SUM_FOLD=0: the tap gathers
+#   on the spot and u2_add_n sums afterwards
+ROI_SUM_FOLD = os.environ.get("U2_ROI_SUM_FOLD", "1") != "0"
+# - the backward reduce of a residual block's tail folded into the next block's conv1 data gradient (u2_conv_dgrad_tail;
+#   U2_TAIL_BWD_FUSE=0: two launches).  The placeholder runs in the other direction here: the conv hands autograd a placeholder for
+#   its input gradient, and the tail's backward, which receives it, finds (dz, sums) in its own state.
+TAIL_BWD_FUSE = os.environ.get("U2_TAIL_BWD_FUSE", "1") != "0"
+_TAIL_SHAPES = ((64, 256), (128, 512), (256, 1024))   # (conv1 output channels, block width) the kernel serves
+ROI_ORDER_MIN = int(os.environ.get("U2_ROI_ORDER_MIN", "1000000000"))   # ROI count from which the ROIAlign forward sorts its rows
+ROI_ALIGN_BWD_ATOMIC = False  # True selects the fp32-atomic scatter variant (kept for A/B tests)
+_UP2_BWD_LAST = None   # (key, dout, dx) of the semantic head's shared upsample gradient (_BilinearUp2Fn.backward)
 
 
 def set_deterministic_stats(on):
@@ -342,6 +64,15 @@ def set_deterministic_stats(on):
     _DET_STATS = bool(on)
 
 
+def set_tail_bwd_fuse(on):
+    """Run-time form of U2_TAIL_BWD_FUSE (tests, A/B runs); applies to graphs built afterwards."""
+    global TAIL_BWD_FUSE
+    TAIL_BWD_FUSE = bool(on)
+
+
+# --------------------------------------------------------------------------------------------
+# convolution / linear
+# --------------------------------------------------------------------------------------------
 def _fixed_order_stats(out, n):
     o = out[..., :n].float().reshape(-1, n)
     packed = torch.cat([o.sum(0), (o * o).sum(0), o.new_zeros(1)])
@@ -511,7 +242,7 @@ def _conv_bwd_weight(ctx, geom, x, weight, dz):
         def launch():
             _hip.call("u2_conv_wgrad_into", x, dz, dst, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride,
                       n, cin, cin, 1, 1, 0)
-    elif arena is not None and _WGRAD_SIDE:
+    elif arena is not None and streams._WGRAD_SIDE:
         # multi-tap filters: kernel-layout scratch, then accumulated into the arena slice by one transposing kernel (the strided
         # torch add took 70-170 us per 3x3 layer, 1.3 ms per step) - all of it on the side stream
         def launch():
@@ -557,41 +288,6 @@ def _tail_launch(ctx, geom, dz, x, weight):
     ph = deferred.post(deferred.TAIL, x.device, x.shape, tail)
     tail.result = (dzt, sums)
     return ph
-
-
-def _conv_bias(bias, round_bias):
-    """The fp32 bias vector the conv epilogue adds (rounded through bf16 as autocast rounds it).  For a parameter owned by
-    solver.FlatSGD the rounded copy is kept and rewritten by the optimizer's batched layout launch after every step (two small
-    cast launches per biased conv and pass otherwise: 64 per training step)."""
-    step_cache = getattr(bias, "_u2_step_bias", None)
-    if step_cache is not None and round_bias:
-        # a derived bias that lives for one pass (the RPN's concatenated predictor bias, used on five levels): rounded once
-        v = step_cache.get("v")
-        if v is None:
-            v = step_cache["v"] = bias.detach().bfloat16().float().contiguous()
-        return v
-    stamp = getattr(bias, "_u2_stamp", None)
-    if stamp is None or not round_bias:
-        return (bias.detach().bfloat16().float() if round_bias else bias.detach().float()).contiguous()
-    ent = bias.__dict__.get("_u2_bias_rounded")
-    if ent is None:
-        # registered with the optimizer's layout table (mode 3): rewritten with the weight layouts in the one launch after each
-        # step (it was two cast launches per biased conv and step: 40 small launches)
-        ent = [torch.empty(bias.shape, dtype=torch.float32, device=bias.device), -1, -1]
-        bias.__dict__["_u2_bias_rounded"] = ent
-        reg = getattr(bias, "_u2_layout_register", None)
-        if reg is not None and bias.dim() == 1:
-            reg(bias, (bias.numel(), 1, 1, 1, 0, 3), ent)
-    if ent[1] != bias._version or ent[2] != stamp[0]:
-        ent[0].copy_(bias.detach().bfloat16().float())
-        ent[1], ent[2] = bias._version, stamp[0]
-    return ent[0]
-
-
-def grad_slot(param):
-    """The optimizer's flat-arena gradient view of a parameter (solver/build.py:FlatSGD), or None.  Kernels that can
-    accumulate into it directly do so and report no gradient to autograd (no temporary, no AccumulateGrad add)."""
-    return getattr(param, "_u2_grad", None) if torch.is_grad_enabled() and param.requires_grad else None
 
 
 def conv2d(x, weight, bias=None, stride=1, pad=0, relu=False, want_stats=False, param=None, round_bias=True):
@@ -700,6 +396,44 @@ def stem_conv(weight, images, pixel_mean, pixel_std, hpad, wpad):
 # --------------------------------------------------------------------------------------------
 # normalisation
 # --------------------------------------------------------------------------------------------
+def _bn_exchange_stats(stats, m, c, sync):
+    """The statistics a (Sync)BatchNorm forward normalises with -> (stats, count, count_dev, world): this process' column sums
+    and element count m, or under SyncBN the sums over all ranks and their count on the device."""
+    world = _world() if sync else 1
+    count, count_dev = float(m), None
+    if world > 1:
+        # nn.SyncBatchNorm (layers/batch_norm.py:187) gathers (mean, invstd, count) of every rank: the ranks pad their
+        # batches to their own maximum image size, so the element counts differ.  One all-reduce of [sum | sumsq | count].
+        packed = getattr(stats, "_u2_packed", None)
+        if packed is None or packed.numel() != 2 * c + 1:  # statistics that did not come from a conv epilogue (tests)
+            packed = torch.cat([stats.reshape(-1).float(), stats.new_zeros(1, dtype=torch.float32)])
+        packed[2 * c :].fill_(float(m))  # an asynchronous fill: no synchronising constant upload per batch shape
+        dist.all_reduce(packed)
+        stats, count_dev = packed[: 2 * c].view(2, c), packed[2 * c :]
+    return stats, count, count_dev, world
+
+
+def _bn_exchange_sums(sums, world, grad_dst):
+    """The backward sums [sum dz | sum dz xhat] of a (Sync)BatchNorm, all-reduced in place under SyncBN
+    -> (this rank's own sums, coef [5, C] scratch, direct, dgamma, dbeta): the parameter gradients go straight into their arena
+    slices (direct) or into coef rows 0-1; rows 2-4 take the coefficients of dx."""
+    local = sums
+    if world > 1:
+        local = sums.clone()
+        dist.all_reduce(sums)
+    coef = torch.empty((5, sums.shape[1]), dtype=torch.float32, device=sums.device)
+    direct = grad_dst is not None
+    dgamma, dbeta = grad_dst if direct else (coef[0], coef[1])
+    return local, coef, direct, dgamma, dbeta
+
+
+def _norm_grad_dst(gamma, beta):
+    """The (dgamma, dbeta) arena slices a norm's backward kernels add into, or None: autograd then receives the two gradients."""
+    gd, bd = grad_slot(gamma), grad_slot(beta)
+    ok = gd is not None and bd is not None and gd.is_contiguous() and bd.is_contiguous() and gd.dtype == torch.float32
+    return (gd, bd) if ok else None
+
+
 class _BatchNormActFn(Function):
     """Training-mode (Sync)BatchNorm (+residual)(+ReLU) on a conv output whose column statistics were
     produced by the conv epilogue (reference: nn.SyncBatchNorm chosen at layers/batch_norm.py:187,
@@ -712,17 +446,7 @@ class _BatchNormActFn(Function):
         b, h, w, c = y.shape
         m = b * h * w
         ctx.lazy_ok = lazy_ok   # None, or the _LazyLink between this node's backward and the guard hook on y
-        world = _world() if sync else 1
-        count, count_dev = float(m), None
-        if world > 1:
-            # nn.SyncBatchNorm (layers/batch_norm.py:187) gathers (mean, invstd, count) of every rank: the ranks pad their
-            # batches to their own maximum image size, so the element counts differ.  One all-reduce of [sum | sumsq | count].
-            packed = getattr(stats, "_u2_packed", None)
-            if packed is None or packed.numel() != 2 * c + 1:  # statistics that did not come from a conv epilogue (tests)
-                packed = torch.cat([stats.reshape(-1).float(), stats.new_zeros(1, dtype=torch.float32)])
-            packed[2 * c :].fill_(float(m))  # an asynchronous fill: no synchronising constant upload per batch shape
-            dist.all_reduce(packed)
-            stats, count_dev = packed[: 2 * c].view(2, c), packed[2 * c :]
+        stats, count, count_dev, world = _bn_exchange_stats(stats, m, c, sync)
         mean = torch.empty(c, dtype=torch.float32, device=y.device)
         invstd, scale, shift = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
         out = torch.empty_like(y)
@@ -791,13 +515,7 @@ class _BatchNormActFn(Function):
                       int(bool(ctx.mask_bits and fuse)))
         if fuse and ctx.res_tail is not None and TAIL_BWD_FUSE:
             ctx.res_tail.g2 = dz   # for the conv1 that shares the previous block's output with this block's shortcut
-        local = sums
-        if world > 1:
-            local = sums.clone()
-            dist.all_reduce(sums)
-        coef = torch.empty((5, c), dtype=torch.float32, device=y.device)
-        direct = ctx.grad_dst is not None
-        dgamma, dbeta = ctx.grad_dst if direct else (coef[0], coef[1])
+        local, coef, direct, dgamma, dbeta = _bn_exchange_sums(sums, world, ctx.grad_dst)
         if ctx.lazy_ok is not None and LAZY_BN_APPLY and (fuse or (not relu and not has_res)):
             # the producing 1x1 conv evaluates the apply step dx = k1 dz + k2 y + k3 on its staged rows (u2_conv1x1_bwd_fused_bn,
             # round 5): only the coefficients (and dgamma / dbeta) are computed here, dx is never stored.  What autograd carries
@@ -833,8 +551,7 @@ def batch_norm_act(y, stats, gamma, beta, running_mean, running_var, residual=No
     pair such as the next residual block's conv1 and identity shortcut); the two gradients are summed inside the
     backward kernel instead of by autograd.  twin=3: a third handle in `._u2_third` as well.  sync=False: per-process statistics (NORM "BN"), no all-reduce.
     res_up=True: `residual` is the next coarser FPN level [B, H/2, W/2, C], nearest-upsampled inside the same pass."""
-    gd, bd = grad_slot(gamma), grad_slot(beta)
-    grad_dst = (gd, bd) if gd is not None and bd is not None else None
+    grad_dst = _norm_grad_dst(gamma, beta)
     twin = (3 if twin == 3 else int(bool(twin))) if torch.is_grad_enabled() else 0
     lazy_ok = None
     if getattr(y, "_u2_lazy_ok", False) and y.requires_grad and torch.is_grad_enabled():
@@ -921,22 +638,25 @@ class _GroupNormActFn(Function):
 
 
 def group_norm_act(y, gamma, beta, groups, relu=False, eps=1e-5):
-    gd, bd = grad_slot(gamma), grad_slot(beta)
-    ok = gd is not None and bd is not None and gd.is_contiguous() and bd.is_contiguous() and gd.dtype == torch.float32
     # without a graph (inference) the statistics are summed in a fixed order, so that a model in eval mode repeats its bits: test-time
     # augmentation compares and averages passes over the same views (modeling/test_time_augmentation.py)
-    return _GroupNormActFn.apply(y, gamma, beta, groups, relu, eps, (gd, bd) if ok else None, not torch.is_grad_enabled())
+    return _GroupNormActFn.apply(y, gamma, beta, groups, relu, eps, _norm_grad_dst(gamma, beta), not torch.is_grad_enabled())
 
 
 # --------------------------------------------------------------------------------------------
 # pooling / resampling
 # --------------------------------------------------------------------------------------------
+def _pooled_shape(h, w):
+    """Output height and width of the 3x3 / stride-2 / pad-1 max pool."""
+    return (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+
+
 class _MaxPoolFn(Function):
     @staticmethod
     def forward(ctx, x):
         _check_act(x)
         b, h, w, c = x.shape
-        ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+        ho, wo = _pooled_shape(h, w)
         y = torch.empty((b, ho, wo, c), dtype=BF16, device=x.device)
         idx = torch.empty((b, ho, wo, c), dtype=torch.uint8, device=x.device)
         _hip.call("u2_maxpool3x3s2_fwd", x, y, idx, b, h, w, c)
@@ -957,9 +677,6 @@ def max_pool_3x3_s2(x):
     return _MaxPoolFn.apply(x)
 
 
-STEM_TAIL_FUSE = os.environ.get("U2_STEM_TAIL_FUSE", "1") != "0"
-
-
 class _BatchNormReluMaxPoolFn(Function):
     """The stem's tail, norm -> relu_ -> max_pool2d(3, 2, 1) (backbone/resnet.py:355-359), without the activation between the
     normalisation and the pool (round 6): the pool normalises its nine taps itself, and the normalisation's backward passes
@@ -971,21 +688,12 @@ class _BatchNormReluMaxPoolFn(Function):
     def forward(ctx, y, stats, gamma, beta, running_mean, running_var, momentum, eps, grad_dst, sync):
         _check_act(y)
         b, h, w, c = y.shape
-        m = b * h * w
-        world = _world() if sync else 1
-        count, count_dev = float(m), None
-        if world > 1:
-            packed = getattr(stats, "_u2_packed", None)
-            if packed is None or packed.numel() != 2 * c + 1:
-                packed = torch.cat([stats.reshape(-1).float(), stats.new_zeros(1, dtype=torch.float32)])
-            packed[2 * c :].fill_(float(m))
-            dist.all_reduce(packed)
-            stats, count_dev = packed[: 2 * c].view(2, c), packed[2 * c :]
+        stats, count, count_dev, world = _bn_exchange_stats(stats, b * h * w, c, sync)
         coef = torch.empty((4, c), dtype=torch.float32, device=y.device)
         mean, invstd, scale, shift = coef[0], coef[1], coef[2], coef[3]
         _hip.call("u2_bn_finalize_fwd", stats, count, count_dev, gamma, beta, running_mean, running_var, momentum, eps, mean,
                   invstd, scale, shift, c)
-        ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+        ho, wo = _pooled_shape(h, w)
         out = torch.empty((b, ho, wo, c), dtype=BF16, device=y.device)
         idx = torch.empty((b, ho, wo, c), dtype=torch.uint8, device=y.device)
         _hip.call("u2_affine_relu_maxpool_fwd", y, scale, shift, out, idx, b, h, w, c)
@@ -1003,13 +711,7 @@ class _BatchNormReluMaxPoolFn(Function):
         dy = dy.contiguous()
         sums = zeros_f32((2, c), y.device)
         _hip.call("u2_affine_relu_maxpool_bwd_reduce", dy, idx, y, mean, invstd, msc, msh, sums, b, h, w, c)
-        local = sums
-        if world > 1:
-            local = sums.clone()
-            dist.all_reduce(sums)
-        coef = torch.empty((5, c), dtype=torch.float32, device=y.device)
-        direct = ctx.grad_dst is not None
-        dgamma, dbeta = ctx.grad_dst if direct else (coef[0], coef[1])
+        local, coef, direct, dgamma, dbeta = _bn_exchange_sums(sums, world, ctx.grad_dst)
         _hip.call("u2_bn_finalize_bwd", sums, count, ctx.count_dev, gamma, mean, invstd, local, dgamma, dbeta, coef[2], coef[3],
                   coef[4], c, int(direct))
         dx = torch.empty_like(y)
@@ -1023,15 +725,14 @@ def stem_tail_ok(c):
 
 
 def batch_norm_relu_max_pool(y, stats, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5, sync=True):
-    gd, bd = grad_slot(gamma), grad_slot(beta)
-    grad_dst = (gd, bd) if gd is not None and bd is not None else None
-    return _BatchNormReluMaxPoolFn.apply(y, stats, gamma, beta, running_mean, running_var, momentum, eps, grad_dst, sync)
+    return _BatchNormReluMaxPoolFn.apply(y, stats, gamma, beta, running_mean, running_var, momentum, eps,
+                                         _norm_grad_dst(gamma, beta), sync)
 
 
 def affine_relu_max_pool(y, scale, shift):
     """Inference: max_pool_3x3_s2(affine_act(y, scale, shift, relu=True)) in one pass; no autograd."""
     b, h, w, c = y.shape
-    ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+    ho, wo = _pooled_shape(h, w)
     out = torch.empty((b, ho, wo, c), dtype=BF16, device=y.device)
     idx = torch.empty((b, ho, wo, c), dtype=torch.uint8, device=y.device)
     _hip.call("u2_affine_relu_maxpool_fwd", y, scale.contiguous(), shift.contiguous(), out, idx, b, h, w, c)
@@ -1093,291 +794,8 @@ class _BilinearUp2Fn(Function):
         return dx, (dout if ctx.has_add else None)
 
 
-_UP2_BWD_LAST = None
-
-
 def bilinear_up2(x, addend=None):
     return _BilinearUp2Fn.apply(x, addend)
-
-
-# --------------------------------------------------------------------------------------------
-# losses
-# --------------------------------------------------------------------------------------------
-class _SemSegLossFn(Function):
-    """bilinear x4 + cross_entropy(mean, ignore) fused (meta_arch/semantic_seg.py:255-267)."""
-
-    @staticmethod
-    def forward(ctx, logits, target_u8, num_classes, ignore):
-        _check_act(logits)
-        b, h, w, lp = logits.shape
-        assert target_u8.dtype == torch.uint8 and target_u8.shape == (b, 4 * h, 4 * w)
-        acc = torch.empty((b, h, w, lp), dtype=torch.float32, device=logits.device)  # every element is written
-        sc = zeros_f32((2,), logits.device)
-        _hip.call("u2_semseg_upsample_ce", logits, target_u8.contiguous(), acc, sc[0:1], sc[1:2], b, h, w, lp,
-                  num_classes, ignore)
-        ctx.save_for_backward(acc, sc)
-        return sc[0] / sc[1]
-
-    @staticmethod
-    def backward(ctx, g):
-        acc, sc = ctx.saved_tensors
-        d = torch.empty(acc.shape, dtype=BF16, device=acc.device)
-        gg = g.detach().float().reshape(1).contiguous()
-        _hip.call("u2_scale_to_bf16", acc, gg, sc[1:2], 1.0, d, acc.numel())
-        return d, None, None, None
-
-
-def sem_seg_loss(logits, target_u8, num_classes, ignore=255):
-    return _SemSegLossFn.apply(logits, target_u8, num_classes, ignore)
-
-
-class _SoftmaxCEFn(Function):
-    """cross_entropy(scores, labels, reduction='mean') (roi_heads/fast_rcnn.py:344)."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, num_classes, counters=None):
-        r, lp = logits.shape
-        d = torch.empty_like(logits)
-        loss = zeros_f32((1,), logits.device)
-        if counters is None:
-            _hip.call("u2_softmax_ce", logits.contiguous(), labels.contiguous(), d, loss, r, num_classes, lp,
-                      1.0 / max(r, 1))
-        else:  # the same kernel body, which also counts fast_rcnn.py:88-115 into counters[0..4] (background = the last class)
-            _check_counters(counters, 5, logits.device)
-            _hip.call("u2_softmax_ce_stats", logits.contiguous(), labels.contiguous(), d, loss, r, num_classes, lp,
-                      1.0 / max(r, 1), counters, num_classes - 1)
-        ctx.save_for_backward(d)
-        return loss[0] / max(r, 1)
-
-    @staticmethod
-    def backward(ctx, g):
-        (d,) = ctx.saved_tensors
-        return d * g, None, None, None   # g: 0-dim fp32, the product keeps d's dtype (one launch)
-
-
-def _check_counters(counters, n, device):
-    assert counters.dtype == torch.int32 and counters.is_contiguous() and counters.numel() >= n and counters.device == device, (
-        "expected >= %d contiguous int32 counters on %s" % (n, device))
-
-
-def softmax_cross_entropy(logits, labels, num_classes, counters=None):
-    """counters (int32 [>= 5], optional): rows, pred == gt, fg, fg and pred == gt, fg and pred == background are ADDED to it
-    (u2_softmax_ce_stats); the loss and its gradient do not depend on it."""
-    if counters is None:
-        return _SoftmaxCEFn.apply(logits, labels, num_classes)
-    return _SoftmaxCEFn.apply(logits, labels, num_classes, counters)
-
-
-class _BoxRegL1Fn(Function):
-    """smooth_l1(beta=0) = L1 over foreground rows, summed, / normalizer (roi_heads/fast_rcnn.py:424-463)."""
-
-    @staticmethod
-    def forward(ctx, pred, proposals, gt_boxes, labels, bg_label, weights, normalizer):
-        r, lp = pred.shape
-        d = torch.empty_like(pred)
-        loss = zeros_f32((1,), pred.device)
-        _hip.call("u2_box_reg_l1", pred.contiguous(), proposals.contiguous(), gt_boxes.contiguous(),
-                  labels.contiguous(), d, loss, r, lp, bg_label, weights[0], weights[1], weights[2], weights[3],
-                  1.0 / normalizer)
-        ctx.save_for_backward(d)
-        return loss[0] / normalizer
-
-    @staticmethod
-    def backward(ctx, g):
-        (d,) = ctx.saved_tensors
-        return d * g, None, None, None, None, None, None
-
-
-def box_reg_l1_loss(pred, proposals, gt_boxes, labels, bg_label, weights, normalizer):
-    return _BoxRegL1Fn.apply(pred, proposals, gt_boxes, labels, bg_label, weights, float(normalizer))
-
-
-class _SigmoidCEFn(Function):
-    """FastRCNNOutputLayers.sigmoid_cross_entropy_loss (roi_heads/fast_rcnn.py:386-422): BCE-with-logits over the K foreground
-    columns, times the federated class mask where given, summed, / rows."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, num_classes, class_weight=None, counters=None):
-        r, lp = logits.shape
-        d = torch.empty_like(logits)
-        loss = zeros_f32((1,), logits.device)
-        if class_weight is not None:
-            assert class_weight.dtype == torch.float32 and class_weight.numel() >= num_classes - 1
-            class_weight = class_weight.contiguous()
-        if counters is not None:
-            _check_counters(counters, 5, logits.device)
-        _hip.call("u2_sigmoid_ce", logits.contiguous(), labels.contiguous(), class_weight, d, loss, r, num_classes, lp,
-                  1.0 / max(r, 1), counters, num_classes - 1)
-        ctx.save_for_backward(d)
-        return loss[0] / max(r, 1)
-
-    @staticmethod
-    def backward(ctx, g):
-        (d,) = ctx.saved_tensors
-        return d * g, None, None, None, None
-
-
-def sigmoid_cross_entropy(logits, labels, num_classes, class_weight=None, counters=None):
-    """num_classes counts the background (K + 1 valid columns, as softmax_cross_entropy takes it); class_weight fp32 [K] or None;
-    counters as softmax_cross_entropy's."""
-    return _SigmoidCEFn.apply(logits, labels, num_classes, class_weight, counters)
-
-
-BOX_REG_LOSS_KINDS = {"smooth_l1": _hip.K.BOXLOSS_SMOOTH_L1, "giou": _hip.K.BOXLOSS_GIOU, "diou": _hip.K.BOXLOSS_DIOU,
-                      "ciou": _hip.K.BOXLOSS_CIOU}
-
-
-class _BoxRegLossFn(Function):
-    """smooth-L1 with beta > 0 and the IoU-family losses on the decoded box (modeling/box_regression.py:310-369) over foreground
-    rows, summed, / normalizer."""
-
-    @staticmethod
-    def forward(ctx, kind, pred, proposals, gt_boxes, labels, bg_label, weights, normalizer, beta, scale_clamp):
-        r, lp = pred.shape
-        d = torch.empty_like(pred)
-        loss = zeros_f32((1,), pred.device)
-        _hip.call("u2_box_reg_loss", BOX_REG_LOSS_KINDS[kind], pred.contiguous(), proposals.contiguous(), gt_boxes.contiguous(),
-                  labels.contiguous(), d, loss, r, lp, bg_label, weights[0], weights[1], weights[2], weights[3], beta,
-                  scale_clamp, 1.0 / normalizer)
-        ctx.save_for_backward(d)
-        return loss[0] / normalizer
-
-    @staticmethod
-    def backward(ctx, g):
-        (d,) = ctx.saved_tensors
-        return (None, d * g) + (None,) * 8
-
-
-def box_reg_loss(kind, pred, proposals, gt_boxes, labels, bg_label, weights, normalizer, beta=0.0,
-                 scale_clamp=math.log(1000.0 / 16)):
-    """kind: smooth_l1 (beta > 0; beta == 0 is box_reg_l1_loss), giou, diou or ciou."""
-    if kind not in BOX_REG_LOSS_KINDS:
-        raise ValueError("Invalid box regression loss type '%s' (one of %s)" % (kind, ", ".join(BOX_REG_LOSS_KINDS)))
-    return _BoxRegLossFn.apply(kind, pred, proposals, gt_boxes, labels, bg_label, weights, float(normalizer), float(beta),
-                               float(scale_clamp))
-
-
-class _MaskPredictBCEFn(Function):
-    """1x1 predictor restricted to the gt-class channel + BCE-with-logits(mean)
-    (roi_heads/mask_head.py:258 + :33-112)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, classes, target_u8, phased=False, counters=None):
-        n, ph, pw, c = x.shape
-        if phased:  # x = the deconvolution's unshuffled phases [n, P, P, 4 C]: the kernel reads (and writes dx) in place
-            ph, pw, c = 2 * ph, 2 * pw, c // 4
-        p = ph * pw
-        k = weight.shape[0]
-        w2 = weight.detach().reshape(k, c).float().contiguous()
-        b2 = bias.detach().float().contiguous()
-        x, classes, target_u8 = x.contiguous(), classes.contiguous(), target_u8.contiguous()
-        loss = zeros_f32((1,), x.device)
-        denom = float(max(n * p, 1))
-        # the loss alone here; the gradients come from a second launch in backward, scaled by the loss's upstream gradient inside
-        # the kernel (forming dx here and multiplying it by that scalar in backward was a 0.2 ms pass over dx per step)
-        if counters is None:
-            _hip.call("u2_mask_predict_bce", x, w2, b2, classes, target_u8, None, None, None, loss, None, n, p, c, 1.0 / denom,
-                      ph if phased else 0, None)
-        else:  # the same loss, and mask_head.py:90-102's counts into counters[0..3]
-            _check_counters(counters, 4, x.device)
-            _hip.call("u2_mask_predict_bce_stats", x, w2, b2, classes, target_u8, loss, counters, n, p, c, ph if phased else 0)
-        ctx.save_for_backward(x, w2, b2, classes, target_u8)
-        ctx.cfg = (n, p, c, k, denom, ph if phased else 0, weight.shape)
-        return loss[0] / denom
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w2, b2, classes, target_u8 = ctx.saved_tensors
-        n, p, c, k, denom, phased_side, wshape = ctx.cfg
-        dx = torch.empty_like(x)
-        dw, db = zeros_f32((k, c), x.device), zeros_f32((k,), x.device)
-        _hip.call("u2_mask_predict_bce", x, w2, b2, classes, target_u8, dx, dw, db, None, None, n, p, c, 1.0 / denom, phased_side,
-                  g.detach().float().reshape(1).contiguous())
-        return dx, dw.view(wshape), db, None, None, None, None
-
-
-def mask_predict_bce_loss(x, weight, bias, classes, target_u8, phased=False, counters=None):
-    """counters (int32 [>= 4], optional): false positives, false negatives, positives and positions are ADDED to it
-    (u2_mask_predict_bce_stats)."""
-    if counters is None:
-        return _MaskPredictBCEFn.apply(x, weight, bias, classes, target_u8, phased)
-    return _MaskPredictBCEFn.apply(x, weight, bias, classes, target_u8, phased, counters)
-
-
-def count_labels_i8(labels, counters):
-    """counters[0] += #(labels == 1), counters[1] += #(labels == 0) over an int8 tensor (the RPN's subsampled anchor labels)."""
-    assert labels.dtype == torch.int8 and labels.is_contiguous()
-    _check_counters(counters, 2, labels.device)
-    _hip.call("u2_count_labels_i8", labels, labels.numel(), counters)
-
-
-def mask_predict_prob(x, weight, bias, classes, phased=False):
-    """mask_rcnn_inference (roi_heads/mask_head.py:115-158) with the 1x1 predictor folded in: fp32 [n, 1, 2P, 2P] probabilities of
-    each detection's predicted class.  x: [n, 2P, 2P, 256] trunk output, or with `phased` the deconvolution's unshuffled GEMM
-    output [n, P, P, 4 * 256] (ConvTranspose2d(..., shuffle=False)).  No autograd."""
-    _check_act(x)
-    n = x.shape[0]
-    side = x.shape[1] * 2 if phased else x.shape[1]
-    c = x.shape[3] // 4 if phased else x.shape[3]
-    out = torch.empty((n, 1, side, side), dtype=torch.float32, device=x.device)
-    if n:
-        _hip.call("u2_mask_predict_prob", x.contiguous(), weight.detach().reshape(weight.shape[0], -1).contiguous(),
-                  bias.detach().contiguous(), classes.to(torch.int64).contiguous(), out, n, side, c, int(phased))
-    return out
-
-
-class _RPNLossFn(Function):
-    """RPN objectness BCE(sum) + localisation L1(sum) over all levels, both / normalizer
-    (proposal_generator/rpn.py:366-429).  `fused`: each level is ONE map holding objectness (columns 0-2) and deltas (3-14)."""
-
-    @staticmethod
-    def forward(ctx, labels, match, gt_boxes, anchors_per_level, num_anchors, normalizer, fused, *obj_and_deltas):
-        nl = len(anchors_per_level)
-        objs, dlts = obj_and_deltas[:nl], obj_and_deltas[nl:]
-        b, atot = labels.shape
-        g = gt_boxes.shape[1]
-        loss = zeros_f32((2,), labels.device)
-        grads = []
-        off = 0
-        for lvl in range(nl):
-            o = objs[lvl]
-            hw = o.shape[1] * o.shape[2]
-            if fused:
-                go, d, gd = torch.empty_like(o), None, None
-            else:
-                d = dlts[lvl]
-                go, gd = torch.empty_like(o), torch.empty_like(d)
-            _hip.call("u2_rpn_loss_level", o, d, labels, match, gt_boxes, anchors_per_level[lvl], go, gd, loss, b, hw,
-                      num_anchors, o.shape[3], d.shape[3] if d is not None else 0, atot, off, g, 1.0 / normalizer)
-            grads.append((go, gd))
-            off += hw * num_anchors
-        assert off == atot
-        ctx.grads = grads
-        ctx.fused = fused
-        ctx.num_anchors = num_anchors
-        return loss[0] / normalizer, loss[1] / normalizer
-
-    @staticmethod
-    def backward(ctx, g_cls, g_loc):
-        if ctx.fused:
-            a = ctx.num_anchors
-            go0 = ctx.grads[0][0]
-            scale = torch.zeros(go0.shape[-1], dtype=torch.float32, device=go0.device)
-            scale[:a] = g_cls
-            scale[a : 5 * a] = g_loc
-            scale = scale.to(go0.dtype)
-            return (None, None, None, None, None, None, None, *[go * scale for go, _ in ctx.grads])
-        gos = [go * g_cls for go, _ in ctx.grads]   # 0-dim fp32 factors: the products keep the maps' dtype
-        gds = [gd * g_loc for _, gd in ctx.grads]
-        return (None, None, None, None, None, None, None, *gos, *gds)
-
-
-def rpn_losses(labels, match, gt_boxes, anchors_per_level, num_anchors, normalizer, objs, deltas):
-    """objs / deltas: per level [B, H, W, LP] maps - or, when the head ran both predictors as one conv (the maps carry
-    `_u2_rpn_fused`), the fused maps in `objs` (deltas are then views of them and are not used)."""
-    if all(getattr(o, "_u2_rpn_fused", False) for o in objs):
-        return _RPNLossFn.apply(labels, match, gt_boxes, anchors_per_level, num_anchors, float(normalizer), True, *objs)
-    return _RPNLossFn.apply(labels, match, gt_boxes, anchors_per_level, num_anchors, float(normalizer), False, *objs, *deltas)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1552,26 +970,72 @@ def roi_grad_tap(feats):
     return list(outs)
 
 
-FUSED_BWD_MIN_PIXELS = int(os.environ.get("U2_FUSED_BWD_MIN_PIXELS", "200000"))
-# Three backward folds hand autograd a zero placeholder and leave the gradient to the node that receives it (layers/deferred.py):
-# - the batch-norm backward apply step of an expanding 1x1 layer evaluated inside that layer's fused backward launch (0: separate)
-LAZY_BN_APPLY = os.environ.get("U2_LAZY_BN_APPLY", "1") != "0"
-# - the ROIAlign gather of a tapped FPN map deferred to the map's _FanOutFn.backward (round 6); U2_ROI_SUM_FOLD=0: the tap gathers
-#   on the spot and u2_add_n sums afterwards
-ROI_SUM_FOLD = os.environ.get("U2_ROI_SUM_FOLD", "1") != "0"
-# - the backward reduce of a residual block's tail folded into the next block's conv1 data gradient (u2_conv_dgrad_tail;
-#   U2_TAIL_BWD_FUSE=0: two launches).  The placeholder runs in the other direction here: the conv hands autograd a placeholder for
-#   its input gradient, and the tail's backward, which receives it, finds (dz, sums) in its own state.
-TAIL_BWD_FUSE = os.environ.get("U2_TAIL_BWD_FUSE", "1") != "0"
-_TAIL_SHAPES = ((64, 256), (128, 512), (256, 1024))   # (conv1 output channels, block width) the kernel serves
+def _roi_process_order(rois, levels, nimg, nlevels):
+    """Processing order of the ROIAlign forward: sorted by (level, image, top row of the box at its level / 8)."""
+    key = (levels.long() * nimg + rois[:, 0].long()) * 4096 + (rois[:, 2] * (0.25 / 8)).long().clamp_(0, 4095)
+    return torch.argsort(key).to(torch.int32)
 
 
-def set_tail_bwd_fuse(on):
-    """Run-time form of U2_TAIL_BWD_FUSE (tests, A/B runs); applies to graphs built afterwards."""
-    global TAIL_BWD_FUSE
-    TAIL_BWD_FUSE = bool(on)
+class _ROIAlignFn(Function):
+    """Multi-level ROIAlign(aligned=True, sampling_ratio=0) (modeling/poolers.py:206-263)."""
+
+    @staticmethod
+    def forward(ctx, rois, levels, out_size, scales, grad_scale, tap, *feats):
+        nl = len(feats)
+        for f in feats:
+            _check_act(f)
+        c = feats[0].shape[3]
+        r = rois.shape[0]
+        ptrs = (ctypes.c_void_p * nl)(*[f.data_ptr() for f in feats])
+        hs, ws, sc = _level_arrays([f.shape for f in feats], scales)
+        out = torch.empty((r, out_size, out_size, c), dtype=BF16, device=rois.device)
+        order = _roi_process_order(rois, levels, feats[0].shape[0], nl) if r >= ROI_ORDER_MIN else None
+        _hip.call("u2_roi_align_fwd", ptrs, hs, ws, sc, nl, rois.contiguous(), levels.contiguous(), order, out, r, c, out_size,
+                  out_size)
+        ctx.save_for_backward(rois, levels)
+        ctx.cfg = (out_size, scales, grad_scale, [tuple(f.shape) for f in feats])
+        ctx.tap = tap
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        rois, levels = ctx.saved_tensors
+        out_size, scales, grad_scale, shapes = ctx.cfg
+        nl = len(shapes)
+        b = shapes[0][0]
+        r, c = rois.shape[0], shapes[0][3]
+        none = (None,) * 6
+        if ROI_ALIGN_BWD_ATOMIC:
+            hs, ws, sc = _level_arrays(shapes, scales)
+            gbuf = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in shapes]
+            ptrs = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbuf])
+            _hip.call("u2_roi_align_bwd", ptrs, hs, ws, sc, nl, rois.contiguous(), levels.contiguous(), dout.contiguous(),
+                      r, c, out_size, out_size, float(grad_scale))
+            return (*none, *[g.to(BF16) for g in gbuf])
+        order, seg = _roi_group(rois, levels, b, nl)
+        entry = _RoiSet(rois, order, seg, dout, out_size, grad_scale)
+        tap = ctx.tap
+        if tap is not None:  # deferred: the tap's backward gathers all pending sets at once
+            tap.scales = scales
+            if dout.is_cuda:  # the tap may run on another stream than this node: mark the point its inputs are complete at
+                ev = torch.cuda.Event()
+                ev.record()
+                entry = entry._replace(event=ev)
+            tap.pending.append(entry)
+            return (*none, *([None] * nl))
+        return (*none, *_roi_gather(shapes, scales, [entry], dout.device))
 
 
+def roi_align(feats, rois, levels, out_size, scales, grad_scale=1.0):
+    tap = getattr(feats[0], "_u2_roi_tap", None)
+    if tap is not None and (ROI_ALIGN_BWD_ATOMIC or tap.ids != [id(f) for f in feats]):
+        tap = None  # not exactly the tapped list of maps: gather on the spot
+    return _ROIAlignFn.apply(rois, levels, out_size, tuple(scales), grad_scale, tap, *feats)
+
+
+# --------------------------------------------------------------------------------------------
+# the state of the backward folds (layers/deferred.py)
+# --------------------------------------------------------------------------------------------
 class _TailState:
     """What a residual block's tail (_BatchNormActFn: residual, ReLU, two handles) shares with the two consumers of its output:
     its saved tensors for the conv1 that may run its reduce; g2, the residual gradient the next tail posts; result, the
@@ -1645,294 +1109,3 @@ def assert_no_deferred_gradients():
         raise RuntimeError("%d deferred batch-norm gradients were not consumed by their convolutions, %d deferred ROIAlign "
                            "gathers not by their fan-out nodes, %d residual-tail gradients not by their tails"
                            % (left[deferred.BN_APPLY], left[deferred.ROI_GATHER], left[deferred.TAIL]))
-
-
-ROI_ORDER_MIN = int(os.environ.get("U2_ROI_ORDER_MIN", "1000000000"))
-
-
-def _roi_process_order(rois, levels, nimg, nlevels):
-    """Processing order of the ROIAlign forward: sorted by (level, image, top row of the box at its level / 8)."""
-    key = (levels.long() * nimg + rois[:, 0].long()) * 4096 + (rois[:, 2] * (0.25 / 8)).long().clamp_(0, 4095)
-    return torch.argsort(key).to(torch.int32)
-
-
-class _ROIAlignFn(Function):
-    """Multi-level ROIAlign(aligned=True, sampling_ratio=0) (modeling/poolers.py:206-263)."""
-
-    @staticmethod
-    def forward(ctx, rois, levels, out_size, scales, grad_scale, tap, *feats):
-        nl = len(feats)
-        for f in feats:
-            _check_act(f)
-        c = feats[0].shape[3]
-        r = rois.shape[0]
-        ptrs = (ctypes.c_void_p * nl)(*[f.data_ptr() for f in feats])
-        hs, ws, sc = _level_arrays([f.shape for f in feats], scales)
-        out = torch.empty((r, out_size, out_size, c), dtype=BF16, device=rois.device)
-        order = _roi_process_order(rois, levels, feats[0].shape[0], nl) if r >= ROI_ORDER_MIN else None
-        _hip.call("u2_roi_align_fwd", ptrs, hs, ws, sc, nl, rois.contiguous(), levels.contiguous(), order, out, r, c, out_size,
-                  out_size)
-        ctx.save_for_backward(rois, levels)
-        ctx.cfg = (out_size, scales, grad_scale, [tuple(f.shape) for f in feats])
-        ctx.tap = tap
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        rois, levels = ctx.saved_tensors
-        out_size, scales, grad_scale, shapes = ctx.cfg
-        nl = len(shapes)
-        b = shapes[0][0]
-        r, c = rois.shape[0], shapes[0][3]
-        none = (None,) * 6
-        if ROI_ALIGN_BWD_ATOMIC:
-            hs, ws, sc = _level_arrays(shapes, scales)
-            gbuf = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in shapes]
-            ptrs = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbuf])
-            _hip.call("u2_roi_align_bwd", ptrs, hs, ws, sc, nl, rois.contiguous(), levels.contiguous(), dout.contiguous(),
-                      r, c, out_size, out_size, float(grad_scale))
-            return (*none, *[g.to(BF16) for g in gbuf])
-        order, seg = _roi_group(rois, levels, b, nl)
-        entry = _RoiSet(rois, order, seg, dout, out_size, grad_scale)
-        tap = ctx.tap
-        if tap is not None:  # deferred: the tap's backward gathers all pending sets at once
-            tap.scales = scales
-            if dout.is_cuda:  # the tap may run on another stream than this node: mark the point its inputs are complete at
-                ev = torch.cuda.Event()
-                ev.record()
-                entry = entry._replace(event=ev)
-            tap.pending.append(entry)
-            return (*none, *([None] * nl))
-        return (*none, *_roi_gather(shapes, scales, [entry], dout.device))
-
-
-ROI_ALIGN_BWD_ATOMIC = False  # True selects the fp32-atomic scatter variant (kept for A/B tests)
-
-
-def roi_align(feats, rois, levels, out_size, scales, grad_scale=1.0):
-    tap = getattr(feats[0], "_u2_roi_tap", None)
-    if tap is not None and (ROI_ALIGN_BWD_ATOMIC or tap.ids != [id(f) for f in feats]):
-        tap = None  # not exactly the tapped list of maps: gather on the spot
-    return _ROIAlignFn.apply(rois, levels, out_size, tuple(scales), grad_scale, tap, *feats)
-
-
-def assign_levels(boxes, min_level, max_level, canonical_size=224, canonical_level=4):
-    n = boxes.shape[0]
-    lv = torch.empty(n, dtype=torch.int32, device=boxes.device)
-    _hip.call("u2_assign_levels", boxes.contiguous(), lv, n, min_level, max_level, float(canonical_size), canonical_level)
-    return lv
-
-
-def mask_crop(masks_u8, rois, size):
-    """BitMasks.crop_and_resize (structures/masks.py:191-218): masks [Nm,H,W] uint8, rois [R,5]."""
-    r = rois.shape[0]
-    out = torch.empty((r, size, size), dtype=torch.uint8, device=rois.device)
-    _hip.call("u2_mask_crop", masks_u8.contiguous(), rois.contiguous(), out, r, masks_u8.shape[1], masks_u8.shape[2], size)
-    return out
-
-
-def iou_match(boxes, gt, ngt, lo, hi, allow_low_quality):
-    """boxes [n,4] (shared) or [B,n,4]; gt [B,G,4]; ngt [B] int32 -> match [B,n] int32, labels [B,n] int8."""
-    per_image = boxes.dim() == 3
-    b, g = gt.shape[0], gt.shape[1]
-    n = boxes.shape[-2]
-    dev = gt.device
-    match = torch.empty((b, n), dtype=torch.int32, device=dev)
-    mval = torch.empty((b, n), dtype=torch.float32, device=dev)
-    labels = torch.empty((b, n), dtype=torch.int8, device=dev)
-    gmax = torch.empty((b, g), dtype=torch.int32, device=dev) if allow_low_quality else None
-    _hip.call("u2_iou_match", boxes.contiguous(), int(per_image), gt.contiguous(), ngt.contiguous(), match, mval, gmax,
-              labels, b, n, g, float(lo), float(hi), int(allow_low_quality))
-    return match, labels, mval
-
-
-def sem_seg_upsample(x, num_classes, scale):
-    """x [B, H, W, Cp] bf16 -> (fp32 [B, num_classes, H*scale, W*scale] bilinear-upsampled logits, int64 [B, H*scale, W*scale]
-    argmax) (u2_semseg_upsample; inference only)."""
-    _check_act(x)
-    b, h, w, cp = x.shape
-    out = torch.empty((b, num_classes, h * scale, w * scale), dtype=torch.float32, device=x.device)
-    amax = torch.empty((b, h * scale, w * scale), dtype=torch.int64, device=x.device)
-    _hip.call("u2_semseg_upsample", x, out, amax, b, h, w, cp, num_classes, int(scale))
-    return out, amax
-
-
-class _TopkSeg(ctypes.Structure):
-    """U2TopkSeg of include/u2seg_hip.h."""
-    _fields_ = ([(f, ctypes.c_void_p) for f in ("vals", "mask", "idx_in", "cnt_in", "out_vals", "out_idx", "out_cnt")]
-                + [("row_stride", ctypes.c_longlong)]
-                + [(f, ctypes.c_int) for f in ("dtype", "rows", "n", "group", "pitch", "mask_value", "k", "largest", "cnt_group",
-                                               "idx_mod", "idx_mul", "reserved")])
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def topk_rows(vals, k, largest=True, mask=None, mask_value=1, group=1, pitch=1, n=None, want_vals=True):
-    """Row-wise selection with a total order (u2_topk_rows): the k best of every row ranked by (value descending if
-    `largest` else ascending, index ascending).  vals: [rows, n] fp32 / bf16 contiguous, or - with group / pitch / n - the
-    `group` valid columns of a [rows, n // group, pitch]-shaped map (element i at (i // group) * pitch + i % group).
-    mask (int8 [rows, n]): only elements equal to mask_value take part.
-    Returns (values fp32 [rows, k] or None, indices int32 [rows, k], counts int32 [rows])."""
-    return topk_rows_multi([dict(vals=vals, k=k, largest=largest, mask=mask, mask_value=mask_value, group=group, pitch=pitch, n=n,
-                                 want_vals=want_vals)])[0]
-
-
-def topk_rows_multi(specs):
-    """Several independent selections (each a dict of topk_rows' arguments) in two launches of u2_topk_rows_multi instead of
-    one or two per selection: the per-level pre-NMS top-k of all feature levels, or the two draws of a sampler over the same keys.
-    A row is streamed by ONE work-group (five to seven dependent sweeps): long rows are cut into equal segments that are ranked
-    as rows of their own in the first launch (reporting positions in the full row), and the survivors (k per segment, the real
-    ones counted) are ranked again in the second.  Returns a list of (values or None, indices, counts)."""
-    first, second, results = [], [], [None] * len(specs)
-    keep = []  # the intermediate tensors are referenced by raw pointers only: they must outlive the launches below
-    for j, sp in enumerate(specs):
-        vals, k, largest = sp["vals"], int(sp["k"]), int(bool(sp.get("largest", True)))
-        if k > _TOPK_MAX_K:
-            # beyond the kernel's LDS-resident survivor list (e.g. PRE_NMS_TOPK = 12000 summed over the levels): a stable
-            # device sort gives the same total order
-            results[j] = _topk_rows_sorted(sp)
-            continue
-        mask, mask_value = sp.get("mask"), int(sp.get("mask_value", 1))
-        group, pitch, n, want_vals = int(sp.get("group", 1)), int(sp.get("pitch", 1)), sp.get("n"), sp.get("want_vals", True)
-        assert vals.is_cuda and vals.dtype in (torch.float32, BF16) and vals.is_contiguous()
-        dev, rows = vals.device, vals.shape[0]
-        if n is None:
-            assert vals.dim() == 2
-            n = vals.shape[1]
-        row_stride = vals[0].numel()
-        if mask is not None:
-            assert mask.dtype == torch.int8 and mask.is_contiguous() and tuple(mask.shape) == (rows, n)
-        idx = torch.empty((rows, k), dtype=torch.int32, device=dev)
-        out = torch.empty((rows, k), dtype=torch.float32, device=dev) if want_vals else None
-        cnt = torch.empty((rows,), dtype=torch.int32, device=dev)
-        results[j] = (out, idx, cnt)
-        dtype = 1 if vals.dtype == BF16 else 0
-        segs = _topk_segments(rows, n, group, pitch, row_stride, k)
-        if segs > 1:
-            seg_n = n // segs
-            k1 = min(k, seg_n)
-            v1 = torch.empty((rows * segs, k1), dtype=torch.float32, device=dev)
-            i1 = torch.empty((rows * segs, k1), dtype=torch.int32, device=dev)
-            c1 = torch.empty((rows * segs,), dtype=torch.int32, device=dev)
-            keep.append((v1, i1, c1))
-            first.append(_TopkSeg(_ptr(vals), _ptr(mask), None, None, _ptr(v1), _ptr(i1), _ptr(c1), row_stride // segs, dtype,
-                                  rows * segs, seg_n, group, pitch, mask_value, k1, largest, 1, segs, seg_n, 0))
-            # dtype 2: fp32 storage of bf16 values (the survivors of a bf16 map) - two digit sweeps instead of four
-            second.append(_TopkSeg(_ptr(v1), None, _ptr(i1), _ptr(c1), _ptr(out), _ptr(idx), _ptr(cnt), segs * k1, 2 * dtype, rows,
-                                   segs * k1, 1, 1, 0, k, largest, k1, 1, 0, 0))
-        else:
-            first.append(_TopkSeg(_ptr(vals), _ptr(mask), None, None, _ptr(out), _ptr(idx), _ptr(cnt), row_stride, dtype, rows, n,
-                                  group, pitch, mask_value, k, largest, 1, 1, 0, 0))
-    for batch in (first, second):
-        batch.sort(key=lambda g: -g.n)  # the longest rows start first
-        for at in range(0, len(batch), 8):
-            part = batch[at:at + 8]
-            _hip.call("u2_topk_rows_multi", (_TopkSeg * len(part))(*part), len(part))
-    del keep
-    return results
-
-
-_TOPK_MAX_K = 16384  # u2_topk_rows keeps the k survivors of a row in LDS (8 bytes each)
-
-
-def _topk_rows_sorted(sp):
-    """topk_rows for k beyond the kernel's limit: torch's stable sort on the device under the same total order (value descending /
-    ascending, index ascending; -0.0 equal to +0.0), same outputs (padding: index 0, value -/+ inf)."""
-    vals, k, largest = sp["vals"], int(sp["k"]), bool(sp.get("largest", True))
-    mask, mask_value = sp.get("mask"), int(sp.get("mask_value", 1))
-    group, pitch, n = int(sp.get("group", 1)), int(sp.get("pitch", 1)), sp.get("n")
-    rows = vals.shape[0]
-    if n is None:
-        n = vals.shape[1]
-    v = vals.reshape(rows, -1)
-    if group != 1 or pitch != 1:
-        v = v.reshape(rows, -1, pitch)[:, : n // group, :group].reshape(rows, n)
-    v = v[:, :n].float()
-    fill = float("-inf") if largest else float("inf")
-    part = torch.ones_like(v, dtype=torch.bool) if mask is None else (mask == mask_value)
-    order = torch.sort(torch.where(part, v, torch.full_like(v, fill)), dim=1, descending=largest, stable=True)[1]
-    # elements that do not take part may tie with real -inf / +inf values: rank them last explicitly
-    order = torch.gather(order, 1, torch.sort((~torch.gather(part, 1, order)).to(torch.int8), dim=1, stable=True)[1])[:, :k]
-    cnt = part.sum(dim=1).clamp(max=k).to(torch.int32)
-    real = torch.arange(order.shape[1], device=v.device)[None] < cnt[:, None]
-    idx = torch.where(real, order, torch.zeros_like(order)).to(torch.int32)
-    out = None
-    if sp.get("want_vals", True):
-        out = torch.where(real, torch.gather(v, 1, order), torch.full_like(v[:, : order.shape[1]], fill))
-    if idx.shape[1] < k:  # k larger than the row
-        pad = k - idx.shape[1]
-        idx = torch.nn.functional.pad(idx, (0, pad))
-        out = torch.nn.functional.pad(out, (0, pad), value=fill) if out is not None else None
-    return out, idx, cnt
-
-
-def _topk_segments(rows, n, group, pitch, row_stride, k):
-    """How many equal segments to cut the rows of a selection into (1 = none): only long rows that few work-groups would
-    stream, a divisor of the group count (segments must tile the row exactly), segments still several times longer than k.
-    The first launch streams n / s elements per work-group, the merging second one s * k (at about twice the cost per element:
-    fp32 keys, carried indices): s is the admissible divisor nearest to sqrt(n / 2k)."""
-    if n < 32768 or rows >= 128 or n % group or row_stride != (n // group) * pitch:
-        return 1
-    groups = n // group
-    target = math.sqrt(n / (2.0 * k))
-    best, best_d = 1, None
-    for s in range(2, 33):
-        if groups % s == 0 and n // s >= max(4096, 2 * k) and rows * s <= 256:
-            d = abs(math.log(s / target))
-            if best_d is None or d < best_d:
-                best, best_d = s, d
-    return best
-
-
-def apply_deltas(src, deltas, weights, img_idx=None, sizes=None, clamp=math.log(1000.0 / 16)):
-    n = src.shape[0]
-    out = torch.empty((n, 4), dtype=torch.float32, device=src.device)
-    do_clip = sizes is not None
-    _hip.call("u2_apply_deltas", src.contiguous(), deltas.contiguous(), img_idx, sizes, out, n, weights[0], weights[1],
-              weights[2], weights[3], float(clamp), int(do_clip))
-    return out
-
-
-class _RpnLevel(ctypes.Structure):
-    """U2RpnLevel of include/u2seg_hip.h."""
-    _fields_ = ([(f, ctypes.c_void_p) for f in ("deltas", "anchors", "idx", "scores")]
-                + [(f, ctypes.c_int) for f in ("hwa", "k", "pitch", "reserved")])
-
-
-def rpn_decode(levels, num_anchors, batch, kmax, sizes, weights, clamp, min_size):
-    """Decoded, clipped and filtered RPN candidates of all levels in one launch (u2_rpn_decode).  levels: list of dicts with
-    deltas (NHWC bf16 view whose channel 0 is the first delta), anchors [hwa, 4] fp32, idx [B, k] int32, scores [B, k] fp32.
-    Returns boxes [B * L, kmax, 4], scores [B * L, kmax] (row = image * L + level), keep int8 [B * L, kmax], nonfinite int32 [1]."""
-    dev = sizes.device
-    rows = batch * len(levels)
-    boxes = torch.empty((rows, kmax, 4), dtype=torch.float32, device=dev)
-    scores = torch.empty((rows, kmax), dtype=torch.float32, device=dev)
-    keep = torch.empty((rows, kmax), dtype=torch.int8, device=dev)
-    nonfinite = zeros_f32((1,), dev).view(torch.int32)
-    segs = []
-    for lv in levels:
-        d, anc, idx, sc = lv["deltas"], lv["anchors"], lv["idx"], lv["scores"]
-        assert d.dtype == BF16 and d.dim() == 4 and d.stride(3) == 1 and d.stride(2) == d.stride(1) // d.shape[2]
-        assert anc.dtype == torch.float32 and anc.is_contiguous() and idx.dtype == torch.int32 and idx.is_contiguous()
-        assert sc.dtype == torch.float32 and sc.is_contiguous() and tuple(idx.shape) == tuple(sc.shape) == (batch, idx.shape[1])
-        hwa = d.shape[1] * d.shape[2] * num_anchors
-        assert anc.shape[0] == hwa and d.stride(0) == d.shape[1] * d.shape[2] * d.stride(2)
-        segs.append(_RpnLevel(d.data_ptr(), anc.data_ptr(), idx.data_ptr(), sc.data_ptr(), hwa, idx.shape[1], d.stride(2), 0))
-    _hip.call("u2_rpn_decode", (_RpnLevel * len(segs))(*segs), len(segs), num_anchors, batch, kmax, sizes, float(weights[0]),
-              float(weights[1]), float(weights[2]), float(weights[3]), float(clamp), float(min_size), boxes, scores, keep, nonfinite)
-    return boxes, scores, keep, nonfinite
-
-
-def batched_nms(boxes, group, counts, thr, max_keep):
-    """boxes [B,n,4] sorted by descending score, group [B,n] int32, counts [B] int32 ->
-    keep [B,max_keep] int32 (positions in the sorted order), nkeep [B] int32."""
-    b, n = boxes.shape[0], boxes.shape[1]
-    ws_bytes = _hip.call_nostream("u2_nms_workspace_bytes", b, n)
-    ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=boxes.device)
-    keep = torch.zeros((b, max_keep), dtype=torch.int32, device=boxes.device)
-    nkeep = torch.zeros(b, dtype=torch.int32, device=boxes.device)
-    _hip.call("u2_batched_nms", boxes.contiguous(), group.contiguous(), counts.contiguous(), ws, keep, nkeep, b, n,
-              float(thr), max_keep)
-    return keep, nkeep

@@ -196,11 +196,11 @@ class PanopticFPN(GeneralizedRCNN):
         # kernels fill the chip while the proposal / sampling bookkeeping of the other branch occupies a few CUs at a time
         # (autograd replays every node on the stream of its forward pass, so the backward passes overlap the same way).
         aux = F.aux_stream(self.device) if sem_f[self.sem_seg_head.in_features[0]].is_cuda else None
-        F.clear_deferred()
+        F.clear_branch_pieces()
         if aux is not None and os.environ.get("U2_SEM_PIECES", "1") != "0":
             # Round 6: the head is handed over in pieces (level stacks, then predictor + loss) that the ROI heads launch - on `aux` -
             # where their own chain is about to be host-bound: in front of the sampler's host synchronisation, between the cascade
-            # stages, in front of the losses (layers/functional.py:defer_pieces).  Launched as a whole in front of the RPN (rounds
+            # stages, in front of the losses (layers/streams.py:queue_branch_pieces).  Launched as a whole in front of the RPN (rounds
             # 2-5) it ran beside the RPN's convolutions and was finished when the idle stretches began (tools/step_idle.py).
             sem_seg_losses = {}
             main = torch.cuda.current_stream(self.device)
@@ -218,12 +218,12 @@ class PanopticFPN(GeneralizedRCNN):
 
             pieces = [on_aux(pc) for pc in self.sem_seg_head.training_pieces(sem_f, gt_sem_seg, sem_seg_losses)]
             # two pieces per call site at first (stride 4 and 8: the two long ones), then one: five pieces over four call sites
-            F.defer_pieces([lambda a=pieces[0], b=pieces[1]: (a(), b())] + pieces[2:] if len(pieces) > 4 else pieces)
+            F.queue_branch_pieces([lambda a=pieces[0], b=pieces[1]: (a(), b())] + pieces[2:] if len(pieces) > 4 else pieces)
             for t in list(sem_f.values()) + [gt_sem_seg]:
                 t.record_stream(aux)
             proposals, proposal_losses = self.proposal_generator(image_sizes, rpn_f, gt_instances)
             _, detector_losses = self.roi_heads(None, roi_f, proposals, gt_instances)
-            F.flush_deferred()
+            F.flush_branch_pieces()
         else:
             if aux is not None:
                 main = torch.cuda.current_stream(self.device)

@@ -490,7 +490,7 @@ class ROIHeads(nn.Module):
         s = sampled.shape[1]
         flags = [cvalid.sum(dim=1)] + ([lp.finite.reshape(1).to(torch.int64)] if lp.finite is not None else [])
         vals = torch.cat(flags).tolist()  # the one host synchronisation of the sampler
-        F.issue_deferred_piece()  # the chip is idle from here until the first stage's kernels are launched (functional.defer_pieces)
+        F.issue_branch_piece()  # the chip is idle from here until the first stage's kernels are launched (streams.queue_branch_pieces)
         if lp.finite is not None:
             check_finite(bool(vals[-1]), self.training)
             lp.finite = None
@@ -700,7 +700,7 @@ class CascadeROIHeads(StandardROIHeads):
             head_outputs.append((self.box_predictor[k], predictions, proposals))
         if self.training:
             losses = {}
-            F.issue_deferred_piece()
+            F.issue_branch_piece()
             storage = get_event_storage() if has_event_storage() else None
             for stage, (predictor, predictions, props) in enumerate(head_outputs):
                 # cascade_rcnn.py:180-184: the stage's statistics are named stage{k}/...; the scope also selects its counters
@@ -757,7 +757,7 @@ class CascadeROIHeads(StandardROIHeads):
         if not bool(nonempty.all()):  # cascade_rcnn.py:291-294: ragged result, take the per-image path
             props = self._create_proposals_from_boxes(list(boxes), image_sizes)
             return self._match_and_label_boxes(props, stage, targets)
-        F.issue_deferred_piece()  # behind the host synchronisation: match / relabel below are ~20 tiny launches
+        F.issue_branch_piece()  # behind the host synchronisation: match / relabel below are ~20 tiny launches
         pt = PaddedTargets.of(targets, dev)
         thr = self.cascade_ious[stage]
         match, labels, _ = F.iou_match(boxes.contiguous(), pt.boxes, pt.counts, thr, thr, False)

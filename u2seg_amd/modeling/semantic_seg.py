@@ -88,7 +88,7 @@ class SemSegFPNHead(nn.Module):
         """The training forward pass as closures that launch it piece by piece, in the order of `layers` (level stacks from the
         common stride upwards, each adding the running sum; predictor + loss last): `out` receives {"loss_sem_seg"} with the last
         piece.  Same kernels in the same order as forward(): where the pieces are launched is the caller's business
-        (layers.functional.defer_pieces)."""
+        (layers.streams.queue_branch_pieces)."""
         state = {"x": None}
 
         def level(f, head):

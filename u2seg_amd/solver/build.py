@@ -60,7 +60,7 @@ class FlatSGD:
             self.flat_param[off : off + n].copy_(p.data.reshape(-1))
             p.data = self.flat_param[off : off + n].view(p.shape)
             p.grad = self.flat_grad[off : off + n].view(p.shape)
-            p._u2_grad = p.grad  # layers/functional.py:grad_slot - kernels accumulate into the arena directly
+            p._u2_grad = p.grad  # layers/weights.py:grad_slot - kernels accumulate into the arena directly
             wds.append(wd_of[id(p)])
             first_chunk.append(len(chunk_tensor))
             for s in range(0, n, CHUNK):
@@ -85,7 +85,7 @@ class FlatSGD:
         self.bucket_elems = bucket_bytes // 4
         self._pending, self._tail_from = [], None
         self._exchange_stream, self._step_stream = None, None
-        # bf16 kernel layouts cached on the parameters (layers/functional.py:_weight_layout): [stamp] is shared with every
+        # bf16 kernel layouts cached on the parameters (layers/weights.py:_weight_layout): [stamp] is shared with every
         # parameter; step() bumps it and rewrites all registered layouts with one launch.
         self._stamp = [0]
         self._layout_entries = []  # (param, key, entry)
