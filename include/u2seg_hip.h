@@ -838,7 +838,9 @@ int u2_kmeans_assign_shadow(const float* x, const float* shadow, const float* c,
 /* csum [K][D] += sum of the rows of x by label, counts [K] += label histogram (both pre-zeroed by the caller, or holding
  * another shard's partial sums).  workspace (optional, u2_kmeans_update_workspace_floats(N, D, K) floats): the points are
  * bucketed by label there and the sums become a segmented reduction that reads every row of x once, whole (0.75 -> ~4 TB/s);
- * without it a privatised-LDS kernel is used. */
+ * without it, or with D > 2048, a privatised-LDS kernel is used.  In both forms a label outside [0, K) (tested as int64) belongs to
+ * no cluster.  Returns -1 and launches nothing for a K no form serves (K > 16384 with a workspace, K > 2168 without); N <= 0: 0.
+ * u2_kmeans_finalize: c = csum / counts elementwise (an empty cluster: 0 / 0 = NaN, as in the reference). */
 long long u2_kmeans_update_workspace_floats(int N, int D, int K);
 int u2_kmeans_update(const float* x, const long long* labels, float* csum, float* counts, int N, int D, int K,
                      float* workspace, void* stream);

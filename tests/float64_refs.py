@@ -1,5 +1,5 @@
 """Float64 reference helpers of tests/test_gpu_optim_resample_float64.py, tests/test_gpu_conv_float64.py,
-tests/test_gpu_inference_tails_float64.py and tests/test_gpu_box_decisions_float64.py, in a plain module so that the CPU tests of
+tests/test_gpu_inference_tails_float64.py, tests/test_gpu_box_decisions_float64.py and tests/test_gpu_kmeans_update_float64.py, in a plain module so that the CPU tests of
 tests/test_float64_refs_host.py check exactly what the GPU tests use.  Plain torch ops only; nothing here touches the HIP
 library.  Every function works on whatever device its inputs live on."""
 import math
@@ -879,3 +879,83 @@ def delta_random_case(n, seed, weights):
 CASCADE_WEIGHTS = [(10.0, 10.0, 5.0, 5.0), (20.0, 20.0, 10.0, 10.0), (30.0, 30.0, 15.0, 15.0)]
 SCALE_CLAMP = math.log(1000.0 / 16)
 DELTA_SIZES = [[64.0, 80.0], [50.0, 77.0], [333.0, 500.0]]   # (h, w) of three images
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# k-means (u2seg_amd/csrc/kmeans.hip): the M step's sums and the E step's arg-min
+# ----------------------------------------------------------------------------------------------------------------------------
+U24 = 2.0 ** -24       # unit roundoff of fp32
+
+
+def gamma32(m):
+    """gamma_m = m u / (1 - m u), u = 2^-24, elementwise in float64: fp32 summation of n terms in ANY order and association
+    (atomics included) obeys |fl(sum) - sum| <= gamma_(n-1) sum |x_i| (Higham, Accuracy and Stability, section 4.2)."""
+    m = torch.as_tensor(m, dtype=F64)
+    return m * U24 / (1 - m * U24)
+
+
+def kmeans_update_ref(x, labels, k):
+    """The M step's raw material in float64: (sums [K, D] = sum of the rows of x by label, counts [K] int64,
+    sum_abs [K, D] = sum of |x| by label).  A label outside [0, K) belongs to no cluster.  Sums start from +0 and rows are added to
+    them (index_add_), so a cluster of -0.0 rows sums to +0 as any accumulator that starts from zero does."""
+    x64 = x.to(F64)
+    k, d = int(k), x.shape[1]
+    ok = (labels >= 0) & (labels < k)
+    idx, rows = labels[ok], x64[ok]
+    sums = torch.zeros((k, d), dtype=F64, device=x.device).index_add_(0, idx, rows)
+    sum_abs = torch.zeros((k, d), dtype=F64, device=x.device).index_add_(0, idx, rows.abs())
+    return sums, torch.bincount(idx, minlength=k), sum_abs
+
+
+def kmeans_argmin_ref(x, c, budget=1 << 26):
+    """The E step in float64, difference form: d_ij = sum_d (x_id - c_jd)^2, label = torch.argmin's choice - a NaN distance beats
+    every number, the first index wins among equals (spelled out as NaN -> -inf so that it holds on every device; a squared
+    distance is never -inf itself).  Also the relative gap (second - best) / best between the two smallest FINITE distances of
+    every point (inf where fewer than two are finite): points with a gap far above fp32 rounding have one defensible label.
+    Row-chunked: at most `budget` float64 differences at a time.  Returns (labels int64 [N], gap float64 [N])."""
+    x64, c64 = x.to(F64), c.to(F64)
+    n, (k, d) = x.shape[0], c.shape
+    labels = torch.empty(n, dtype=torch.int64, device=x.device)
+    gap = torch.empty(n, dtype=F64, device=x.device)
+    step = max(1, budget // max(1, k * d))
+    for s in range(0, n, step):
+        dist = ((x64[s: s + step, None, :] - c64[None, :, :]) ** 2).sum(-1)
+        labels[s: s + step] = torch.argmin(torch.where(torch.isnan(dist), float("-inf"), dist), dim=1)
+        fin = torch.where(torch.isfinite(dist), dist, float("inf"))
+        if k >= 2:
+            two = torch.topk(fin, 2, dim=1, largest=False).values
+            rel = torch.where(two[:, 1] == two[:, 0], 0.0, (two[:, 1] - two[:, 0]) / two[:, 0])     # 0 / 0: a tie at distance 0
+            gap[s: s + step] = torch.where(torch.isfinite(two[:, 1]), rel, float("inf"))
+        else:
+            gap[s: s + step] = float("inf")
+    return labels, gap
+
+
+KM_RUN_ENDS = [7, 8, 9, 16, 255, 256, 257, 264, 511, 512, 513, 520, 767, 768, 769, 1024, 1279, 1280, 1281]
+
+
+def kmeans_labels(pattern, n, k, gen):
+    """Label patterns of the M-step tests (int64 [N] on the CPU, every label in [0, K)):
+      uniform  random;                      sorted  the same, ascending;
+      rr       i % K: the label changes on every entry of the label-ordered list's walk and on each of the rows in flight;
+      first / last   all 0 / all K - 1: one label over every work-group;
+      runs     ascending runs that end at KM_RUN_ENDS - on multiples of 8 (the rows in flight) and of 256 (a work-group's entries)
+               and one entry either side -, the last run takes the rest (labels past K - 1 fold onto K - 1);
+      holes    random, with clusters 0, K - 1 and the block [K / 3, K / 2) left empty (needs K >= 8)."""
+    if pattern == "uniform":
+        return torch.randint(0, k, (n,), generator=gen)
+    if pattern == "sorted":
+        return torch.randint(0, k, (n,), generator=gen).sort().values
+    if pattern == "rr":
+        return torch.arange(n) % k
+    if pattern == "first":
+        return torch.zeros(n, dtype=torch.int64)
+    if pattern == "last":
+        return torch.full((n,), k - 1, dtype=torch.int64)
+    if pattern == "runs":
+        return torch.searchsorted(torch.tensor(KM_RUN_ENDS), torch.arange(n), right=True).clamp(max=k - 1)
+    if pattern == "holes":
+        assert k >= 8
+        allowed = torch.tensor([j for j in range(1, k - 1) if not k // 3 <= j < k // 2])
+        return allowed[torch.randint(0, allowed.numel(), (n,), generator=gen)]
+    raise ValueError(pattern)

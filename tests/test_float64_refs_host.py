@@ -506,3 +506,95 @@ def test_mask_crop_random_case_margin_on_the_cpu():
     assert float(near.double().mean()) <= 1e-3
     assert torch.equal((v32 >= 0.5)[~near], (avg >= 0.5)[~near])
     assert 0.2 < float((avg >= 0.5).double().mean()) < 0.8
+
+
+def test_kmeans_update_ref_equals_the_oracle_and_a_hand_worked_case():
+    """kmeans_update_ref: four points worked by hand (an out-of-range label on either side, an empty cluster); sums / counts ==
+    oracle.ops.kmeans_update's centroids (scatter_add_ + bincount in float64) on in-range labels; sum_abs against a loop."""
+    from oracle import ops as O
+
+    x = torch.tensor([[1.0, -2.0], [3.0, 4.0], [-5.0, 6.0], [7.0, 8.0], [100.0, 100.0], [-100.0, 100.0]])
+    lab = torch.tensor([2, 0, 2, 0, -1, 3])
+    s, n, a = R.kmeans_update_ref(x, lab, 3)
+    assert s.dtype == F64 and n.dtype == torch.int64 and a.dtype == F64
+    assert s.tolist() == [[10.0, 12.0], [0.0, 0.0], [-4.0, 4.0]] and n.tolist() == [2, 0, 2]
+    assert a.tolist() == [[10.0, 12.0], [0.0, 0.0], [6.0, 8.0]]
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn((500, 7), generator=g)
+    x[::5] *= 1e3
+    for pattern in ("uniform", "rr", "holes", "runs"):
+        lab = R.kmeans_labels(pattern, 500, 23, g)
+        assert int(lab.min()) >= 0 and int(lab.max()) < 23
+        s, n, a = R.kmeans_update_ref(x, lab, 23)
+        want_c, want_n = O.kmeans_update(x.double(), lab, 23)
+        assert torch.equal(n.double(), want_n)
+        full = n > 0
+        assert float(((s / n[:, None])[full] - want_c[full]).abs().max()) <= 1e-12 * float(want_c[full].abs().max())
+        assert bool(torch.isnan(want_c[~full]).all()) and not bool(s[~full].any())
+        for j in range(23):
+            assert float((a[j] - x[lab == j].double().abs().sum(0)).abs().max()) <= 1e-12 * (1 + float(a[j].max()))
+        if pattern == "holes":
+            assert n[0] == 0 and n[22] == 0 and not bool(n[7:11].any()) and bool((n[1:7] > 0).all())
+    # a cluster of -0.0 rows sums to +0; a NaN row poisons its own cluster only
+    x = torch.tensor([[-0.0, 1.0], [float("nan"), 2.0], [3.0, float("inf")]])
+    s, n, a = R.kmeans_update_ref(x, torch.tensor([0, 1, 2]), 3)
+    assert not bool(torch.signbit(s[0, 0])) and bool(torch.isnan(s[1, 0])) and float(s[2, 1]) == float("inf")
+    assert int(torch.isnan(s).sum()) == 1 and int(torch.isinf(s).sum()) == 1
+
+
+def test_kmeans_label_runs_end_where_the_kernel_counts():
+    lab = R.kmeans_labels("runs", 2000, 300, None)
+    ends = (torch.nonzero(lab[1:] != lab[:-1])[:, 0] + 1).tolist()
+    assert ends == R.KM_RUN_ENDS and all(e in ends for e in (7, 8, 9, 255, 256, 257, 511, 512, 513))
+    assert int(R.kmeans_labels("runs", 2000, 5, None).max()) == 4
+    assert R.kmeans_labels("rr", 10, 3, None).tolist() == [0, 1, 2, 0, 1, 2, 0, 1, 2, 0]
+
+
+def test_gamma32_is_highams_constant():
+    g = R.gamma32(torch.tensor([0, 1, 1000, 1 << 17]))
+    assert g[0] == 0 and g[1] == 2.0 ** -24 / (1 - 2.0 ** -24) and abs(float(g[3]) - 2.0 ** -7 / (1 - 2.0 ** -7)) < 1e-18
+    # fp32 summation in two different orders stays inside the bound (the bound is what the GPU tests use, not these sums)
+    x = torch.randn(1000, generator=torch.Generator().manual_seed(1)) * 100
+    exact, abs_sum = float(x.double().sum()), float(x.double().abs().sum())
+    seq = torch.zeros((), dtype=torch.float32)
+    for v in x:
+        seq = seq + v
+    for got in (float(seq), float(x.sum())):
+        assert abs(got - exact) <= float(R.gamma32(999)) * abs_sum
+
+
+def test_kmeans_argmin_ref_equals_the_oracle_and_torch_argmin_on_nan():
+    """kmeans_argmin_ref == oracle.ops.kmeans_assign in float64 on finite centroids, whatever the chunking; with NaN rows it is
+    torch.argmin of the distance matrix (the NaN wins, the first NaN among several); the gap is the relative distance between the
+    two nearest FINITE centroids; a duplicated centroid is a zero gap decided for the lower index."""
+    from oracle import ops as O
+
+    g = torch.Generator().manual_seed(9)
+    cen = torch.randn((12, 16), generator=g) * 2
+    x = cen[torch.randint(0, 12, (300,), generator=g)] + 0.5 * torch.randn((300, 16), generator=g)
+    c = cen + 0.3 * torch.randn((12, 16), generator=g)
+    lab, gap = R.kmeans_argmin_ref(x, c)
+    assert torch.equal(lab, O.kmeans_assign(x.double(), c.double()))
+    lab2, gap2 = R.kmeans_argmin_ref(x, c, budget=16 * 12 * 7)      # chunks of 7 rows
+    assert torch.equal(lab, lab2) and torch.equal(gap, gap2)
+    d = ((x.double()[:, None] - c.double()[None]) ** 2).sum(-1)
+    two = d.sort(dim=1).values[:, :2]
+    assert torch.equal(gap, (two[:, 1] - two[:, 0]) / two[:, 0]) and float(gap.min()) > 1e-3
+    for rows, want in (((5,), 5), ((7, 3), 3), ((0, 11), 0)):
+        cn = c.clone()
+        for r in rows:
+            cn[r, 2] = float("nan")
+        labn, gapn = R.kmeans_argmin_ref(x, cn)
+        dn = ((x.double()[:, None] - cn.double()[None]) ** 2).sum(-1)
+        assert torch.equal(labn, torch.argmin(dn, dim=1)) and bool((labn == want).all())
+        keep = [j for j in range(12) if j not in rows]
+        assert torch.equal(gapn, R.kmeans_argmin_ref(x, c[keep])[1])
+    cd = c.clone()
+    cd[9] = cd[4]
+    labd, gapd = R.kmeans_argmin_ref(x, cd)
+    assert not bool((labd == 9).any()) and bool((gapd[lab == 4] == 0).all()) and bool((labd[lab == 4] == 4).all())
+    cf = c.clone()
+    cf[6] = 1e20
+    labf, _ = R.kmeans_argmin_ref(x, cf)
+    assert not bool((labf == 6).any()) and torch.equal(labf[lab != 6], lab[lab != 6])
+    assert R.kmeans_argmin_ref(x[:3], c[:1])[1].tolist() == [float("inf")] * 3

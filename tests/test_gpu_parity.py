@@ -1061,7 +1061,7 @@ def test_kmeans_config4_full_size_properties(data_kind):
         want = x[rows].double().mean(0)
         assert float((cn[j].double() - want).abs().max()) <= 1e-5 * max(1.0, float(want.abs().max())), j
     # second iteration on the updated centroids (the empty cluster's NaN row parked far away again: what a NaN centroid does to
-    # the arg-min is the subject of test_kmeans_vs_oracle, not of this size test)
+    # the arg-min is the subject of test_gpu_kmeans_update_float64.py::test_assign_with_non_finite_centroids, not of this size test)
     c2 = cn.clone()
     c2[k - 1] = 1.0e3
     lab2 = KM.assign(x, c2)

@@ -902,3 +902,21 @@ def test_host_thread_cap_and_image_index(monkeypatch):
     got = image_index(sizes, "cpu")
     want = torch.repeat_interleave(torch.arange(4, dtype=torch.float32), torch.tensor(sizes))
     assert got.dtype == torch.float32 and torch.equal(got, want)
+
+
+def test_kmeans_update_refuses_labels_the_kernel_would_misread():
+    """KM.update / KM.update_sharded hand `labels` to the kernel as N raw int64 words on x's device: a tensor of another type,
+    stride, device or length is an error before anything is allocated or launched (CPU tensors: a launch would fail differently)."""
+    from u2seg_amd.cluster import kmeans as KM
+
+    x = torch.zeros((6, 4))
+    good = torch.zeros(6, dtype=torch.int64)
+    bad = {"dtype": good.int(), "float": good.float(), "stride": torch.zeros(12, dtype=torch.int64)[::2], "short": good[:5],
+           "long": torch.zeros(7, dtype=torch.int64), "2-d": good.view(6, 1), "device": torch.zeros(6, dtype=torch.int64, device="meta"),
+           "list": [0] * 6}
+    for fn in (KM.update, KM.update_sharded):
+        for name, lab in bad.items():
+            with pytest.raises(ValueError, match="labels"):
+                fn(x, lab, 3)
+    KM._check_labels(x, good)
+    KM._check_labels(x[:0], good[:0])

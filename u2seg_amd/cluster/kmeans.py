@@ -106,9 +106,23 @@ def last_coarse_undecided(device):
     return int(ws.view(torch.int32)[((k + 3) & ~3) + (2 if mode == "two-level" else 1)])   # "blocks": its undecided ARE the re-checked
 
 
+def _check_labels(x, labels):
+    """The kernels read `labels` as N raw int64 words on x's device: anything else would be misread without a word."""
+    n = x.shape[0]
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64:
+        raise ValueError("k-means labels must be an int64 tensor, got %s" % (getattr(labels, "dtype", type(labels)),))
+    if labels.device != x.device:
+        raise ValueError("k-means labels are on %s, x is on %s" % (labels.device, x.device))
+    if labels.dim() != 1 or labels.numel() != n:
+        raise ValueError("k-means labels must have shape [%d], got %s" % (n, tuple(labels.shape)))
+    if not labels.is_contiguous():
+        raise ValueError("k-means labels must be contiguous")
+
+
 def update(x, labels, k):
     """c = scatter_add(x by label) / bincount(label) -> (centroids [K, D], counts [K])."""
     n, d = x.shape
+    _check_labels(x, labels)
     buf = torch.zeros(k * d + k, dtype=torch.float32, device=x.device)    # one fill for both
     csum, counts = buf[: k * d].view(k, d), buf[k * d:]
     _hip.call("u2_kmeans_update", x.contiguous(), labels, csum, counts, n, d, k, _update_workspace(n, d, k, x.device))
@@ -131,6 +145,7 @@ def update_sharded(x_local, labels_local, k, group=None):
     counts, one all-reduce of (K*D + K) floats (0.92 MB at K = 300, D = 768), then the division - every rank ends up
     with the same centroids, labels stay sharded."""
     n, d = x_local.shape
+    _check_labels(x_local, labels_local)
     buf = torch.zeros(k * d + k, dtype=torch.float32, device=x_local.device)
     csum, counts = buf[: k * d].view(k, d), buf[k * d :]
     if n:

@@ -1144,7 +1144,8 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const float* __restr
       l[u] = -1;
       v[u] = float4{0.f, 0.f, 0.f, 0.f};
       if (p < pe) {
-        l[u] = (int)labels[p];
+        const long long lab = labels[p];
+        l[u] = (lab >= 0 && lab < K) ? (int)lab : -1;   // as the bucketing kernels: a label outside [0, K) is no cluster's member
         const float* src = x + (size_t)p * D + dq;
         if (vec) {
           v[u] = *reinterpret_cast<const float4*>(src);
