@@ -392,6 +392,18 @@ int u2_count_labels_i8(const void* labels, long long n, int* counters, void* str
 int u2_rpn_loss_level(const void* obj, const void* dlt, const void* labels, const int* match, const float* gt,
                       const float* anchors, void* dobj, void* ddlt, float* loss, int B, int HW, int A, int LPo, int LPd,
                       int Atot, int lvl_off, int G, float gscale, void* stream);
+/* u2_rpn_loss_level with the localisation loss options (MODEL.RPN.BBOX_REG_LOSS_TYPE, SMOOTH_L1_BETA, BBOX_REG_WEIGHTS): same
+ * arguments, layouts (separate maps, or dlt == ddlt == NULL for the fused A == 3 map) and objectness part.  The positives' deltas
+ * are scored by `kind` (the U2_BOXLOSS_* codes below) with the anchor as the source box: SMOOTH_L1 on
+ * delta - get_deltas(anchor, gt; weights), quadratic below beta and plain L1 at beta == 0; GIOU / DIOU / CIOU on
+ * apply_deltas(delta, anchor; weights, scale_clamp) against the matched gt, the gradient taken through the decode (0 through a
+ * clamped dw / dh, CIoU's alpha constant).  The delta gradient is exactly 0 for anchors whose label is not 1 and in every pad
+ * column; the launch writes the whole gradient map(s).  With kind SMOOTH_L1, beta 0 and unit weights it returns
+ * u2_rpn_loss_level's bits.  An unknown kind, beta < 0 or a weight <= 0 returns -1. */
+int u2_rpn_loss_level_opt(int kind, const void* obj, const void* dlt, const void* labels, const int* match, const float* gt,
+                          const float* anchors, void* dobj, void* ddlt, float* loss, int B, int HW, int A, int LPo, int LPd,
+                          int Atot, int lvl_off, int G, float gscale, float wx, float wy, float ww, float wh, float beta,
+                          float scale_clamp, void* stream);
 int u2_box_reg_l1(const void* pred, const float* prop, const float* gtb, const void* labels, void* dpred, float* loss,
                   int R, int LP, int bg_label, float wx, float wy, float ww, float wh, float gscale, void* stream);
 /* FastRCNNOutputLayers.sigmoid_cross_entropy_loss (roi_heads/fast_rcnn.py:386-422) in the layout of u2_softmax_ce: logits bf16
@@ -417,6 +429,15 @@ int u2_sigmoid_ce(const void* logits, const void* labels, const float* class_wei
 int u2_box_reg_loss(int kind, const void* pred, const float* prop, const float* gtb, const void* labels, void* dpred,
                     float* loss, int R, int LP, int bg_label, float wx, float wy, float ww, float wh, float beta,
                     float scale_clamp, float gscale, void* stream);
+
+/* u2_box_reg_loss for class-specific regression (cls_agnostic_bbox_reg = False): pred bf16 [R][LP] with 4 * bg_label valid
+ * columns; a foreground row of label c reads columns 4c .. 4c + 3 and dpred receives its gradient there.  Every other element of
+ * dpred - the other classes' columns, the pad columns, background rows - is written as exactly 0 by the same launch, whatever
+ * it held.  All four kinds; SMOOTH_L1 takes any beta >= 0 (0 = plain L1, the gradient bits of u2_box_reg_l1).  An unknown
+ * kind, beta < 0 or LP < 4 * bg_label returns -1; R == 0 launches nothing. */
+int u2_box_reg_loss_cls(int kind, const void* pred, const float* prop, const float* gtb, const void* labels, void* dpred,
+                        float* loss, int R, int LP, int bg_label, float wx, float wy, float ww, float wh, float beta,
+                        float scale_clamp, float gscale, void* stream);
 
 /* ---- ROI bookkeeping (roi.hip) -----------------------------------------------------------------
  * layers/roi_align.py:49-65 via modeling/poolers.py:206-263; structures/masks.py:191-218; modeling/poolers.py:23-59;
@@ -467,6 +488,11 @@ int u2_iou_match(const float* boxes, int per_image_boxes, const float* gt, const
                  int allow_low_quality, void* stream);
 int u2_apply_deltas(const float* src, const float* deltas, const int* img, const float* sizes, float* out, int n,
                     float wx, float wy, float ww, float wh, float clamp, int do_clip, void* stream);
+/* The class-specific decode (fast_rcnn.py:494-524): deltas [R][LP] (bf16 if deltas_bf16 else fp32) with 4 K valid columns, src
+ * fp32 [R][4] -> out fp32 [R][4 K], class c of row r = u2_apply_deltas (no clip) of columns 4c .. 4c + 3 against src[r].  One
+ * thread per (row, class); the source boxes are not repeated.  LP < 4 K returns -1. */
+int u2_apply_deltas_cls(const float* src, const void* deltas, int deltas_bf16, float* out, int R, int K, int LP, float wx,
+                        float wy, float ww, float wh, float clamp, void* stream);
 long long u2_nms_workspace_bytes(int B, int n);
 int u2_batched_nms(const float* boxes, const int* group, const int* cnt, void* workspace, int* keep, int* nkeep, int B,
                    int n, float thr, int max_keep, void* stream);

@@ -6,9 +6,13 @@
 //   mask_rcnn_loss: gt-class channel gather + BCE-with-logits(mean)          roi_heads/mask_head.py:33-112
 //     (fused with the 1x1 predictor conv of mask_head.py:258 so only the gt-class channel is computed)
 //   RPN.losses: BCE-with-logits(sum) + L1 over positives, / (batch_per_image * N)   proposal_generator/rpn.py:366-429
+//     (and with MODEL.RPN.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA / BBOX_REG_WEIGHTS: smooth-L1, GIoU, DIoU, CIoU)
+//   _dense_box_regression_loss, class agnostic and class specific                    modeling/box_regression.py:310-369
+//     (the per-row arithmetic of the three kernels that evaluate it: box_loss_rows.h)
 //   Box2BoxTransform.get_deltas                                               modeling/box_regression.py:43-76
 #include "common.h"
 #include "u2seg_hip.h"
+#include "box_loss_rows.h"
 
 namespace {
 
@@ -521,24 +525,43 @@ __global__ __launch_bounds__(256) void count_labels_i8_kernel(const int8_t* __re
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Box coding helpers (fp32, same operation order as box_regression.py:43-116)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void get_deltas(const float* s, const float* t, float wx, float wy, float ww, float wh, float* d) {
-  const float sw = s[2] - s[0], sh = s[3] - s[1];
-  const float scx = s[0] + 0.5f * sw, scy = s[1] + 0.5f * sh;
-  const float tw = t[2] - t[0], th = t[3] - t[1];
-  const float tcx = t[0] + 0.5f * tw, tcy = t[1] + 0.5f * th;
-  d[0] = wx * (tcx - scx) / sw;
-  d[1] = wy * (tcy - scy) / sh;
-  d[2] = ww * logf(tw / sw);
-  d[3] = wh * logf(th / sh);
-}
-
 // RPN losses for one FPN level.  obj: [B][HW][LPo] (A valid cols), dlt: [B][HW][LPd] (4A valid cols),
 // labels int8 [B][Atot] (-1 ignore / 0 / 1, already subsampled), match int32 [B][Atot], gt fp32 [B][G][4],
 // anchors fp32 [HW*A][4] of this level.  Writes dobj/ddlt (bf16, same layouts, pads zero) and adds to loss[0:2].
 // FUSED3: one 32-wide map holds both predictions of A = 3 anchors (columns 0-2 objectness, 3-14 deltas) and takes one gradient row
+
+// objectness of one anchor with label t in {0, 1}: BCE-with-logits added to lc, the logit gradient returned
+__device__ __forceinline__ bf16_t rpn_objectness(float z, float t, float gscale, float& lc) {
+  lc += fmaxf(z, 0.f) - z * t + log1pf(__expf(-fabsf(z)));
+  return f2bf((1.f / (1.f + __expf(-z)) - t) * gscale);
+}
+
+// one position's gradient rows: go_l[8] objectness, gd_l[16] deltas, pads zero; every column of the maps' rows is written
+template <bool FUSED3>
+__device__ __forceinline__ void rpn_store_grads(bf16_t* __restrict__ dobj, bf16_t* __restrict__ ddlt, size_t i, int LPo, int LPd,
+                                                const bf16_t* go_l, const bf16_t* gd_l) {
+  uint4* go = reinterpret_cast<uint4*>(dobj + i * LPo);
+  const uint4 zero4 = make_uint4(0, 0, 0, 0);
+  if (FUSED3) {
+    bf16_t row[16];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) row[c] = go_l[c];
+#pragma unroll
+    for (int c = 0; c < 12; ++c) row[3 + c] = gd_l[c];
+    row[15] = 0;
+    go[0] = *reinterpret_cast<const uint4*>(row);
+    go[1] = *reinterpret_cast<const uint4*>(row + 8);
+    for (int c = 2; c < LPo / 8; ++c) go[c] = zero4;
+    return;
+  }
+  uint4* gd = reinterpret_cast<uint4*>(ddlt + i * LPd);
+  go[0] = *reinterpret_cast<const uint4*>(go_l);
+  for (int c = 1; c < LPo / 8; ++c) go[c] = zero4;
+  gd[0] = *reinterpret_cast<const uint4*>(gd_l);
+  gd[1] = *reinterpret_cast<const uint4*>(gd_l + 8);
+  for (int c = 2; c < LPd / 8; ++c) gd[c] = zero4;
+}
+
 template <bool FUSED3>
 __global__ __launch_bounds__(256) void rpn_loss_level_kernel(const bf16_t* __restrict__ obj, const bf16_t* __restrict__ dlt,
                                                              const int8_t* __restrict__ labels, const int* __restrict__ match,
@@ -563,10 +586,7 @@ __global__ __launch_bounds__(256) void rpn_loss_level_kernel(const bf16_t* __res
       const int aidx = pix * A + a;
       const int lab = labels[(size_t)b * Atot + lvl_off + aidx];
       if (lab < 0) continue;
-      const float z = bf2f(obj[i * LPo + a]);
-      const float t = (float)lab;
-      lc += fmaxf(z, 0.f) - z * t + log1pf(__expf(-fabsf(z)));
-      go_l[a] = f2bf((1.f / (1.f + __expf(-z)) - t) * gscale);
+      go_l[a] = rpn_objectness(bf2f(obj[i * LPo + a]), (float)lab, gscale, lc);
       if (lab == 1) {
         const int g = match[(size_t)b * Atot + lvl_off + aidx];
         float d[4];
@@ -580,26 +600,54 @@ __global__ __launch_bounds__(256) void rpn_loss_level_kernel(const bf16_t* __res
         }
       }
     }
-    uint4* go = reinterpret_cast<uint4*>(dobj + i * LPo);
-    const uint4 zero4 = make_uint4(0, 0, 0, 0);
-    if (FUSED3) {
-      bf16_t row[16];
+    rpn_store_grads<FUSED3>(dobj, ddlt, i, LPo, LPd, go_l, gd_l);
+  }
+  const float s0 = block_sum_256(lc, red);
+  const float s1 = block_sum_256(ll, red);
+  if (threadIdx.x == 0) { atomicAdd(loss + 0, s0); atomicAdd(loss + 1, s1); }
+}
+
+// The same level with the localisation loss options (rpn.py:366-429 over box_regression.py:310-369): the positives' rows go
+// through box_loss_row (box_loss_rows.h) with the anchor as the source box - smooth-L1 with any beta >= 0 on
+// delta - get_deltas(anchor, gt; weights), or GIoU / DIoU / CIoU on apply_deltas(delta, anchor; weights, scale_clamp) with the
+// gradient taken back through the decode.  Objectness, layouts and stores are rpn_loss_level_kernel's.
+template <bool FUSED3, int KIND>
+__global__ __launch_bounds__(256) void rpn_loss_level_opt_kernel(const bf16_t* __restrict__ obj, const bf16_t* __restrict__ dlt,
+                                                                 const int8_t* __restrict__ labels, const int* __restrict__ match,
+                                                                 const float* __restrict__ gt, const float* __restrict__ anchors,
+                                                                 bf16_t* __restrict__ dobj, bf16_t* __restrict__ ddlt,
+                                                                 float* __restrict__ loss, int B, int HW, int A, int LPo, int LPd,
+                                                                 int Atot, int lvl_off, int G, float gscale, float wx, float wy,
+                                                                 float ww, float wh, float beta, float scale_clamp) {
+  __shared__ float red[4];
+  float lc = 0.f, ll = 0.f;
+  const size_t total = (size_t)B * HW;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int b = (int)(i / HW);
+    const int pix = (int)(i - (size_t)b * HW);
+    bf16_t go_l[8], gd_l[16];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) row[c] = go_l[c];
+    for (int c = 0; c < 8; ++c) go_l[c] = 0;
 #pragma unroll
-      for (int c = 0; c < 12; ++c) row[3 + c] = gd_l[c];
-      row[15] = 0;
-      go[0] = *reinterpret_cast<const uint4*>(row);
-      go[1] = *reinterpret_cast<const uint4*>(row + 8);
-      for (int c = 2; c < LPo / 8; ++c) go[c] = zero4;
-      continue;
+    for (int c = 0; c < 16; ++c) gd_l[c] = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      if (a >= A) break;
+      const int aidx = pix * A + a;
+      const int lab = labels[(size_t)b * Atot + lvl_off + aidx];
+      if (lab < 0) continue;
+      go_l[a] = rpn_objectness(bf2f(obj[i * LPo + a]), (float)lab, gscale, lc);
+      if (lab == 1) {
+        const int g = match[(size_t)b * Atot + lvl_off + aidx];
+        float d[4], gd[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) d[q] = bf2f(dlt[i * LPd + a * 4 + q]);
+        box_loss_row<KIND>(d, anchors + (size_t)aidx * 4, gt + ((size_t)b * G + g) * 4, wx, wy, ww, wh, beta, scale_clamp, ll, gd);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) gd_l[a * 4 + q] = f2bf(gd[q] * gscale);
+      }
     }
-    uint4* gd = reinterpret_cast<uint4*>(ddlt + i * LPd);
-    go[0] = *reinterpret_cast<const uint4*>(go_l);
-    for (int c = 1; c < LPo / 8; ++c) go[c] = zero4;
-    gd[0] = *reinterpret_cast<const uint4*>(gd_l);
-    gd[1] = *reinterpret_cast<const uint4*>(gd_l + 8);
-    for (int c = 2; c < LPd / 8; ++c) gd[c] = zero4;
+    rpn_store_grads<FUSED3>(dobj, ddlt, i, LPo, LPd, go_l, gd_l);
   }
   const float s0 = block_sum_256(lc, red);
   const float s1 = block_sum_256(ll, red);
@@ -731,72 +779,9 @@ __global__ __launch_bounds__(256) void sigmoid_ce_kernel(const bf16_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// The box heads' regression losses other than plain L1 (box_regression.py:310-369), class agnostic, one thread per row.
-// SMOOTH_L1 (beta > 0): on pred - get_deltas(prop, gt).  GIOU / DIOU / CIOU: the box is decoded as apply_deltas does
-// (box_regression.py:78-116), the loss of layers/losses.py:5-133 is evaluated against gt (GIoU: 1 - I/(U + eps) + (C - U)/(C + eps))
-// and its gradient is taken back through the decode by hand: d/dx1 .. d/dy2 of the loss, then centre / size, then the deltas.
-// torch's max / min hand half the gradient to each side of a tie; tie() does the same.  A clamped dw / dh passes nothing.
+// The box heads' regression losses other than plain L1 (box_regression.py:310-369), class agnostic, one thread per row; the
+// row's arithmetic is box_loss_row (box_loss_rows.h).
 // ------------------------------------------------------------------------------------------------
-constexpr float BOXLOSS_EPS = 1e-7f;
-
-__device__ __forceinline__ float tie(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }  // d max(a, b) / da
-
-template <int KIND>
-__device__ __forceinline__ float iou_family_loss(const float* b, const float* g, float* gb) {
-  const float x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
-  const float x1g = g[0], y1g = g[1], x2g = g[2], y2g = g[3];
-  // intersection, zero unless both overlaps are strictly positive
-  const float iw = fminf(x2, x2g) - fmaxf(x1, x1g), ih = fminf(y2, y2g) - fmaxf(y1, y1g);
-  const bool hit = ih > 0.f && iw > 0.f;
-  const float I = hit ? iw * ih : 0.f;
-  const float m = hit ? 1.f : 0.f;
-  const float dI[4] = {-ih * tie(x1, x1g) * m, -iw * tie(y1, y1g) * m, ih * tie(x2g, x2) * m, iw * tie(y2g, y2) * m};
-  const float bw = x2 - x1, bh = y2 - y1;
-  const float dA[4] = {-bh, -bw, bh, bw};
-  // smallest enclosing box
-  const float cw = fmaxf(x2, x2g) - fminf(x1, x1g), ch = fmaxf(y2, y2g) - fminf(y1, y1g);
-  const float dcw[4] = {-tie(x1g, x1), 0.f, tie(x2, x2g), 0.f};
-  const float dch[4] = {0.f, -tie(y1g, y1), 0.f, tie(y2, y2g)};
-  if constexpr (KIND == U2_BOXLOSS_GIOU) {
-    const float U = bw * bh + (x2g - x1g) * (y2g - y1g) - I;
-    const float C = cw * ch;
-    const float iou = I / (U + BOXLOSS_EPS), mis = (C - U) / (C + BOXLOSS_EPS);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float dU = dA[q] - dI[q], dC = dcw[q] * ch + cw * dch[q];
-      gb[q] = -(dI[q] - iou * dU) / (U + BOXLOSS_EPS) + ((dC - dU) - mis * dC) / (C + BOXLOSS_EPS);
-    }
-    return 1.f - iou + mis;
-  } else {
-    const float un = bw * bh + (x2g - x1g) * (y2g - y1g) - I + BOXLOSS_EPS;
-    const float iou = I / un;
-    const float diag = cw * cw + ch * ch + BOXLOSS_EPS;
-    const float ex = (x2 + x1) / 2.f - (x1g + x2g) / 2.f, ey = (y2 + y1) / 2.f - (y1g + y2g) / 2.f;
-    const float dist = ex * ex + ey * ey;
-    const float term = dist / diag;
-    const float ddist[4] = {ex, ey, ex, ey};
-    float av = 0.f, dvw = 0.f, dvh = 0.f;   // CIoU: alpha v and alpha dv/d(width, height) of the decoded box
-    if constexpr (KIND == U2_BOXLOSS_CIOU) {
-      const float k = 4.f / (3.14159265358979323846f * 3.14159265358979323846f);
-      const float ratio = bw / bh;
-      const float da = atanf((x2g - x1g) / (y2g - y1g)) - atanf(ratio);
-      const float v = k * da * da;
-      const float alpha = v / (1.f - iou + v + BOXLOSS_EPS);   // a constant of the gradient (no_grad in the reference)
-      const float dvdr = -2.f * k * da / (1.f + ratio * ratio);
-      av = alpha * v;
-      dvw = alpha * dvdr / bh;
-      dvh = -alpha * dvdr * ratio / bh;
-    }
-    const float dshape[4] = {-dvw, -dvh, dvw, dvh};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float dU = dA[q] - dI[q], ddiag = 2.f * (cw * dcw[q] + ch * dch[q]);
-      gb[q] = -(dI[q] - iou * dU) / un + (ddist[q] - term * ddiag) / diag + dshape[q];
-    }
-    return 1.f - iou + term + av;
-  }
-}
-
 template <int KIND>
 __global__ __launch_bounds__(256) void box_reg_loss_kernel(const bf16_t* __restrict__ pred, const float* __restrict__ prop,
                                                            const float* __restrict__ gtb, const long long* __restrict__ labels,
@@ -809,38 +794,10 @@ __global__ __launch_bounds__(256) void box_reg_loss_kernel(const bf16_t* __restr
     float gd[4] = {0.f, 0.f, 0.f, 0.f};
     const long long lab = labels[r];
     if (lab >= 0 && lab < bg_label) {
-      const float* p = prop + (size_t)r * 4;
-      const float* g = gtb + (size_t)r * 4;
       float d[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) d[q] = bf2f(pred[(size_t)r * LP + q]);
-      if constexpr (KIND == U2_BOXLOSS_SMOOTH_L1) {
-        float tgt[4];
-        get_deltas(p, g, wx, wy, ww, wh, tgt);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float df = d[q] - tgt[q], n = fabsf(df);
-          l += n < beta ? 0.5f * n * n / beta : n - 0.5f * beta;
-          gd[q] = n < beta ? df / beta : (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f));
-        }
-      } else {
-        const float pw = p[2] - p[0], ph = p[3] - p[1];
-        const float cx = p[0] + 0.5f * pw, cy = p[1] + 0.5f * ph;
-        const float dx = d[0] / wx, dy = d[1] / wy;
-        float dw = d[2] / ww, dh = d[3] / wh;
-        const bool open_w = dw <= scale_clamp, open_h = dh <= scale_clamp;   // clamp(max =) passes the gradient up to equality
-        dw = fminf(dw, scale_clamp);
-        dh = fminf(dh, scale_clamp);
-        const float pcx = dx * pw + cx, pcy = dy * ph + cy;
-        const float bw = expf(dw) * pw, bh = expf(dh) * ph;
-        const float b[4] = {pcx - 0.5f * bw, pcy - 0.5f * bh, pcx + 0.5f * bw, pcy + 0.5f * bh};
-        float gb[4];
-        l += iou_family_loss<KIND>(b, g, gb);
-        gd[0] = (gb[0] + gb[2]) * pw / wx;
-        gd[1] = (gb[1] + gb[3]) * ph / wy;
-        gd[2] = open_w ? 0.5f * (gb[2] - gb[0]) * bw / ww : 0.f;
-        gd[3] = open_h ? 0.5f * (gb[3] - gb[1]) * bh / wh : 0.f;
-      }
+      box_loss_row<KIND>(d, prop + (size_t)r * 4, gtb + (size_t)r * 4, wx, wy, ww, wh, beta, scale_clamp, l, gd);
     }
     bf16_t* gp = dpred + (size_t)r * LP;
     const bf16_t head[8] = {f2bf(gd[0] * gscale), f2bf(gd[1] * gscale), f2bf(gd[2] * gscale), f2bf(gd[3] * gscale), 0, 0, 0, 0};
@@ -856,6 +813,82 @@ __global__ __launch_bounds__(256) void box_reg_loss_kernel(const bf16_t* __restr
   }
   const float s = block_sum_256(l, red);
   if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same losses with class-specific regression (fast_rcnn.py:424-463 with cls_agnostic_bbox_reg = False): pred [R][LP] bf16
+// holds 4 K valid columns and a foreground row of label c reads and differentiates columns 4c .. 4c + 3 only.  Every other
+// element of dpred is written as zero here: at K = 800 a row is 6.4 KB of gradient for 8 bytes of payload, so the kernel is a
+// fill with a little arithmetic in front.  A work-group takes 256 rows at a time.  First one thread per row evaluates it as
+// box_reg_loss_kernel does (the same rows per thread, so the loss is summed in the same order) and leaves its four gradients
+// and their column in LDS; then each wave writes every fourth row of the 256 in 16-byte pieces, the piece holding the label's
+// columns patched in registers.  Wide rows are cut into gridDim.y column slices, one work-group each: every slice evaluates the
+// rows (a few hundred flops against 256 rows x 1 KB of stores), slice 0 alone keeps the loss.  SMOOTH_L1 with beta == 0 is
+// plain L1 (box_loss_row).
+// ------------------------------------------------------------------------------------------------
+template <int KIND>
+__global__ __launch_bounds__(256) void box_reg_loss_cls_kernel(const bf16_t* __restrict__ pred, const float* __restrict__ prop,
+                                                               const float* __restrict__ gtb, const long long* __restrict__ labels,
+                                                               bf16_t* __restrict__ dpred, float* __restrict__ loss, int R, int LP,
+                                                               int bg_label, float wx, float wy, float ww, float wh, float beta,
+                                                               float scale_clamp, float gscale) {
+  __shared__ float red[4];
+  __shared__ __attribute__((aligned(8))) bf16_t s_head[256][4];
+  __shared__ int s_col[256];   // first of the label's columns, negative for a row without gradient
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float l = 0.f;
+  for (int r0 = blockIdx.x * 256; r0 < R; r0 += gridDim.x * 256) {   // (uniform over the work-group: the barriers are safe)
+    const int r = r0 + threadIdx.x;
+    float gd[4] = {0.f, 0.f, 0.f, 0.f};
+    int c0 = -8;
+    if (r < R) {
+      const long long lab = labels[r];
+      if (lab >= 0 && lab < bg_label) {
+        c0 = 4 * (int)lab;   // c0 + 3 < 4 bg_label <= LP
+        float d[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) d[q] = bf2f(pred[(size_t)r * LP + c0 + q]);
+        box_loss_row<KIND>(d, prop + (size_t)r * 4, gtb + (size_t)r * 4, wx, wy, ww, wh, beta, scale_clamp, l, gd);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s_head[threadIdx.x][q] = f2bf(gd[q] * gscale);
+    s_col[threadIdx.x] = c0;
+    __syncthreads();
+    const int rows = R - r0 < 256 ? R - r0 : 256;
+    for (int j = wave; j < rows; j += 4) {
+      bf16_t* gp = dpred + (size_t)(r0 + j) * LP;
+      const int cj = s_col[j];
+      bf16_t head[4];
+      *reinterpret_cast<uint2*>(head) = *reinterpret_cast<const uint2*>(s_head[j]);
+      if ((LP & 7) == 0) {
+        uint4* gv = reinterpret_cast<uint4*>(gp);
+        const int hit = cj >> 3;                 // the piece with the label's columns (-1: none) ...
+        const bool upper = (cj >> 2) & 1;        // ... and the half of it they are
+        const int pieces = LP / 8, per = (pieces + gridDim.y - 1) / gridDim.y;   // this slice's pieces
+        const int last = min(pieces, ((int)blockIdx.y + 1) * per);
+        for (int ch = blockIdx.y * per + lane; ch < last; ch += 64) {
+          bf16_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+          if (ch == hit) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              v[q] = upper ? (bf16_t)0 : head[q];
+              v[4 + q] = upper ? head[q] : (bf16_t)0;
+            }
+          }
+          gv[ch] = *reinterpret_cast<const uint4*>(v);
+        }
+      } else {
+        for (int c = lane; c < LP; c += 64) {
+          const int q = c - cj;
+          gp[c] = q == 0 ? head[0] : (q == 1 ? head[1] : (q == 2 ? head[2] : (q == 3 ? head[3] : (bf16_t)0)));
+        }
+      }
+    }
+    __syncthreads();   // the rows are out before the next 256 overwrite the LDS
+  }
+  const float s = block_sum_256(l, red);
+  if (threadIdx.x == 0 && blockIdx.y == 0 && s != 0.f) atomicAdd(loss, s);
 }
 
 }  // namespace
@@ -968,6 +1001,42 @@ extern "C" int u2_rpn_loss_level(const void* obj, const void* dlt, const void* l
   return 0;
 }
 
+extern "C" int u2_rpn_loss_level_opt(int kind, const void* obj, const void* dlt, const void* labels, const int* match,
+                                     const float* gt, const float* anchors, void* dobj, void* ddlt, float* loss, int B, int HW,
+                                     int A, int LPo, int LPd, int Atot, int lvl_off, int G, float gscale, float wx, float wy,
+                                     float ww, float wh, float beta, float scale_clamp, void* stream) {
+  if (kind < U2_BOXLOSS_SMOOTH_L1 || kind > U2_BOXLOSS_CIOU || !(beta >= 0.f)) return -1;
+  if (!(wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f)) return -1;
+  if (A > 4 || (LPo & 7)) return -1;
+  const bool fused = dlt == nullptr;  // the layouts of u2_rpn_loss_level
+  if (fused) {
+    if (ddlt || A != 3 || LPo < 16) return -1;
+    dlt = (const bf16_t*)obj + A;
+    LPd = LPo;
+  } else if (!ddlt || LPd < 16 || (LPd & 7)) {
+    return -1;
+  }
+  if (B <= 0 || HW <= 0) return 0;
+  size_t g = ((size_t)B * HW + 255) / 256;
+  if (g > 2048) g = 2048;
+#define U2_RPNLOSS_LAUNCH(FUSED, KIND)                                                                                         \
+  hipLaunchKernelGGL((rpn_loss_level_opt_kernel<FUSED, KIND>), dim3((int)g), dim3(256), 0, (hipStream_t)stream,               \
+                     (const bf16_t*)obj, (const bf16_t*)dlt, (const int8_t*)labels, match, gt, anchors, (bf16_t*)dobj,         \
+                     (bf16_t*)ddlt, loss, B, HW, A, LPo, LPd, Atot, lvl_off, G, gscale, wx, wy, ww, wh, beta, scale_clamp)
+#define U2_RPNLOSS_KIND(KIND)                                                                                                  \
+  if (fused) U2_RPNLOSS_LAUNCH(true, KIND); else U2_RPNLOSS_LAUNCH(false, KIND)
+  switch (kind) {
+    case U2_BOXLOSS_SMOOTH_L1: U2_RPNLOSS_KIND(U2_BOXLOSS_SMOOTH_L1); break;
+    case U2_BOXLOSS_GIOU: U2_RPNLOSS_KIND(U2_BOXLOSS_GIOU); break;
+    case U2_BOXLOSS_DIOU: U2_RPNLOSS_KIND(U2_BOXLOSS_DIOU); break;
+    default: U2_RPNLOSS_KIND(U2_BOXLOSS_CIOU); break;
+  }
+#undef U2_RPNLOSS_KIND
+#undef U2_RPNLOSS_LAUNCH
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int u2_box_reg_l1(const void* pred, const float* prop, const float* gtb, const void* labels, void* dpred,
                              float* loss, int R, int LP, int bg_label, float wx, float wy, float ww, float wh, float gscale,
                              void* stream) {
@@ -1006,6 +1075,30 @@ extern "C" int u2_box_reg_loss(int kind, const void* pred, const float* prop, co
   if (g > 1024) g = 1024;
 #define U2_BOXLOSS_LAUNCH(KIND)                                                                                              \
   hipLaunchKernelGGL(box_reg_loss_kernel<KIND>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, prop, gtb, \
+                     (const long long*)labels, (bf16_t*)dpred, loss, R, LP, bg_label, wx, wy, ww, wh, beta, scale_clamp, gscale)
+  switch (kind) {
+    case U2_BOXLOSS_SMOOTH_L1: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_SMOOTH_L1); break;
+    case U2_BOXLOSS_GIOU: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_GIOU); break;
+    case U2_BOXLOSS_DIOU: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_DIOU); break;
+    default: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_CIOU); break;
+  }
+#undef U2_BOXLOSS_LAUNCH
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int u2_box_reg_loss_cls(int kind, const void* pred, const float* prop, const float* gtb, const void* labels,
+                                   void* dpred, float* loss, int R, int LP, int bg_label, float wx, float wy, float ww, float wh,
+                                   float beta, float scale_clamp, float gscale, void* stream) {
+  if (kind < U2_BOXLOSS_SMOOTH_L1 || kind > U2_BOXLOSS_CIOU || !(beta >= 0.f)) return -1;
+  if (bg_label < 1 || bg_label > (1 << 24) || LP < 4 * bg_label) return -1;   // 4 K valid columns
+  if (R <= 0) return 0;
+  int g = (R + 255) / 256;   // (the geometry of u2_box_reg_loss: the loss is summed in the same order)
+  if (g > 1024) g = 1024;
+  int slices = (LP & 7) ? 1 : (LP / 8 + 63) / 64;   // one pass of a wave's 64 lanes per slice and row where 8 slices reach
+  if (slices > 8) slices = 8;
+#define U2_BOXLOSS_LAUNCH(KIND)                                                                                                  \
+  hipLaunchKernelGGL(box_reg_loss_cls_kernel<KIND>, dim3(g, slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, prop, gtb, \
                      (const long long*)labels, (bf16_t*)dpred, loss, R, LP, bg_label, wx, wy, ww, wh, beta, scale_clamp, gscale)
   switch (kind) {
     case U2_BOXLOSS_SMOOTH_L1: U2_BOXLOSS_LAUNCH(U2_BOXLOSS_SMOOTH_L1); break;

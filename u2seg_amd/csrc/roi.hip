@@ -792,14 +792,9 @@ __global__ __launch_bounds__(256) void match_label_kernel(const float* __restric
   }
 }
 
-// boxes = apply_deltas(deltas, src) then clip to (h, w) of the image `img[i]`
-__global__ void apply_deltas_kernel(const float* __restrict__ src, const float* __restrict__ deltas,
-                                    const int* __restrict__ img, const float* __restrict__ sizes, float* __restrict__ out,
-                                    int n, float wx, float wy, float ww, float wh, float clamp, int do_clip) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* s = src + (size_t)i * 4;
-  const float* d = deltas + (size_t)i * 4;
+// Box2BoxTransform.apply_deltas (box_regression.py:78-116) of one box: s = the source box, d = its four deltas
+__device__ __forceinline__ void decode_box(const float* s, const float* d, float wx, float wy, float ww, float wh, float clamp,
+                                           float& x1, float& y1, float& x2, float& y2) {
   const float w = s[2] - s[0], h = s[3] - s[1];
   const float cx = s[0] + 0.5f * w, cy = s[1] + 0.5f * h;
   const float dx = d[0] / wx, dy = d[1] / wy;
@@ -809,7 +804,17 @@ __global__ void apply_deltas_kernel(const float* __restrict__ src, const float* 
   dh = dh > clamp ? clamp : dh;
   const float pcx = dx * w + cx, pcy = dy * h + cy;
   const float pw = expf(dw) * w, ph = expf(dh) * h;
-  float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
+  x1 = pcx - 0.5f * pw; y1 = pcy - 0.5f * ph; x2 = pcx + 0.5f * pw; y2 = pcy + 0.5f * ph;
+}
+
+// boxes = apply_deltas(deltas, src) then clip to (h, w) of the image `img[i]`
+__global__ void apply_deltas_kernel(const float* __restrict__ src, const float* __restrict__ deltas,
+                                    const int* __restrict__ img, const float* __restrict__ sizes, float* __restrict__ out,
+                                    int n, float wx, float wy, float ww, float wh, float clamp, int do_clip) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float x1, y1, x2, y2;
+  decode_box(src + (size_t)i * 4, deltas + (size_t)i * 4, wx, wy, ww, wh, clamp, x1, y1, x2, y2);
   if (do_clip) {
     const int b = img ? img[i] : 0;
     const float H = sizes[b * 2 + 0], W = sizes[b * 2 + 1];
@@ -818,6 +823,28 @@ __global__ void apply_deltas_kernel(const float* __restrict__ src, const float* 
   }
   float* o = out + (size_t)i * 4;
   o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
+}
+
+// Class-specific decode (fast_rcnn.py:494-524 with 4 K deltas per row): one thread per (row, class) reads its four deltas from
+// the head's output as it lies ([R][LP], bf16 or fp32) and decodes them against the row's ONE source box - the proposals are
+// not repeated K times.  out fp32 [R][4 K], 16 bytes per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void apply_deltas_cls_kernel(const float* __restrict__ src, const T* __restrict__ deltas,
+                                                               float* __restrict__ out, long long n, int K, int LP, float wx,
+                                                               float wy, float ww, float wh, float clamp) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const long long r = i / K;
+  const int c = (int)(i - r * K);
+  const T* dp = deltas + (size_t)r * LP + 4 * c;
+  float d[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if constexpr (sizeof(T) == 2) d[q] = bf2f(dp[q]); else d[q] = dp[q];
+  }
+  float4 o;
+  decode_box(src + (size_t)r * 4, d, wx, wy, ww, wh, clamp, o.x, o.y, o.z, o.w);
+  reinterpret_cast<float4*>(out)[i] = o;
 }
 
 // ---- RPN proposal decoding, all levels in one launch (round 5) ---------------------------------------------------------------
@@ -1095,6 +1122,23 @@ extern "C" int u2_apply_deltas(const float* src, const float* deltas, const int*
   if (n <= 0) return 0;
   hipLaunchKernelGGL(apply_deltas_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, deltas, img, sizes,
                      out, n, wx, wy, ww, wh, clamp, do_clip);
+  U2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int u2_apply_deltas_cls(const float* src, const void* deltas, int deltas_bf16, float* out, int R, int K, int LP,
+                                   float wx, float wy, float ww, float wh, float clamp, void* stream) {
+  if (K < 1 || LP < 4 * K) return -1;
+  if (R <= 0) return 0;
+  const long long n = (long long)R * K;
+  if ((n + 255) / 256 > 0x7fffffffLL) return -1;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (deltas_bf16)
+    hipLaunchKernelGGL(apply_deltas_cls_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, (const bf16_t*)deltas, out, n,
+                       K, LP, wx, wy, ww, wh, clamp);
+  else
+    hipLaunchKernelGGL(apply_deltas_cls_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, (const float*)deltas, out, n,
+                       K, LP, wx, wy, ww, wh, clamp);
   U2_CHECK_LAUNCH();
   return 0;
 }

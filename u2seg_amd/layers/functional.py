@@ -24,9 +24,9 @@ from torch.autograd import Function
 
 from .. import _hip
 from . import deferred, streams
-from .losses import (BOX_REG_LOSS_KINDS, box_reg_l1_loss, box_reg_loss, count_labels_i8, mask_predict_bce_loss,  # noqa: F401
+from .losses import (BOX_REG_LOSS_KINDS, box_reg_l1_loss, box_reg_loss, box_reg_loss_cls, count_labels_i8, mask_predict_bce_loss,  # noqa: F401
                      mask_predict_prob, rpn_losses, sem_seg_loss, sigmoid_cross_entropy, softmax_cross_entropy)
-from .select import (_TOPK_MAX_K, _topk_rows_sorted, _topk_segments, apply_deltas, assign_levels, batched_nms,  # noqa: F401
+from .select import (_TOPK_MAX_K, _topk_rows_sorted, _topk_segments, apply_deltas, apply_deltas_cls, assign_levels, batched_nms,  # noqa: F401
                      iou_match, mask_crop, rpn_decode, sem_seg_upsample, topk_rows, topk_rows_multi)
 from .streams import (_NO_STREAMK, _conv_variant, _run_wgrad, _world, aux_stream, clear_branch_pieces,  # noqa: F401
                       flush_branch_pieces, issue_branch_piece, join_all_streams, join_aux_stream, join_wgrad_stream,

@@ -130,6 +130,24 @@ def box_reg_loss(kind, pred, proposals, gt_boxes, labels, bg_label, weights, nor
     return _ScaledGradLossFn.apply(pred, launch, normalizer)
 
 
+def box_reg_loss_cls(kind, pred, proposals, gt_boxes, labels, bg_label, weights, normalizer, beta=0.0,
+                     scale_clamp=math.log(1000.0 / 16)):
+    """box_reg_l1_loss / box_reg_loss for class-specific regression (cls_agnostic_bbox_reg=False): pred [R, LP] holds
+    4 * bg_label valid columns and a foreground row of label c is scored on columns 4c .. 4c + 3 (fast_rcnn.py:445-450).  All
+    four kinds; smooth_l1 takes any beta >= 0.  The kernel writes the whole [R, LP] gradient, zeros included."""
+    if kind not in BOX_REG_LOSS_KINDS:
+        raise ValueError("Invalid box regression loss type '%s' (one of %s)" % (kind, ", ".join(BOX_REG_LOSS_KINDS)))
+    r, lp = pred.shape
+    normalizer, beta, scale_clamp = float(normalizer), float(beta), float(scale_clamp)
+
+    def launch(x, d, loss):
+        _hip.call("u2_box_reg_loss_cls", BOX_REG_LOSS_KINDS[kind], x.contiguous(), proposals.contiguous(), gt_boxes.contiguous(),
+                  labels.contiguous(), d, loss, r, lp, bg_label, weights[0], weights[1], weights[2], weights[3], beta,
+                  scale_clamp, 1.0 / normalizer)
+
+    return _ScaledGradLossFn.apply(pred, launch, normalizer)
+
+
 class _MaskPredictBCEFn(Function):
     """1x1 predictor restricted to the gt-class channel + BCE-with-logits(mean)
     (roi_heads/mask_head.py:258 + :33-112)."""
@@ -198,11 +216,13 @@ def mask_predict_prob(x, weight, bias, classes, phased=False):
 
 
 class _RPNLossFn(Function):
-    """RPN objectness BCE(sum) + localisation L1(sum) over all levels, both / normalizer
-    (proposal_generator/rpn.py:366-429).  `fused`: each level is ONE map holding objectness (columns 0-2) and deltas (3-14)."""
+    """RPN objectness BCE(sum) + localisation loss(sum) over all levels, both / normalizer
+    (proposal_generator/rpn.py:366-429).  `fused`: each level is ONE map holding objectness (columns 0-2) and deltas (3-14).
+    `options`: None = L1 with unit weights (u2_rpn_loss_level), else (kind code, beta, weights, scale_clamp) for
+    u2_rpn_loss_level_opt."""
 
     @staticmethod
-    def forward(ctx, labels, match, gt_boxes, anchors_per_level, num_anchors, normalizer, fused, *obj_and_deltas):
+    def forward(ctx, labels, match, gt_boxes, anchors_per_level, num_anchors, normalizer, fused, options, *obj_and_deltas):
         nl = len(anchors_per_level)
         objs, dlts = obj_and_deltas[:nl], obj_and_deltas[nl:]
         b, atot = labels.shape
@@ -218,8 +238,13 @@ class _RPNLossFn(Function):
             else:
                 d = dlts[lvl]
                 go, gd = torch.empty_like(o), torch.empty_like(d)
-            _hip.call("u2_rpn_loss_level", o, d, labels, match, gt_boxes, anchors_per_level[lvl], go, gd, loss, b, hw,
-                      num_anchors, o.shape[3], d.shape[3] if d is not None else 0, atot, off, g, 1.0 / normalizer)
+            args = (o, d, labels, match, gt_boxes, anchors_per_level[lvl], go, gd, loss, b, hw, num_anchors, o.shape[3],
+                    d.shape[3] if d is not None else 0, atot, off, g, 1.0 / normalizer)
+            if options is None:
+                _hip.call("u2_rpn_loss_level", *args)
+            else:
+                kind, beta, weights, scale_clamp = options
+                _hip.call("u2_rpn_loss_level_opt", kind, *args, weights[0], weights[1], weights[2], weights[3], beta, scale_clamp)
             grads.append((go, gd))
             off += hw * num_anchors
         assert off == atot
@@ -237,15 +262,28 @@ class _RPNLossFn(Function):
             scale[:a] = g_cls
             scale[a : 5 * a] = g_loc
             scale = scale.to(go0.dtype)
-            return (None, None, None, None, None, None, None, *[go * scale for go, _ in ctx.grads])
+            return (None, None, None, None, None, None, None, None, *[go * scale for go, _ in ctx.grads])
         gos = [go * g_cls for go, _ in ctx.grads]   # 0-dim fp32 factors: the products keep the maps' dtype
         gds = [gd * g_loc for _, gd in ctx.grads]
-        return (None, None, None, None, None, None, None, *gos, *gds)
+        return (None, None, None, None, None, None, None, None, *gos, *gds)
 
 
-def rpn_losses(labels, match, gt_boxes, anchors_per_level, num_anchors, normalizer, objs, deltas):
+def rpn_losses(labels, match, gt_boxes, anchors_per_level, num_anchors, normalizer, objs, deltas, box_reg_loss_type="smooth_l1",
+               smooth_l1_beta=0.0, weights=(1.0, 1.0, 1.0, 1.0), scale_clamp=math.log(1000.0 / 16)):
     """objs / deltas: per level [B, H, W, LP] maps - or, when the head ran both predictors as one conv (the maps carry
-    `_u2_rpn_fused`), the fused maps in `objs` (deltas are then views of them and are not used)."""
+    `_u2_rpn_fused`), the fused maps in `objs` (deltas are then views of them and are not used).
+    The localisation loss: box_reg_loss_type smooth_l1 (beta >= 0), giou, diou or ciou with the anchors' Box2BoxTransform
+    `weights`; smooth_l1 with beta 0 and unit weights is the launch it has always been (u2_rpn_loss_level)."""
+    if box_reg_loss_type not in BOX_REG_LOSS_KINDS:
+        raise ValueError("Invalid dense box regression loss type '%s' (one of %s)" % (box_reg_loss_type, ", ".join(BOX_REG_LOSS_KINDS)))
+    weights = tuple(float(w) for w in weights)
+    beta = float(smooth_l1_beta)
+    if len(weights) != 4 or min(weights) <= 0 or beta < 0:
+        raise ValueError("rpn_losses: four positive weights and beta >= 0 expected, got %r, %r" % (weights, beta))
+    options = None
+    if (box_reg_loss_type, beta, weights) != ("smooth_l1", 0.0, (1.0, 1.0, 1.0, 1.0)):
+        options = (BOX_REG_LOSS_KINDS[box_reg_loss_type], beta, weights, float(scale_clamp))
     if all(getattr(o, "_u2_rpn_fused", False) for o in objs):
-        return _RPNLossFn.apply(labels, match, gt_boxes, anchors_per_level, num_anchors, float(normalizer), True, *objs)
-    return _RPNLossFn.apply(labels, match, gt_boxes, anchors_per_level, num_anchors, float(normalizer), False, *objs, *deltas)
+        return _RPNLossFn.apply(labels, match, gt_boxes, anchors_per_level, num_anchors, float(normalizer), True, options, *objs)
+    return _RPNLossFn.apply(labels, match, gt_boxes, anchors_per_level, num_anchors, float(normalizer), False, options, *objs,
+                            *deltas)

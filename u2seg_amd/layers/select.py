@@ -188,6 +188,17 @@ def apply_deltas(src, deltas, weights, img_idx=None, sizes=None, clamp=math.log(
     return out
 
 
+def apply_deltas_cls(src, deltas, num_classes, weights, clamp=math.log(1000.0 / 16)):
+    """Class-specific decode: deltas [R, LP] (bf16 or fp32, 4 * num_classes valid columns, read where they lie) against
+    src fp32 [R, 4] -> fp32 [R, 4 * num_classes]; no R x K x 4 copy of the source boxes is formed (u2_apply_deltas_cls)."""
+    r, lp = deltas.shape
+    assert deltas.dtype in (torch.bfloat16, torch.float32) and src.shape == (r, 4) and src.dtype == torch.float32
+    out = torch.empty((r, 4 * num_classes), dtype=torch.float32, device=src.device)
+    _hip.call("u2_apply_deltas_cls", src.contiguous(), deltas.contiguous(), int(deltas.dtype == torch.bfloat16), out, r,
+              num_classes, lp, weights[0], weights[1], weights[2], weights[3], float(clamp))
+    return out
+
+
 class _RpnLevel(ctypes.Structure):
     """U2RpnLevel of include/u2seg_hip.h."""
     _fields_ = ([(f, ctypes.c_void_p) for f in ("deltas", "anchors", "idx", "scores")]

@@ -1,11 +1,14 @@
 """The box heads' loss options written out in plain torch: fp32 ops under autograd, on any device.  These are the definitions
-the HIP kernels of csrc/losses.hip (u2_sigmoid_ce, u2_box_reg_loss) are measured against, as impl="host" is for the
-test-time augmentation.
+the HIP kernels of csrc/losses.hip (u2_sigmoid_ce, u2_box_reg_loss, u2_box_reg_loss_cls, u2_rpn_loss_level_opt) are measured
+against, as impl="host" is for the test-time augmentation.
 
   sigmoid_cross_entropy    roi_heads/fast_rcnn.py:386-422
   fed_loss_classes_mask    roi_heads/fast_rcnn.py:356-382, 414-416
   box_reg_loss             roi_heads/fast_rcnn.py:424-463 over modeling/box_regression.py:310-369, layers/losses.py:5-133 and
-                           Box2BoxTransform (box_regression.py:43-116)
+                           Box2BoxTransform (box_regression.py:43-116); class specific with cls_agnostic=False
+  rpn_box_reg_loss         proposal_generator/rpn.py:405-413 over box_regression.py:310-369 (_dense_box_regression_loss)
+  rpn_objectness_loss      proposal_generator/rpn.py:415-420
+  predict_boxes_cls        roi_heads/fast_rcnn.py:494-524 with 4 K deltas per row
 
 GIoU: the reference takes giou_loss from fvcore.  Here it is pinned as
     loss = 1 - I / (U + eps) + (C - U) / (C + eps),   eps = 1e-7,
@@ -145,18 +148,54 @@ def ciou_loss(b1, b2, eps=EPS):
 _IOU_LOSSES = {"giou": giou_loss, "diou": diou_loss, "ciou": ciou_loss}
 
 
-def box_reg_loss(kind, deltas, proposals, gt_boxes, gt_classes, num_classes, weights, beta=0.0,
-                 scale_clamp=math.log(1000.0 / 16)):
-    """The box regression loss over the foreground rows 0 <= gt_classes < K, summed (the caller divides by max(R, 1)).
-    deltas [R, >= 4] (class agnostic: the first four columns), proposals / gt_boxes fp32 [R, 4]."""
+def _box_rows_loss(kind, pred, src, gt, weights, beta, scale_clamp):
+    """The summed loss of rows of four deltas `pred` against their source boxes and ground truth (all [n, 4], fp32)."""
     if kind not in BOX_REG_LOSS_TYPES:
         raise ValueError("Invalid box regression loss type '%s' (one of %s)" % (kind, ", ".join(BOX_REG_LOSS_TYPES)))
-    fg = (gt_classes >= 0) & (gt_classes < num_classes)
-    pred = deltas[:, :4].float()[fg]
-    prop, gt = proposals.float()[fg], gt_boxes.float()[fg]
     if kind == "smooth_l1":
-        n = torch.abs(pred - get_deltas(prop, gt, weights))
+        n = torch.abs(pred - get_deltas(src, gt, weights))
         if beta < 1e-5:
             return n.sum()
         return torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta).sum()
-    return _IOU_LOSSES[kind](apply_deltas(pred, prop, weights, scale_clamp), gt).sum()
+    return _IOU_LOSSES[kind](apply_deltas(pred, src, weights, scale_clamp), gt).sum()
+
+
+def box_reg_loss(kind, deltas, proposals, gt_boxes, gt_classes, num_classes, weights, beta=0.0,
+                 scale_clamp=math.log(1000.0 / 16), cls_agnostic=True):
+    """The box regression loss over the foreground rows 0 <= gt_classes < K, summed (the caller divides by max(R, 1)).
+    deltas [R, >= 4] (class agnostic: the first four columns) or, with cls_agnostic=False, [R, >= 4 K]: a row of class c is
+    scored on columns 4c .. 4c + 3 (fast_rcnn.py:445-450).  proposals / gt_boxes fp32 [R, 4]."""
+    if kind not in BOX_REG_LOSS_TYPES:
+        raise ValueError("Invalid box regression loss type '%s' (one of %s)" % (kind, ", ".join(BOX_REG_LOSS_TYPES)))
+    fg = (gt_classes >= 0) & (gt_classes < num_classes)
+    if cls_agnostic:
+        pred = deltas[:, :4].float()[fg]
+    else:
+        cols = 4 * gt_classes[fg][:, None] + torch.arange(4, device=deltas.device)
+        pred = deltas.float()[fg].gather(1, cols)
+    return _box_rows_loss(kind, pred, proposals.float()[fg], gt_boxes.float()[fg], weights, beta, scale_clamp)
+
+
+def predict_boxes_cls(deltas, proposals, num_classes, weights, scale_clamp=math.log(1000.0 / 16)):
+    """deltas [R, >= 4 K], proposals [R, 4] -> [R, 4 K]: every class's deltas applied to the row's proposal."""
+    r, k = deltas.shape[0], num_classes
+    d = deltas[:, : 4 * k].float().reshape(r * k, 4)
+    src = proposals.float()[:, None, :].expand(r, k, 4).reshape(r * k, 4)
+    return apply_deltas(d, src, weights, scale_clamp).reshape(r, 4 * k)
+
+
+def rpn_box_reg_loss(kind, labels, match, gt_boxes, anchors, deltas, weights=(1.0, 1.0, 1.0, 1.0), beta=0.0,
+                     scale_clamp=math.log(1000.0 / 16)):
+    """The RPN's localisation loss, summed over the positives (the caller divides by batch_size_per_image * B).
+    labels [B, A] (1 = positive; 0 and -1 take no part), match [B, A] the matched ground truth's index, gt_boxes fp32
+    [B, G, 4], anchors fp32 [A, 4] (all levels concatenated), deltas [B, A, 4]."""
+    b_idx, a_idx = torch.nonzero(labels == 1, as_tuple=True)
+    pred = deltas.float()[b_idx, a_idx]
+    gt = gt_boxes.float()[b_idx, match[b_idx, a_idx].long()]
+    return _box_rows_loss(kind, pred, anchors.float()[a_idx], gt, weights, beta, scale_clamp)
+
+
+def rpn_objectness_loss(labels, logits):
+    """BCE-with-logits over the anchors with label >= 0, summed.  labels / logits [B, A]."""
+    valid = labels >= 0
+    return TF.binary_cross_entropy_with_logits(logits.float()[valid], labels[valid].float(), reduction="sum")

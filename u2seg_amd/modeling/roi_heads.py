@@ -117,7 +117,7 @@ def build_box_head(cfg, input_shape):
 
 
 class FastRCNNOutputLayers(nn.Module):
-    """cls_score (K+1) and bbox_pred (4 when class agnostic) + losses / inference (fast_rcnn.py:174-569)."""
+    """cls_score (K+1) and bbox_pred (4 when class agnostic, else 4 K) + losses / inference (fast_rcnn.py:174-569)."""
 
     @configurable
     def __init__(self, input_shape, *, box2box_weights, num_classes, test_score_thresh=0.0, test_nms_thresh=0.5,
@@ -130,8 +130,8 @@ class FastRCNNOutputLayers(nn.Module):
         self.num_classes = num_classes
         input_size = input_shape.channels * (input_shape.width or 1) * (input_shape.height or 1)
         self.cls_score = Linear(input_size, num_classes + 1)
+        self.cls_agnostic_bbox_reg = bool(cls_agnostic_bbox_reg)
         num_bbox_reg_classes = 1 if cls_agnostic_bbox_reg else num_classes
-        assert cls_agnostic_bbox_reg, "the U2Seg configs use class-agnostic box regression"
         self.bbox_pred = Linear(input_size, num_bbox_reg_classes * 4)
         nn.init.normal_(self.cls_score.weight, std=0.01)
         nn.init.normal_(self.bbox_pred.weight, std=0.001)
@@ -180,7 +180,7 @@ class FastRCNNOutputLayers(nn.Module):
         }
 
     def forward(self, x):
-        """x [R, 1024] -> scores [R, 832] (K+1 valid), deltas [R, 32] (4 valid)."""
+        """x [R, 1024] -> scores [R, 832] (K+1 valid), deltas [R, 32] (4 valid) or, class specific, [R, ceil32(4 K)] (4 K valid)."""
         return self.cls_score(x), self.bbox_pred(x)
 
     def losses(self, predictions, proposals):
@@ -203,7 +203,10 @@ class FastRCNNOutputLayers(nn.Module):
             loss_cls = F.sigmoid_cross_entropy(scores, gt_classes, self.num_classes + 1, fed, _stage_counters())
         else:
             loss_cls = F.softmax_cross_entropy(scores, gt_classes, self.num_classes + 1, _stage_counters())
-        if self.box_reg_loss_type == "smooth_l1" and self.smooth_l1_beta == 0.0:
+        if not self.cls_agnostic_bbox_reg:  # fast_rcnn.py:445-450: the row's own class's four columns
+            loss_box = F.box_reg_loss_cls(self.box_reg_loss_type, deltas, proposal_boxes, gt_boxes, gt_classes, self.num_classes,
+                                          self.box2box_weights, max(r, 1.0), self.smooth_l1_beta, _SCALE_CLAMP)
+        elif self.box_reg_loss_type == "smooth_l1" and self.smooth_l1_beta == 0.0:
             loss_box = F.box_reg_l1_loss(deltas, proposal_boxes, gt_boxes, gt_classes, self.num_classes,
                                          self.box2box_weights, max(r, 1.0))
         else:
@@ -213,7 +216,8 @@ class FastRCNNOutputLayers(nn.Module):
         return {k: v * self.loss_weight.get(k, 1.0) for k, v in losses.items()}
 
     def predict_boxes(self, predictions, proposals, stacked=False):
-        """stacked=True (BatchList input): one [B, S, 4] tensor instead of the per-image tuple."""
+        """Per image [R_i, 4], class specific [R_i, 4 K]; stacked=True (BatchList input): one [B, S, .] tensor instead of the
+        per-image tuple."""
         _, deltas = predictions
         num_prop = [len(p) for p in proposals]
         if isinstance(proposals, BatchList) and proposals.stacked:
@@ -221,12 +225,16 @@ class FastRCNNOutputLayers(nn.Module):
         else:
             assert not stacked or len(set(num_prop)) == 1
             proposal_boxes = torch.cat([p.proposal_boxes.tensor for p in proposals], dim=0)
+        width = 4 if self.cls_agnostic_bbox_reg else 4 * self.num_classes
         if proposal_boxes.shape[0] == 0:
-            return [proposal_boxes.new_zeros((0, 4)) for _ in proposals]
-        boxes = F.apply_deltas(proposal_boxes, deltas[:, :4].float().contiguous(), self.box2box_weights, None, None,
-                               _SCALE_CLAMP)
+            return [proposal_boxes.new_zeros((0, width)) for _ in proposals]
+        if self.cls_agnostic_bbox_reg:
+            boxes = F.apply_deltas(proposal_boxes, deltas[:, :4].float().contiguous(), self.box2box_weights, None, None,
+                                   _SCALE_CLAMP)
+        else:  # the deltas are read where the predictor left them: no [R, K, 4] copy of the proposals, no fp32 copy of the deltas
+            boxes = F.apply_deltas_cls(proposal_boxes.float(), deltas.detach(), self.num_classes, self.box2box_weights, _SCALE_CLAMP)
         if stacked:
-            return boxes.view(len(num_prop), num_prop[0], 4)
+            return boxes.view(len(num_prop), num_prop[0], width)
         return boxes.split(num_prop)
 
     def predict_probs(self, predictions, proposals, split=True):
@@ -626,6 +634,7 @@ class CascadeROIHeads(StandardROIHeads):
         box_heads = nn.ModuleList(box_heads)
         box_predictors = nn.ModuleList(box_predictors)
         assert len(box_predictors) == num_stages and len(proposal_iou_thresholds) == num_stages
+        assert all(p.cls_agnostic_bbox_reg for p in box_predictors), "CascadeROIHeads only support class-agnostic regression now!"
         super().__init__(box_in_features=box_in_features, box_pooler=box_pooler, box_head=box_heads,
                          box_predictor=box_predictors, **kwargs)
         self.cascade_ious = tuple(proposal_iou_thresholds)

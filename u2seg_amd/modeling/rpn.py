@@ -3,7 +3,8 @@
 proposal_generator/proposal_utils.py:22-205).
 
 Device work goes through the HIP kernels: shared 3x3 conv + 1x1 heads (conv_igemm), anchor<->gt IoU matching
-(u2_iou_match), the fused per-level loss (u2_rpn_loss_level), box decoding (u2_apply_deltas) and per-level NMS
+(u2_iou_match), the fused per-level loss (u2_rpn_loss_level; u2_rpn_loss_level_opt with the
+localisation loss options), box decoding (u2_apply_deltas) and per-level NMS
 (u2_batched_nms), per-level top-k, score sort and anchor subsampling (u2_topk_rows).  torch is left with gathers / concatenation."""
 import math
 
@@ -17,6 +18,7 @@ from ..structures import Boxes, Instances
 from ..utils.events import RPN_SLOT, step_counters
 from ..utils.registry import Registry
 from .batched import LazyProposals, PaddedTargets, device_constant
+from .box_losses import BOX_REG_LOSS_TYPES
 from .sampling import subsample_labels
 
 ANCHOR_GENERATOR_REGISTRY = Registry("ANCHOR_GENERATOR")
@@ -206,9 +208,16 @@ class RPN(nn.Module):
         if isinstance(loss_weight, float):
             loss_weight = {"loss_rpn_cls": loss_weight, "loss_rpn_loc": loss_weight}
         self.loss_weight = loss_weight
-        assert box_reg_loss_type == "smooth_l1" and smooth_l1_beta == 0.0, "the U2Seg configs use L1 (beta 0)"
-        assert tuple(bbox_reg_weights) == (1.0, 1.0, 1.0, 1.0)
-        self.bbox_reg_weights = tuple(bbox_reg_weights)
+        if box_reg_loss_type not in BOX_REG_LOSS_TYPES:
+            raise ValueError("Invalid dense box regression loss type '%s' (MODEL.RPN.BBOX_REG_LOSS_TYPE is one of %s)"
+                             % (box_reg_loss_type, ", ".join(BOX_REG_LOSS_TYPES)))
+        bbox_reg_weights = tuple(float(w) for w in bbox_reg_weights)
+        if len(bbox_reg_weights) != 4 or min(bbox_reg_weights) <= 0:
+            raise ValueError("MODEL.RPN.BBOX_REG_WEIGHTS must be four positive numbers, got %r" % (bbox_reg_weights,))
+        if not float(smooth_l1_beta) >= 0:
+            raise ValueError("MODEL.RPN.SMOOTH_L1_BETA must be >= 0, got %r" % (smooth_l1_beta,))
+        self.box_reg_loss_type, self.smooth_l1_beta = box_reg_loss_type, float(smooth_l1_beta)
+        self.bbox_reg_weights = bbox_reg_weights
 
     @classmethod
     def from_config(cls, cfg, input_shape):
@@ -284,7 +293,8 @@ class RPN(nn.Module):
         if counters is not None:  # rpn.py:396-403: the subsampled positives / negatives, counted on the device
             F.count_labels_i8(labels.contiguous(), counters[RPN_SLOT:RPN_SLOT + 2])
         loss_cls, loss_loc = F.rpn_losses(labels, match, gt_boxes_pad, anchors_per_level, self.rpn_head.num_anchors,
-                                          normalizer, objs, dlts)
+                                          normalizer, objs, dlts, self.box_reg_loss_type, self.smooth_l1_beta,
+                                          self.bbox_reg_weights, _SCALE_CLAMP)
         losses = {"loss_rpn_cls": loss_cls, "loss_rpn_loc": loss_loc}
         return {k: v * self.loss_weight.get(k, 1.0) for k, v in losses.items()}
 
