@@ -959,3 +959,167 @@ def kmeans_labels(pattern, n, k, gen):
         allowed = torch.tensor([j for j in range(1, k - 1) if not k // 3 <= j < k // 2])
         return allowed[torch.randint(0, allowed.numel(), (n,), generator=gen)]
     raise ValueError(pattern)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# nearest-neighbour search (u2seg_amd/csrc/knn_select.h, knn.hip, usl.hip): the lists, the select stage's key error, decidability
+# ----------------------------------------------------------------------------------------------------------------------------
+KN_SPARE = 4           # knn.hip KN_SPARE, usl.hip US_SPARE: candidates kept beyond the K (H) that are returned
+
+
+def knn_dists(x_train, x_query, budget=1 << 25):
+    """[Nq, Nt] float64: sum_d (x_query_id - x_train_jd)^2 in the difference form, at most `budget` differences at a time."""
+    x64, y64 = x_query.to(F64), x_train.to(F64)
+    nq, (nt, d) = x64.shape[0], y64.shape
+    out = torch.empty((nq, nt), dtype=F64, device=x_query.device)
+    step = max(1, budget // max(1, nt * d))
+    for s in range(0, nq, step):
+        out[s: s + step] = ((x64[s: s + step, None, :] - y64[None, :, :]) ** 2).sum(-1)
+    return out
+
+
+def knn_ref(x_train, x_query, k, budget=1 << 25):
+    """Brute-force k nearest neighbours in float64: (d [Nq, k] float64 ascending, ind [Nq, k] int64, dist [Nq, Nt] float64 - the whole
+    matrix, for knn_decidable).  A stable sort: among equal distances the smaller train index comes first; an infinite distance
+    sorts behind every number and a NaN behind that (torch.sort), so a train row with a non-finite element is ranked last."""
+    dist = knn_dists(x_train, x_query, budget)
+    s = torch.sort(dist, dim=1, stable=True)
+    return s.values[:, :k].contiguous(), s.indices[:, :k].contiguous(), dist
+
+
+def knn_key_bound(x_train, x_query):
+    """E_i [Nq] float64: a bound on |computed key - true key| of the select stage for query row i and EVERY train row j.
+
+    The kernel ranks the train rows of query i by the key  kappa_ij = |y'_j|^2 - 2 x'_i . y'_j,  x' = x - m, y' = y - m, where m is
+    the point the kernel translates by; kappa_ij = d_ij - |x'_i|^2, so the true keys order the rows as the true distances do,
+    whatever m is.  In fp32, u = 2^-24, gamma_n = n u / (1 - n u) (gamma32), -ffp-contract=off:
+      m        per column the sum of the FINITE train elements over Nt: a sum of at most Nt terms in some order (error
+               <= gamma_(Nt-1) sum|y|) and one division, so |m - mean| <= delta := gamma_Nt sum|y| / Nt with mean = sum y / Nt, both
+               sums over the finite elements.  m only has to be A point, but the magnitudes below are taken about it:
+               |x' | <= a := |x - mean| + delta,  |y'| <= b := |y - mean| + delta  elementwise.
+      staging  fl(x - m) = x'(1 + e), |e| <= u: one rounding per element of either operand.
+      |y'_j|^2 squares (one rounding each) of the staged elements, summed in some order: D - 1 more roundings per term, with the two
+               of the staging  |tn_j - |y'_j|^2| <= gamma_(D+2) b_j . b_j.
+      x'.y'    an fma chain of length D on the MFMA, |fl(a.b) - a.b| <= gamma_D |a|.|b|, with the staging's two roundings
+               |acc_ij - x'_i.y'_j| <= gamma_(D+2) a_i . b_j.
+      key      fl(tn_j - 2 acc_ij): the doubling is exact, the subtraction rounds once, (1 + u)(...) - 1: with
+               u + gamma_(D+2) + u gamma_(D+2) <= gamma_(D+3) (Higham, Lemma 3.3) and |kappa_ij| <= b_j.b_j + 2 a_i.b_j
+                   |key_ij - kappa_ij| <= gamma_(D+3) (b_j . b_j + 2 a_i . b_j) =: E_ij,       E_i = max_j E_ij.
+    The maximum runs over the train rows without a NaN or Inf element: the others are never ranked."""
+    x64, y64 = x_query.to(F64), x_train.to(F64)
+    nt, d = y64.shape
+    fin = torch.where(torch.isfinite(y64), y64, 0.0)
+    mean = fin.sum(0) / nt
+    delta = float(gamma32(nt)) * fin.abs().sum(0) / nt
+    y64 = y64[torch.isfinite(y64).all(1)]
+    a, b = (x64 - mean).abs() + delta, (y64 - mean).abs() + delta
+    per = (b * b).sum(1)[None, :] + 2 * (a @ b.T)
+    return float(gamma32(d + 3)) * per.max(1).values
+
+
+def knn_decidable(dist, k, e, spare=KN_SPARE):
+    """[Nq] bool: at most k + spare train rows have a float64 distance <= d_(k) + 2 E_i, d_(k) the k-th smallest of the row.
+    Then the k + spare smallest COMPUTED keys (ties by index) contain every row of the true top k: were a row t with d_t <= d_(k)
+    missing, k + spare other rows would have computed keys <= its own, hence true keys <= kappa_t + 2 E_i, hence distances
+    <= d_(k) + 2 E_i - k + spare + 1 rows with t itself.  Non-finite distances are never <= anything finite."""
+    dk = torch.sort(dist, dim=1).values[:, k - 1]
+    return (dist <= (dk + 2 * e)[:, None]).sum(1) <= k + spare
+
+
+def lattice_rows(n, d, gen, amp=8):
+    """[n, d] fp32 on the CPU: integer coordinates in [-amp, amp], every row followed by its negation and, for odd n, a last row of
+    zeros - every column sums to exactly 0 in any order, so the select stage's translation is the identity and, coordinates being
+    small integers, every key and every distance an integer far below 2^24: exact in fp32 whatever the order of summation."""
+    half = torch.randint(-amp, amp + 1, (n // 2, d), generator=gen).float()
+    rows = torch.stack([half, -half], dim=1).reshape(-1, d)
+    return torch.cat([rows, torch.zeros((n % 2, d))]) if n % 2 else rows
+
+
+def assert_lattice(x_train, x_query, amp=8):
+    """The preconditions of the bit-for-bit kNN / USL cases, on finite elements: small integers, exact zero column sums."""
+    for t in (x_train, x_query):
+        f = t[torch.isfinite(t)]
+        assert torch.equal(f, f.round()) and float(f.abs().max()) <= amp
+    yt = torch.where(torch.isfinite(x_train), x_train, 0.0)
+    assert not bool(yt.to(F64).sum(0).any()), "train columns must sum to exactly 0"
+    assert 3 * x_train.shape[1] * (2 * amp) ** 2 < TWO24
+
+
+def fp32_value(v):
+    """The fp32 number next to the Python float v, as a Python float: what a C `float` argument receives."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def usl_reg_ref(x, sel, labels, reg_in, h, alpha, momentum, one_minus_momentum, exclude, exact=False):
+    """One update of USL's selection regularizer (u2_usl_regularizer, usl.hip) in float64 with a per-row error bound and the rows
+    the bound holds for -> (want [N], bound [N], checked [N] bool, alt).  want = reg_in * momentum + S * one_minus_momentum with
+    S = sum over the H nearest selected rows of 1 / v^alpha after the reference's mask (tests/usl_select_oracle.py: regularizer64);
+    the two scalars are taken as given - hand the kernel the same fp32 values (fp32_value).  usl_reg_within applies the result.
+
+    The bound, u = 2^-24, gamma_n = gamma32(n), g = gamma_(D+2) the refine stage's difference-form bound (0 with exact=True:
+    lattice inputs, whose distances are integers below 2^24):
+      which rows  When the K + 4 -> H + 4 candidates contain the true top H (knn_decidable with H for K), the kernel's c-th smallest
+                  fp32 distance among them lies within g of the true c-th smallest d_(c), c <= H: an order statistic moves by no more
+                  than its elements do.  So the kernel's sorted list is the reference's sorted list, term by term, up to g - whichever
+                  rows stand behind the values.  A distance is 0 in fp32 exactly when it is 0 (no square underflows: asserted), so
+                  the zero mask strikes the same terms.  With exact=True the kernel's order IS the stable float64 order and every
+                  row is checked.
+      the label   The row behind a value matters to the same-cluster mask alone: there the position lab = labels[i] must be in both
+                  top-H sets or in neither, which fp32 guarantees when d_lab (1 + g) < d_(H+1) (1 - g) (in) or
+                  d_lab (1 - g) > d_(H) (1 + g) (out), or H = S (in), or lab is no position (out); the argument above then holds for
+                  the lists without lab.  Where lab is the H-th or the (H+1)-th nearest and those two are closer than that, fp32 may
+                  rank either of them H-th: alt = (want_alt, bound_alt, rows) is the other outcome - the (H+1)-th in place of the
+                  H-th, the mask on whichever of them is lab - and the kernel may give either.  That needs the (H-1)-th and the
+                  (H+2)-th to be clear of both; a row where they are not, or where lab is unclear in another way, is unchecked.
+      a term      1 / v (alpha 1: the distance's factor and one rounding), 1 / sqrt(v) (alpha 0.5: the factor - a square root halves
+                  it, counted whole - and two roundings), 1 / (v v) (alpha 2: the factor twice, two roundings): a product of c
+                  factors (1 + eta)^(+-1), |eta| <= g, and m factors (1 + eps)^(+-1), |eps| <= u, is within
+                  r = s / (1 - s), s = c g + m u, of 1 (Higham, Lemma 3.1).  A masked term is 1e10 on both sides (an fp32 number).
+      the sum     H terms in some order: gamma_(H-1) <= gamma_H of the sum of the computed terms, which are positive:
+                  |S^ - S| <= e_S := (r + gamma_H (1 + r)) S.
+      the blend   fl(fl(reg_in * momentum) + fl(S^ * one_minus_momentum)): three roundings,
+                  bound = one_minus_momentum e_S + gamma_3 (|reg_in| momentum + one_minus_momentum (S + e_S))."""
+    from tests.usl_select_oracle import regularizer64
+
+    n, (s, d) = x.shape[0], sel.shape
+    assert alpha in (1, 0.5, 2) and 1 <= h <= s and momentum >= 0 and one_minus_momentum >= 0
+    g = 0.0 if exact else float(gamma32(d + 2))
+    c, m = {1: (1, 1), 0.5: (1, 2), 2: (2, 2)}[alpha]
+    r = (c * g + m * U24) / (1 - (c * g + m * U24))
+    reg64 = reg_in.to(F64)
+
+    def blend(new):
+        e_s = (r + float(gamma32(h)) * (1 + r)) * new
+        bound = one_minus_momentum * e_s + float(gamma32(3)) * (reg64.abs() * momentum + one_minus_momentum * (new + e_s))
+        return reg64 * momentum + new * one_minus_momentum, bound
+
+    want, bound = blend(regularizer64(x, sel, labels, torch.zeros(n, dtype=F64, device=x.device), h, alpha, 0.0, exclude))
+    checked = torch.ones(n, dtype=torch.bool, device=x.device)
+    alt = (want, bound, ~checked)
+    if n and not exact:
+        dist = knn_dists(sel, x)
+        assert not bool(((dist > 0) & (dist < 1e-30)).any())
+        checked = knn_decidable(dist, h, knn_key_bound(sel, x))
+        if exclude and h < s:
+            srt = torch.sort(dist, dim=1, stable=True)
+            v, j = srt.values, srt.indices
+            lab = labels.to(x.device).reshape(-1)
+            position = (lab >= 0) & (lab < s)
+            d_lab = torch.gather(dist, 1, lab.clamp(0, s - 1)[:, None])[:, 0]
+            clear = (d_lab * (1 + g) < v[:, h] * (1 - g)) | (d_lab * (1 - g) > v[:, h - 1] * (1 + g)) | ~position
+            at_edge = (j[:, h - 1] == lab) | (j[:, h] == lab)
+            inner = v[:, h - 2] * (1 + g) < v[:, h - 1] * (1 - g) if h > 1 else torch.ones_like(clear)
+            outer = v[:, h + 1] * (1 - g) > v[:, h] * (1 + g) if h + 1 < s else torch.ones_like(clear)
+            swap = ~clear & at_edge & inner & outer
+            vm = torch.where(j[:, : h + 1] == lab[:, None], 1e10, v[:, : h + 1])
+            terms = 1 / vm if alpha == 1 else 1 / vm ** alpha
+            alt = blend(terms[:, : h - 1].sum(1) + terms[:, h]) + (swap,)
+            checked &= clear | swap
+    return want, bound, checked, alt
+
+
+def usl_reg_within(got, ref):
+    """[N] bool: reg_out within usl_reg_ref's bound of the reference - or, on the rows of alt, of the other outcome."""
+    want, bound, _, (want_alt, bound_alt, rows) = ref
+    g = got.to(F64)
+    return ((g - want).abs() <= bound) | (rows & ((g - want_alt).abs() <= bound_alt))

@@ -598,3 +598,128 @@ def test_kmeans_argmin_ref_equals_the_oracle_and_torch_argmin_on_nan():
     labf, _ = R.kmeans_argmin_ref(x, cf)
     assert not bool((labf == 6).any()) and torch.equal(labf[lab != 6], lab[lab != 6])
     assert R.kmeans_argmin_ref(x[:3], c[:1])[1].tolist() == [float("inf")] * 3
+
+
+def test_knn_ref_equals_the_oracle_in_float64_and_a_hand_worked_case():
+    """knn_ref == oracle.ops.knn on float64 inputs (the oracle stores its distances in fp32: compared after that rounding), for any
+    chunking; a hand-worked case with a tie and a duplicate; a train row with NaN / Inf is ranked behind every finite one."""
+    from oracle import ops as O
+
+    g = torch.Generator().manual_seed(4)
+    xt, xq = torch.randn((157, 24), generator=g), torch.randn((61, 24), generator=g)
+    xt[90] = xt[12]                                              # a duplicate: equal distances from every query
+    d, ind, dist = R.knn_ref(xt, xq, 9)
+    assert d.dtype == F64 and ind.dtype == torch.int64 and dist.shape == (61, 157) and d.shape == ind.shape == (61, 9)
+    want_ind, want_d = O.knn(xt.double(), xq.double(), 9)
+    assert torch.equal(ind, want_ind) and torch.equal(d.float(), want_d)
+    assert torch.equal(torch.gather(dist, 1, ind), d) and bool((d[:, 1:] >= d[:, :-1]).all())
+    for budget in (1, 157 * 24 * 7, 1 << 30):                    # one row, seven rows, everything at a time
+        d2, ind2, dist2 = R.knn_ref(xt, xq, 9, budget=budget)
+        assert torch.equal(d, d2) and torch.equal(ind, ind2) and torch.equal(dist, dist2)
+    # by hand: the query (0, 0); train rows 0 and 3 tie at distance 25, rows 1 and 4 are the same point at distance 1
+    yt = torch.tensor([[3.0, 4.0], [1.0, 0.0], [0.0, 6.0], [-5.0, 0.0], [1.0, 0.0], [2.0, 0.0]])
+    d, ind, dist = R.knn_ref(yt, torch.zeros((1, 2)), 5)
+    assert dist.tolist() == [[25.0, 1.0, 36.0, 25.0, 1.0, 4.0]]
+    assert ind.tolist() == [[1, 4, 5, 0, 3]] and d.tolist() == [[1.0, 1.0, 4.0, 25.0, 25.0]]
+    yt[1, 0], yt[5, 1] = float("nan"), float("inf")
+    d, ind, _ = R.knn_ref(yt, torch.zeros((1, 2)), 6)
+    assert ind.tolist() == [[4, 0, 3, 2, 5, 1]] and d[0, :4].tolist() == [1.0, 25.0, 25.0, 36.0]
+    assert float(d[0, 4]) == float("inf") and bool(torch.isnan(d[0, 5]))
+
+
+def test_knn_decidable_on_three_points_and_the_key_bound():
+    """knn_decidable by hand: train points 0, 3, 3.01 on a line and the query 0 - distances 0, 9, 9.0601.  With E = 0.1 the third
+    lies within 2 E of the second: k = 2 is decidable with one spare candidate and not with none; k = 1 (nothing within 0.2 of 0)
+    and k = 3 (there is no fourth) are decidable without any; with E = 0.01 so is k = 2.  knn_key_bound: its formula on a case
+    small enough to evaluate by hand, and - a plausibility check, not where the bound comes from - the expanded-form key in fp32
+    on the CPU stays inside it."""
+    yt = torch.tensor([[0.0], [3.0], [3.01]], dtype=F64)
+    dist = R.knn_ref(yt, torch.zeros((1, 1), dtype=F64), 1)[2]
+    assert (dist - torch.tensor([[0.0, 9.0, 9.0601]], dtype=F64)).abs().max() < 1e-12
+    e = torch.tensor([0.1], dtype=F64)
+    assert R.knn_decidable(dist, 2, e, spare=1).tolist() == [True] and R.knn_decidable(dist, 2, e, spare=0).tolist() == [False]
+    assert R.knn_decidable(dist, 1, e, spare=0).tolist() == [True] and R.knn_decidable(dist, 3, e, spare=0).tolist() == [True]
+    assert R.knn_decidable(dist, 2, e / 10, spare=0).tolist() == [True]
+    assert R.knn_decidable(dist, 2, e).tolist() == [True] and R.KN_SPARE == 4
+    # two train rows (2, 0) and (-2, 0): mean 0, mean|y| = (2, 0); the query (1, 1): a = (1, 1) + delta, b = (2, 0) + delta
+    yt, xq = torch.tensor([[2.0, 0.0], [-2.0, 0.0]]), torch.tensor([[1.0, 1.0]])
+    dl = float(R.gamma32(2)) * 2.0
+    want = float(R.gamma32(5)) * ((2 + dl) ** 2 + 2 * (1 + dl) * (2 + dl))
+    assert abs(float(R.knn_key_bound(yt, xq)[0]) - want) <= 1e-15 * want
+    # a third train row (NaN, 0): its finite elements count for the mean of now three rows - still (0, 0), sum|y| / 3 = (4/3, 0) -,
+    # the row itself is not in the maximum
+    bad = torch.cat([yt, torch.tensor([[float("nan"), 0.0]])])
+    dl = float(R.gamma32(3)) * 4.0 / 3.0
+    want = float(R.gamma32(5)) * ((2 + dl) ** 2 + 2 * (1 + dl) * (2 + dl))
+    assert abs(float(R.knn_key_bound(bad, xq)[0]) - want) <= 1e-15 * want
+    g = torch.Generator().manual_seed(8)
+    for d, off in ((16, 0.0), (48, 0.0), (32, 100.0), (768, 0.0)):
+        yt, xq = torch.randn((300, d), generator=g) + off, torch.randn((40, d), generator=g) + off
+        m32 = yt.mean(0)
+        y1, x1 = yt - m32, xq - m32
+        key32 = (y1 * y1).sum(1)[None, :] - 2 * (x1 @ y1.T)
+        y2, x2 = yt.double() - m32.double(), xq.double() - m32.double()
+        key64 = (y2 * y2).sum(1)[None, :] - 2 * (x2 @ y2.T)
+        e = R.knn_key_bound(yt, xq)
+        assert bool(((key32.double() - key64).abs() <= e[:, None]).all())
+        assert float(e.max()) < 1e-2 * float(R.knn_dists(yt, xq).min())
+
+
+def test_lattice_rows_are_what_the_exact_cases_need():
+    g = torch.Generator().manual_seed(2)
+    for n in (1, 2, 31, 320, 641):
+        y = R.lattice_rows(n, 16, g)
+        assert y.shape == (n, 16) and y.dtype == torch.float32
+        R.assert_lattice(y, R.lattice_rows(5, 16, g))
+        assert torch.equal(y[0:n - 1:2], -y[1:n:2]) and (n % 2 == 0 or not bool(y[-1].any()))
+    with pytest.raises(AssertionError):
+        R.assert_lattice(torch.ones((2, 16)), torch.ones((1, 16)))
+    with pytest.raises(AssertionError):
+        R.assert_lattice(R.lattice_rows(4, 16, g), torch.full((1, 16), 0.5))
+
+
+def test_usl_reg_ref_equals_the_oracle_and_names_the_other_outcome_at_the_edge():
+    """usl_reg_ref's value is regularizer64's (momentum 0.5: 1 - momentum is the same number in both); its bound holds for the same
+    update computed in fp32 on the CPU (a plausibility check, not where the bound comes from); and by hand: selected rows at 1, 2,
+    2.000001 and 10 on a line, the data row at 0 with the label of the row at 2, H = 2 with the same-cluster mask - the second and
+    third distances (4 and 4.000004) are closer than 2 gamma_18 * 4, so fp32 may put either second: the reference masks the second
+    (1 + 1e-10), the other outcome keeps the third unmasked (1 + 1 / 4.000004); with the label on the nearest row nothing is open."""
+    from tests.usl_select_oracle import regularizer64
+
+    g = torch.Generator().manual_seed(6)
+    x, y = torch.randn((90, 32), generator=g), torch.randn((40, 32), generator=g)
+    x[3] = y[5]
+    labels = torch.randint(0, 43, (90,), generator=g)
+    labels[3] = 5
+    reg = torch.rand(90, generator=g)
+    for alpha in (1, 0.5, 2):
+        for exclude in (False, True):
+            ref = R.usl_reg_ref(x, y, labels, reg, 7, alpha, 0.5, 0.5, exclude)
+            assert torch.equal(ref[0], regularizer64(x, y, labels, reg, 7, alpha, 0.5, exclude)) and bool(ref[2].all()) and not bool(ref[3][2].any())
+            d32 = ((x[:, None, :] - y[None, :, :]) ** 2).sum(-1)
+            v, j = torch.sort(d32, dim=1, stable=True)
+            v, j = v[:, :7].clone(), j[:, :7]
+            if exclude:
+                v[j == labels[:, None]] = 1e10
+            else:
+                v[v == 0] = 1e10
+            p = v if alpha == 1 else (v.sqrt() if alpha == 0.5 else v * v)
+            got = reg * 0.5 + (1 / p).sum(1) * 0.5
+            assert bool(R.usl_reg_within(got, ref).all())
+            assert float((ref[1] / ref[0]).max()) < 1e-5
+    sel = torch.zeros((4, 16))
+    sel[:, 0] = torch.tensor([1.0, 2.0, 2.000001, 10.0])
+    x0, zero = torch.zeros((1, 16)), torch.zeros(1)
+    want, bound, checked, (want_alt, _, rows) = R.usl_reg_ref(x0, sel, torch.tensor([1]), zero, 2, 1, 0.0, 1.0, True)
+    d3 = float(sel[2, 0].double() ** 2)
+    assert rows.tolist() == [True] and checked.tolist() == [True] and 4 < d3 < 4 * (1 + 2 * float(R.gamma32(18)))
+    assert abs(float(want[0]) - (1 + 1e-10)) < 1e-15 and abs(float(want_alt[0]) - (1 + 1 / d3)) < 1e-15
+    assert R.usl_reg_within(torch.tensor([1.0]), (want, bound, checked, (want_alt, bound, rows))).tolist() == [True]
+    assert R.usl_reg_within(torch.tensor([1.0 + 1 / 4.0]), (want, bound, checked, (want_alt, bound, rows))).tolist() == [True]
+    assert R.usl_reg_within(torch.tensor([1.1]), (want, bound, checked, (want_alt, bound, rows))).tolist() == [False]
+    ref = R.usl_reg_ref(x0, sel, torch.tensor([0]), zero, 2, 1, 0.0, 1.0, True)
+    assert not bool(ref[3][2].any()) and bool(ref[2].all()) and abs(float(ref[0][0]) - (1e-10 + 0.25)) < 1e-15
+    # three rows inside the window: not a plain swap any more, the row is unchecked
+    sel[3, 0] = 2.000002
+    ref = R.usl_reg_ref(x0, sel, torch.tensor([1]), zero, 2, 1, 0.0, 1.0, True)
+    assert ref[2].tolist() == [False] and ref[3][2].tolist() == [False]

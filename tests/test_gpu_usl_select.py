@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import float64_refs as R
 from tests.usl_select_oracle import horizon_dists, regularizer64, select_loop
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +59,14 @@ def clustered(n, d, k, seed, unit=False):
 
 
 def check_reg(x, y, labels, reg_in, got, h, alpha, momentum, exclude):
+    # the derived per-row bound of float64_refs.usl_reg_ref on the scalars the kernel received (select.py rounds momentum and
+    # 1 - momentum to fp32), for every row: none may be undecidable, which is a matter of the reference alone
+    m32, omm32 = R.fp32_value(float(momentum)), R.fp32_value(float(1 - momentum))
+    ref = R.usl_reg_ref(x, y, labels, reg_in, h, alpha, m32, omm32, exclude)
+    assert int((~ref[2]).sum()) == 0, "%d rows are undecidable: the case does not test what it is there for" % int((~ref[2]).sum())
+    over = ~R.usl_reg_within(got, ref)
+    assert not bool(over.any()), (int(over.sum()), torch.where(over)[0][:8].tolist())
+    # and the flat tolerance these tests started with, against the reference's own scalars
     want = regularizer64(x, y, labels, reg_in, h, alpha, momentum, exclude)
     rel = (got.double() - want).abs() / want.abs().clamp_min(1e-30)
     bad = torch.where(rel > RTOL)[0]

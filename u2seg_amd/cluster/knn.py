@@ -23,7 +23,13 @@ def _workspace(nq, nt, d, k, device):
 
 
 def kNN(x_train, x_test, K=20):
-    """nn_utils.py:204-227: (ind_knn int64 [N_test, K], d_knn fp32 [N_test, K]); squared L2 distances in ascending order."""
+    """nn_utils.py:204-227: (ind_knn int64 [N_test, K], d_knn fp32 [N_test, K]); squared L2 distances in ascending order,
+    equal distances in the order of the train index.
+
+    Non-finite features: a train row with a NaN or Inf element is never anybody's neighbour (the reference's Kmin_argKmin
+    never selects a NaN; the lists are those of the train set without that row, with its numbering); where fewer than K
+    finite train rows are left, the trailing slots of every list hold NaN / -1.  A query row with a NaN or Inf element has
+    no ranked neighbour: its whole list is NaN / -1."""
     assert len(x_train.shape) == 2
     assert len(x_test.shape) == 2
     assert x_train.is_cuda and x_test.is_cuda and x_train.shape[1] == x_test.shape[1]
@@ -31,7 +37,7 @@ def kNN(x_train, x_test, K=20):
     nq, nt, d = x_test.shape[0], x_train.shape[0], x_train.shape[1]
     if nt < K:
         raise ValueError("kNN: %d train rows < K = %d (the reference assumes at least K rows, nn_utils.py:236)" % (nt, K))
-    # a query row with non-finite features has no ranked neighbour: it keeps NaN distances and index -1
+    # u2_knn writes ranked neighbours only: the slots described above keep this fill
     d_knn = torch.full((nq, K), float("nan"), dtype=torch.float32, device=x_test.device)
     ind_knn = torch.full((nq, K), -1, dtype=torch.int64, device=x_test.device)
     ws = _workspace(nq, nt, d, K, x_test.device)

@@ -16,6 +16,9 @@
 //   refine  one wave per query row: recomputes sum_d (x - y)^2 for the KK candidates in the reference's difference form
 //           (no cancellation; the row's own distance is exactly 0), ranks them by (distance, index) and writes the first K.
 // The 4 spare candidates absorb the rounding difference between the two formulations at the K-th / (K+1)-th boundary.
+// Non-finite rows: a train row with a NaN or Inf element is left out of the column mean (knn_colsum_kernel), its own key is
+// NaN or +Inf and never passes the threshold, so it is in nobody's list; a query row with one is skipped by the refine
+// kernel.  d_knn / ind_knn are written for ranked neighbours only: every other slot keeps what the caller put there.
 // The select kernel lives in knn_select.h (instantiated here as <32, 10>); usl.hip uses a longer list of the same kernel.
 #include "knn_select.h"
 #include "u2seg_hip.h"
@@ -35,6 +38,12 @@ __global__ __launch_bounds__(256) void knn_refine_kernel(const float* __restrict
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= Nq) return;
   const float* xi = xq + (size_t)row * D;
+  // A query row with a NaN or Inf element has no ranked neighbour: its slots are left as the caller filled them.  (NaN keys
+  // never pass the select stage's threshold, but an Inf element gives keys of -Inf wherever the train element is larger than
+  // the mean, and those do.)
+  bool finite = true;
+  for (int d = lane; d < D; d += 64) finite &= isfinite(xi[d]);
+  if (!__all(finite)) return;
   float my_d = INFINITY;
   int my_j = INT_MAX;
   for (int k = 0; k < KK; ++k) {

@@ -33,7 +33,10 @@ constexpr size_t kn_lds_bytes() {
               + 2 * KN_ROWS);                       // qcnt, thr
 }
 
-// partial[s][d] = sum over the rows of slice s of y[.][d]  (fixed order: deterministic)
+// partial[s][d] = sum over the rows of slice s of the finite y[.][d]  (fixed order: deterministic).  A NaN or Inf element is
+// left out: the translation point is arbitrary (distances do not depend on it), and a mean poisoned by one bad train row
+// would turn every key of every row into NaN.  Left out, only the bad row's own key is NaN or +Inf, which never passes the
+// threshold: the row is never ranked, as torch.sort and Kmin_argKmin never rank it.
 __global__ __launch_bounds__(256) void knn_colsum_kernel(const float* __restrict__ y, float* __restrict__ partial, int D, int N) {
   __shared__ float red[4][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -42,7 +45,7 @@ __global__ __launch_bounds__(256) void knn_colsum_kernel(const float* __restrict
   const int r0 = blockIdx.y * per, r1 = min(N, r0 + per);
   float s = 0.f;
   if (d < D)
-    for (int r = r0 + w; r < r1; r += 4) s += y[(size_t)r * D + d];
+    for (int r = r0 + w; r < r1; r += 4) { const float v = y[(size_t)r * D + d]; if (isfinite(v)) s += v; }
   red[w][lane] = s;
   __syncthreads();
   if (w == 0 && d < D) partial[(size_t)blockIdx.y * D + d] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);

@@ -18,6 +18,7 @@
 //           (distance, position), then the mask, the power sum over the first H and the momentum blend.  Only reg_out and
 //           the zero count leave the kernel; the candidate lists are workspace.
 // The 4 spare candidates absorb the rounding difference between the two formulations at the H-th / (H+1)-th boundary.
+// A selected row with a NaN or Inf element is left out of the column mean and never becomes a candidate (knn_select.h).
 #include "knn_select.h"
 #include "u2seg_hip.h"
 
