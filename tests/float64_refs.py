@@ -1,5 +1,6 @@
 """Float64 reference helpers of tests/test_gpu_optim_resample_float64.py, tests/test_gpu_conv_float64.py,
-tests/test_gpu_inference_tails_float64.py, tests/test_gpu_box_decisions_float64.py and tests/test_gpu_kmeans_update_float64.py, in a plain module so that the CPU tests of
+tests/test_gpu_inference_tails_float64.py, tests/test_gpu_box_decisions_float64.py, tests/test_gpu_kmeans_update_float64.py and
+tests/test_gpu_kmeans_assign_float64.py, in a plain module so that the CPU tests of
 tests/test_float64_refs_host.py check exactly what the GPU tests use.  Plain torch ops only; nothing here touches the HIP
 library.  Every function works on whatever device its inputs live on."""
 import math
@@ -1123,3 +1124,258 @@ def usl_reg_within(got, ref):
     want, bound, _, (want_alt, bound_alt, rows) = ref
     g = got.to(F64)
     return ((g - want).abs() <= bound) | (rows & ((g - want_alt).abs() <= bound_alt))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# k-means E step at its screening margins (tests/test_gpu_kmeans_assign_float64.py)
+# ----------------------------------------------------------------------------------------------------------------------------
+# Edges of the relative-gap bands, gap / (|x_i| max_j |c_j|).  1e-4 and 2e-2 are the margin_rel the launcher u2_kmeans_assign_shadow
+# hands to the three-product pass and to the leading-piece pass; the shadow pass gets 3e-4 and adds the norms of what fp16 dropped
+# and the index bits to it, so its margin lies between: 3e-3 is ten times its constant.
+KM_BANDS = (1e-4, 3e-3, 2e-2)
+KM_LADDER_RUNGS = (1, 3, 5, 7, 9, 11, 13, 16, 20)
+KM_LADDER_M = (2, 5, 8, 11, 2, 5, 2, 5)     # one per pair of kmeans_ladder_pairs, in its order
+KM_EDGE_ROWS = (0, 127, 128, 255, 256, -1)  # first / last point of a work-group of the exact kernel (128) and of the screens (256)
+
+
+def kmeans_key_bound(x, c):
+    """E_i [N] float64: a bound on |computed key - true key| of the exact E-step kernel (kmeans_assign_kernel) for point i and EVERY
+    centroid j.  The kernel ranks the centroids of point i by the key  kappa_ij = |c_j|^2 - 2 x_i . c_j = d_ij - |x_i|^2,  which orders
+    them as the distances do.  Nothing is translated there: this is knn_key_bound's derivation without m.  In fp32, u = 2^-24,
+    gamma_n = n u / (1 - n u) (gamma32):
+      cn_j   D squares (one rounding each) summed in some order (D - 1 more roundings on a term's way):
+             |cn_j - |c_j|^2| <= gamma_D |c_j|.|c_j|;
+      acc_ij an fma chain of length D on the MFMA:  |acc_ij - x_i.c_j| <= gamma_D |x_i|.|c_j|  (the dot product of the absolute values);
+      key    fl(cn_j - 2 acc_ij): the doubling is exact, the subtraction rounds once; u + gamma_D + u gamma_D <= gamma_(D+1) (Higham,
+             Lemma 3.3), and with knn_key_bound's two spare roundings
+                 |key_ij - kappa_ij| <= gamma_(D+3) (|c_j|.|c_j| + 2 |x_i|.|c_j|) =: E_ij,      E_i = max_j E_ij.
+    The maximum runs over the centroid rows without a NaN or Inf element.  A row of x with a NaN gets E_i = NaN.  No number here is
+    measured."""
+    ax = x.to(F64).abs()
+    ac = c.to(F64)
+    ac = ac[torch.isfinite(ac).all(1)].abs()
+    per = (ac * ac).sum(1)[None, :] + 2 * (ax @ ac.T)
+    return float(gamma32(x.shape[1] + 3)) * per.max(1).values
+
+
+def kmeans_decision_ref(x, c, budget=1 << 25):
+    """What the decision rule of the E step needs, from kmeans_argmin_ref's distance matrix (float64, difference form), row-chunked.
+    Returns a dict of [N] tensors on x's device:
+      ref     the float64 arg-min (NaN distance first, lowest index among equals);   d1  its distance;
+      gap     d_(2) - d_(1), the ABSOLUTE float64 gap between the two smallest distances (inf for K = 1);
+      e       kmeans_key_bound;   rel  gap / (|x_i| max_j |c_j|), norms in float64, the maximum over finite centroid rows;
+      nan     the row of x holds a NaN;
+      decidable   gap > 2 e (never for a NaN row);
+      low     the lowest index j with d_ij <= d_(1) + 2 e;
+      same    every centroid row within that band has the bits of row `low`."""
+    x64, c64 = x.to(F64), c.to(F64)
+    n, (k, d) = x.shape[0], c.shape
+    dev = x.device
+    e = kmeans_key_bound(x, c)
+    fin = torch.isfinite(c64).all(1)
+    cmax = c64[fin].norm(dim=1).max() if bool(fin.any()) else torch.zeros((), dtype=F64, device=dev)
+    # canon[j]: the lowest index whose row has the bits of row j
+    inv = torch.unique(c.contiguous().view(torch.int32), dim=0, return_inverse=True)[1]
+    first = torch.full((int(inv.max()) + 1,), k, dtype=torch.int64, device=dev).scatter_reduce(0, inv, torch.arange(k, device=dev), "amin")
+    canon = first[inv]
+    out = {name: torch.empty(n, dtype=F64, device=dev) for name in ("d1", "gap")}
+    out.update({name: torch.empty(n, dtype=torch.int64, device=dev) for name in ("ref", "low")})
+    out["same"] = torch.empty(n, dtype=torch.bool, device=dev)
+    idx = torch.arange(k, device=dev)
+    step = max(1, budget // max(1, k * d))
+    for s in range(0, n, step):
+        sl = slice(s, s + step)
+        dist = ((x64[sl, None, :] - c64[None, :, :]) ** 2).sum(-1)
+        dist = torch.where(torch.isnan(dist), float("-inf"), dist)
+        two = torch.topk(dist, min(2, k), dim=1, largest=False).values
+        out["ref"][sl] = torch.argmin(dist, dim=1)
+        out["d1"][sl] = two[:, 0]
+        out["gap"][sl] = two[:, 1] - two[:, 0] if k >= 2 else float("inf")
+        band = dist <= (two[:, 0] + 2 * e[sl])[:, None]
+        band |= idx[None, :] == out["ref"][sl][:, None]                      # (a NaN bound compares false: the arg-min itself stays in)
+        out["low"][sl] = torch.where(band, idx[None, :], k).min(1).values
+        out["same"][sl] = torch.where(band, canon[None, :], -1).max(1).values == torch.where(band, canon[None, :], k).min(1).values
+    out["gap"] = torch.where(torch.isnan(out["gap"]), 0.0, out["gap"])        # inf - inf, -inf - -inf: no gap to speak of
+    out["e"] = e
+    out["nan"] = torch.isnan(x).any(1)
+    out["scale"] = x64.norm(dim=1) * cmax
+    out["rel"] = out["gap"] / out["scale"]
+    out["decidable"] = (out["gap"] > 2 * e) & ~out["nan"]
+    return out
+
+
+def kmeans_rule_ok(x, c, labels, ref):
+    """[N] bool: the label obeys the decision rule, the same for every path and every point (ref = kmeans_decision_ref(x, c)):
+      a row of x with a NaN     label 0 (torch.argmin on an all-NaN row; km_less);
+      a decidable point         (gap > 2 E_i) the float64 arg-min: both computed keys are within E_i of the true ones, so the computed
+                                order of the two nearest is the true one, and every other centroid is farther still;
+      an undecidable point      the label l has d_il <= d_(1) + 2 E_i, and where all centroid rows within that band have the same bits
+                                (equal keys, whatever the arithmetic) the lowest index of them.
+    Rows of x with +-Inf are out of scope, as centroid rows with +-Inf are: the expanded form gives Inf - Inf there."""
+    k = c.shape[0]
+    inside = (labels >= 0) & (labels < k)
+    lab = labels.clamp(0, k - 1)
+    d_l = ((x.to(F64) - c.to(F64)[lab]) ** 2).sum(1)
+    d_l = torch.where(torch.isnan(d_l), float("-inf"), d_l)
+    loose = (d_l <= ref["d1"] + 2 * ref["e"]) & (~ref["same"] | (lab == ref["low"]))
+    ok = torch.where(ref["nan"], lab == 0, torch.where(ref["decidable"], lab == ref["ref"], loose))
+    return ok & inside
+
+
+def kmeans_band(ref):
+    """[N] int64: 0 undecidable (or a NaN row), 1 .. 4 the decidable point's relative-gap band (2 E_i / (|x_i| max|c|), 1e-4),
+    [1e-4, 3e-3), [3e-3, 2e-2), >= 2e-2."""
+    b = 1 + sum((ref["rel"] >= edge).long() for edge in KM_BANDS)
+    return torch.where(ref["decidable"], b, torch.zeros_like(b))
+
+
+def kmeans_rule_report(path, x, c, labels, ref):
+    """None when every label obeys the rule, else the failure message: the path, the count of wrong decidable labels (and of
+    undecidable ones outside their band), the first such row with its float64 gap, its E_i and its relative-gap band."""
+    ok = kmeans_rule_ok(x, c, labels, ref)
+    if bool(ok.all()):
+        return None
+    bad = ~ok
+    wrong_dec = bad & ref["decidable"]
+    i = int(torch.nonzero(wrong_dec if bool(wrong_dec.any()) else bad)[0, 0])
+    return ("%s: %d decidable labels differ from the float64 arg-min, %d undecidable labels lie outside d_(1) + 2 E, %d NaN rows are not 0 "
+            "(N = %d, K = %d, D = %d); first: row %d got %d, float64 arg-min %d, gap %.6e, E_i %.6e, relative gap %.3e, band %d" % (
+                path, int(wrong_dec.sum()), int((bad & ~ref["decidable"] & ~ref["nan"]).sum()), int((bad & ref["nan"]).sum()),
+                x.shape[0], c.shape[0], x.shape[1], i, int(labels[i]), int(ref["ref"][i]), float(ref["gap"][i]), float(ref["e"][i]),
+                float(ref["rel"][i]), int(kmeans_band(ref)[i])))
+
+
+def kmeans_ladder_pairs(k):
+    """Centroid pairs (a, b) of the gap ladder - where two candidates meet in the arg-min - with their m, [(a, b, m)]:
+    (0, 1), (15, 16): neighbours inside and across a 16-block;  (3, 19): the same lane of neighbouring 16-blocks;  (31, 32): across
+    the exact kernel's 32-centroid tiles;  (K - 2, K - 1): the last two;  K > 320: (319, 320) and (5, 325) across the blocks of 320,
+    and at K = 641 (7, K - 1), whose last block holds that one centroid.  Pairs that K has no room for, or has twice, fall away.
+    c_b is made from c_a; where b already is another pair's b (K = 641: 640), the pair is made the other way round, c_a from c_b."""
+    cand = [(0, 1), (15, 16), (3, 19), (31, 32), (k - 2, k - 1)]
+    if k > 320:
+        cand += [(319, 320), (5, 325)]
+    if k == 641:
+        cand.append((7, k - 1))
+    out, seen, made = [], set(), set()
+    for i, (a, b) in enumerate(cand):
+        if not (0 <= a < k and 0 <= b < k and a != b) or (a, b) in seen:
+            continue
+        seen.add((a, b))
+        if b in made:
+            a, b = b, a
+        assert b not in made and all(b not in p[:2] for p in out), (k, a, b)
+        made.add(b)
+        out.append((a, b, KM_LADDER_M[i]))
+    return out
+
+
+def kmeans_gap_ladder(k, d, n, offset=0.0, seed=0, device="cpu"):
+    """Inputs of the E-step tests: (x [n, D] fp32, c [K, D] fp32, ref = kmeans_decision_ref(x, c), ladder [n] bool) on `device`.
+
+    A background mixture as in the other k-means tests - centres 2 randn, points centre + 0.5 randn, centroids centre + 0.3 randn,
+    everything + offset - and, for every pair (a, b, m) of kmeans_ladder_pairs,  c_b = c_a + 2^-m |c_a| u  (u a random unit vector)
+    with the points  x = c_a + lambda (c_b - c_a) + eta,  eta orthogonal to c_b - c_a, |eta| = 0.05 |c_b - c_a|,  whose gap between a
+    and b is |c_b - c_a|^2 |2 lambda - 1| whatever eta is.  lambda = 1/2 +- 2^-r for r in KM_LADDER_RUNGS and for the r that put the
+    relative gap gap / (|x| max|c|) on the geometric middle of each band of KM_BANDS the pair can reach (2^-2m |c_a| / max|c| is its
+    largest; the lowest band ends at 2 E / (|x| max|c|), taken at the pair's midpoint - a band that is empty there gets no rung).
+    Repetitions (each with its own eta): two of the rungs of KM_LADDER_RUNGS; of the bands' rungs 120 / (2 x the number of m = 2 pairs,
+    which alone reach the upper bands), so that every band gets 32 points from the ladder alone where it can: with a common offset
+    of 25 the background lies in one band ([3e-3, 2e-2): neighbouring centroids are 8 D apart and |x| |c| is 630 D) and only the rungs
+    on c_b's side, which is far from every other centroid, get past it; at K = 641 the pair behind centroid 640 loses rungs to
+    centroid 7 next to it.
+    Everything is built in float64 and rounded to fp32 once;
+    the reference works from the rounded values.  Ladder rows take what n allows (all of them when n is large enough), the
+    background the rest; decidable ladder rows from the narrowest bands sit at KM_EDGE_ROWS (those below n), the rest is shuffled."""
+    g = torch.Generator().manual_seed(1000003 * seed + 7919 * k + 31 * d + int(offset))
+    rn = lambda *shape: torch.randn(shape, generator=g, dtype=F64)   # noqa: E731
+    centres = 2 * rn(k, d)
+    c = centres + 0.3 * rn(k, d) + offset
+    pairs = kmeans_ladder_pairs(k)
+    for a, b, m in pairs:
+        u = rn(d)
+        c[b] = c[a] + 2.0 ** -m * c[a].norm() * u / u.norm()
+    c = c.float().to(F64)                                             # the centroids the points are placed between
+    cmax = c.norm(dim=1).max()
+    n_m2 = sum(1 for p in pairs if p[2] == 2)
+    reps = -(-120 // (2 * n_m2)) if pairs else 0
+    rows = []
+    for a, b, m in pairs:
+        w = c[b] - c[a]
+        mid = c[a] + 0.5 * w
+        scale = mid.norm() * cmax / (w @ w)                           # |2 lambda - 1| = relative gap x scale
+        low = float(2 * kmeans_key_bound(mid[None], c)[0] / (mid.norm() * cmax))
+        edges = [low * 1.02] + list(KM_BANDS) + [4 * KM_BANDS[-1]]
+        banded = [0.5 * math.sqrt(lo * hi) * float(scale) for lo, hi in zip(edges[:-1], edges[1:]) if lo < hi]
+        for o in 2 * [2.0 ** -r for r in KM_LADDER_RUNGS] + reps * [o for o in banded if o <= 0.5]:
+            for sign in (1.0, -1.0):
+                eta = rn(d)
+                eta = eta - (eta @ w) / (w @ w) * w
+                rows.append(c[a] + (0.5 + sign * o) * w + 0.05 * w.norm() * eta / eta.norm())
+    lad = torch.stack(rows) if rows else torch.zeros((0, d), dtype=F64)
+    lad = lad[torch.randperm(lad.shape[0], generator=g)[: (3 * n + 3) // 4]]     # at least a quarter of the rows is background
+    nb = n - lad.shape[0]
+    back = centres[torch.randint(0, k, (nb,), generator=g)] + 0.5 * rn(nb, d) + offset
+    x = torch.cat([lad, back]).float()
+    is_lad = torch.arange(n) < lad.shape[0]
+    # the reference is a matter of each row alone: taken before the placement, which needs it, and permuted with the rows
+    x, c32 = x.to(device), c.float().to(device)
+    ref = kmeans_decision_ref(x, c32)
+    band = kmeans_band(ref).cpu()
+    by_band = [torch.nonzero((band == bnd) & is_lad)[:, 0].tolist() for bnd in (1, 2, 3, 4)]
+    by_band = [rows_ for rows_ in by_band if rows_][:2]                # the two narrowest decidable bands the ladder has rows in
+    edge_pos = sorted({e % n for e in KM_EDGE_ROWS if -n <= e < n})
+    chosen = []
+    for j in range(len(edge_pos) if by_band else 0):                   # alternately from the two
+        rows_ = by_band[j % len(by_band)]
+        if j // len(by_band) < len(rows_):
+            chosen.append(rows_[j // len(by_band)])
+    taken = set(chosen)
+    rest = iter([i for i in torch.randperm(n, generator=g).tolist() if i not in taken])
+    at = dict(zip(edge_pos, chosen))
+    perm = torch.tensor([at[p] if p in at else next(rest) for p in range(n)], dtype=torch.int64)
+    is_lad = is_lad[perm].to(device)
+    perm = perm.to(device)
+    return x[perm].contiguous(), c32, {name: v[perm] for name, v in ref.items()}, is_lad
+
+
+def kmeans_ladder_conditions(ref, n):
+    """What the ladder must offer before any kernel runs, on the reference alone -> (counts of bands 1 .. 4, undecidable share,
+    band 1 is empty by construction).  Band 1, (2 E_i / (|x_i| max|c|), 1e-4), is empty where its lower end is no smaller than its
+    upper one for EVERY point: 2 E_i / (|x_i| max|c|) >= 2 gamma_(D+3) max|c| / |x_i|, about 6 gamma_(D+3) on these mixtures, which
+    passes 1e-4 between D = 256 and D = 768."""
+    band = kmeans_band(ref)
+    counts = [int((band == b).sum()) for b in (1, 2, 3, 4)]
+    lower = 2 * ref["e"] / ref["scale"]
+    empty = bool((lower[~ref["nan"]] >= KM_BANDS[0]).all())
+    return counts, float((band == 0).sum()) / max(n, 1), empty
+
+
+def kmeans_fp32_plain(x, c):
+    """The E step as a plain fp32 program on whatever device: arg-min of |c_j|^2 - 2 x_i.c_j with torch.argmin's order (NaN first)."""
+    key = (c * c).sum(1)[None, :] - 2 * (x @ c.T)
+    return torch.argmin(torch.where(torch.isnan(key), float("-inf"), key), dim=1)
+
+
+# The cases of tests/test_gpu_kmeans_assign_float64.py as (K, D, N, offset), here so that the CPU twin checks the ladder's conditions
+# and the plain fp32 emulation on every one.  2817 = 256 * 11 + 1 = 128 * 22 + 1: a last work-group of one point on every path.
+KM_N_STD = 11 * 256 + 1
+KM_SCREEN_SHAPES = [(40, 64), (300, 256), (17, 768), (2, 32), (320, 64)]
+KM_SCREENED_CASES = [(k, d, KM_N_STD, off) for k, d in KM_SCREEN_SHAPES for off in (0.0, 25.0)] + [(40, 64, 256, 0.0), (300, 256, 256, 25.0)]
+KM_EXACT_CASES = [(40, 64, KM_N_STD, 0.0), (300, 256, KM_N_STD, 0.0), (300, 256, KM_N_STD, 25.0), (641, 64, KM_N_STD, 0.0),
+                  (17, 768, KM_N_STD, 25.0), (40, 64, 255, 0.0), (40, 48, KM_N_STD, 0.0), (40, 16, KM_N_STD, 0.0), (1, 64, KM_N_STD, 0.0),
+                  (40, 64, 1, 0.0), (40, 64, 127, 0.0), (40, 64, 129, 25.0)]
+KM_TWO_LEVEL_CASES = KM_SCREENED_CASES + [(40, 64, 24 * 256 + 1, 0.0)]
+KM_SHADOW_CASES = KM_SCREENED_CASES + [(40, 64, 66003, 0.0)]
+KM_BLOCKS_CASES = [(k, 64, KM_N_STD, off) for k in (321, 641, 1280) for off in (0.0, 25.0)] + [(641, 256, KM_N_STD, 0.0)]
+KM_ALL_CASES = sorted(set(KM_EXACT_CASES + KM_TWO_LEVEL_CASES + KM_SHADOW_CASES + KM_BLOCKS_CASES))
+
+
+def kmeans_check_ladder(ref, n, d):
+    """The conditions a full-size ladder case (N >= 2048, K >= 2) is asserted to meet on the reference alone: every band holds at
+    least 32 decidable points - but for the lowest where it is empty by construction, which it is exactly from D = 768 on -
+    and at most 0.4 of the points are undecidable.  Returns (counts of bands 1 .. 4, undecidable share)."""
+    counts, undecidable, empty = kmeans_ladder_conditions(ref, n)
+    assert empty == (d >= 768), (d, empty)
+    assert all(cnt >= 32 for cnt in counts[1 if empty else 0:]) and undecidable <= 0.4, (counts, undecidable)
+    assert not empty or counts[0] == 0
+    return counts, undecidable

@@ -723,3 +723,121 @@ def test_usl_reg_ref_equals_the_oracle_and_names_the_other_outcome_at_the_edge()
     sel[3, 0] = 2.000002
     ref = R.usl_reg_ref(x0, sel, torch.tensor([1]), zero, 2, 1, 0.0, 1.0, True)
     assert ref[2].tolist() == [False] and ref[3][2].tolist() == [False]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the E step's decision rule and gap ladder (tests/test_gpu_kmeans_assign_float64.py)
+# ----------------------------------------------------------------------------------------------------------------------------
+def test_kmeans_key_bound_equals_a_brute_force_loop():
+    """E_i = gamma_(D+3) max_j (|c_j|^2 + 2 |x_i|.|c_j|) by explicit loops on a tiny case with signs, a NaN centroid row (left out of
+    the maximum) and a NaN point (E_i NaN)."""
+    g = torch.Generator().manual_seed(3)
+    x, c = torch.randn((4, 5), generator=g), torch.randn((3, 5), generator=g) * 3
+    c[1, 2] = float("nan")
+    x[3, 0] = float("nan")
+    e = R.kmeans_key_bound(x, c)
+    gam = (5 + 3) * 2.0 ** -24 / (1 - (5 + 3) * 2.0 ** -24)
+    for i in range(3):
+        best = 0.0
+        for j in (0, 2):
+            cc = sum(float(c[j, t]) ** 2 for t in range(5))
+            xc = sum(abs(float(x[i, t])) * abs(float(c[j, t])) for t in range(5))
+            best = max(best, cc + 2 * xc)
+        assert abs(float(e[i]) - gam * best) <= 1e-15 * gam * best
+    assert bool(torch.isnan(e[3])) and e.dtype == F64
+
+
+def test_kmeans_decision_rule_on_a_hand_worked_case():
+    """Centroids 0, 2, 2 (a duplicate of the second) and 10 on a line, D = 1, E_i = gamma_4 max (c^2 + 2 |x| c).  x = 0.5: gap
+    2.25 - 0.25, decidable, only label 0 passes.  x = 1 - 2^-22: distances differ by 2^-20, far below 2 E (E ~ 2.9e-5): labels 0, 1
+    and 2 pass (the band's rows are not all the same: any of them may win), 3 does not.  x = 3: the band holds the two duplicates
+    alone - label 1 passes, label 2 does not.  A NaN point: label 0 only.  A label outside [0, K) never passes."""
+    c = torch.tensor([[0.0], [2.0], [2.0], [10.0]])
+    x = torch.tensor([[0.5], [1 - 2.0 ** -22], [3.0], [float("nan")]])
+    ref = R.kmeans_decision_ref(x, c)
+    gam = float(R.gamma32(4))
+    assert torch.allclose(ref["e"][:3], gam * torch.tensor([110.0, 100 + 20 * (1 - 2.0 ** -22), 160.0], dtype=F64), rtol=1e-14, atol=0)
+    assert ref["ref"].tolist() == [0, 0, 1, 0] and ref["decidable"].tolist() == [True, False, False, False]
+    assert float(ref["gap"][0]) == 2.0 and float(ref["gap"][2]) == 0.0
+    assert abs(float(ref["gap"][1]) - 2.0 ** -20) < 1e-15 and ref["nan"].tolist() == [False, False, False, True]
+    assert ref["low"].tolist()[:3] == [0, 0, 1] and ref["same"].tolist()[:3] == [True, False, True]
+    assert abs(float(ref["rel"][0]) - 2.0 / (0.5 * 10.0)) < 1e-15
+    assert R.kmeans_band(ref).tolist() == [4, 0, 0, 0]
+    for labels, want in (([0, 0, 1, 0], [True] * 4), ([1, 1, 2, 1], [False, True, False, False]), ([2, 2, 3, 2], [False, True, False, False]),
+                         ([3, 3, 0, 3], [False] * 4), ([0, -1, 4, 0], [True, False, False, True])):
+        assert R.kmeans_rule_ok(x, c, torch.tensor(labels), ref).tolist() == want, labels
+    assert R.kmeans_rule_report("p", x, c, torch.tensor([0, 0, 1, 0]), ref) is None
+    msg = R.kmeans_rule_report("the path", x, c, torch.tensor([1, 3, 1, 5]), ref)
+    assert msg.startswith("the path: 1 decidable labels differ") and "1 undecidable" in msg and "1 NaN rows" in msg and "row 0 got 1" in msg
+    assert "gap 2.000000e+00" in msg and "band 4" in msg
+    # K = 1: every point decidable, whatever the distance
+    one = R.kmeans_decision_ref(x[:3], c[:1])
+    assert one["decidable"].tolist() == [True] * 3 and one["ref"].tolist() == [0] * 3
+
+
+def test_kmeans_ladder_pairs_cover_the_meeting_places():
+    assert R.kmeans_ladder_pairs(1) == [] and R.kmeans_ladder_pairs(2) == [(0, 1, 2)]
+    assert R.kmeans_ladder_pairs(17) == [(0, 1, 2), (15, 16, 5)]
+    assert R.kmeans_ladder_pairs(40) == [(0, 1, 2), (15, 16, 5), (3, 19, 8), (31, 32, 11), (38, 39, 2)]
+    assert R.kmeans_ladder_pairs(321)[-1] == (319, 320, 2) and len(R.kmeans_ladder_pairs(321)) == 5
+    assert R.kmeans_ladder_pairs(641)[4:] == [(639, 640, 2), (319, 320, 5), (5, 325, 2), (640, 7, 5)]      # 640 is made once: 7 from it
+    assert R.kmeans_ladder_pairs(1280)[4:] == [(1278, 1279, 2), (319, 320, 5), (5, 325, 2)]
+    for k in (2, 17, 40, 300, 320, 321, 641, 1280):
+        made = [b for _, b, _ in R.kmeans_ladder_pairs(k)]
+        assert len(set(made)) == len(made) and {m for _, _, m in R.kmeans_ladder_pairs(k)} <= {2, 5, 8, 11}
+
+
+@pytest.mark.parametrize("k,d,n,off", R.KM_ALL_CASES, ids=["K%d-D%d-N%d-off%d" % e for e in R.KM_ALL_CASES])
+def test_kmeans_gap_ladder_offers_what_the_gpu_cases_assume(k, d, n, off):
+    """Every case of the GPU module, on the CPU: inputs are fp32 and finite; a full-size case meets the band counts and the
+    undecidable share (kmeans_check_ladder) with ladder rows at both ends of the scale; decidable ladder rows of the two narrowest
+    bands sit at the work-group edges; every centroid pair is some point's two nearest; and a plain fp32 program - |c|^2 - 2 x c^T
+    and torch.argmin - obeys the decision rule at every point while differing from float64 at some undecidable ones: the rule
+    is neither vacuous nor stricter than fp32 arithmetic allows."""
+    x, c, ref, is_lad = R.kmeans_gap_ladder(k, d, n, off)
+    assert x.dtype == c.dtype == torch.float32 and x.shape == (n, d) and c.shape == (k, d)
+    assert bool(torch.isfinite(x).all()) and bool(torch.isfinite(c).all()) and not bool(ref["nan"].any())
+    again = R.kmeans_decision_ref(x, c, budget=k * d * 37)           # the reference went through the placement's permutation with its rows
+    assert all(torch.equal(ref[name], again[name]) for name in ("ref", "low", "same", "decidable")) and torch.allclose(ref["gap"], again["gap"])
+    band = R.kmeans_band(ref)
+    if n >= 2048 and k >= 2:
+        counts, share = R.kmeans_check_ladder(ref, n, d)
+        assert share >= 0.002                                         # and there ARE undecidable points
+        edges = [e % n for e in R.KM_EDGE_ROWS]
+        present = [b for b in (1, 2, 3, 4) if bool(((band == b) & is_lad).any())][:2]
+        assert bool(is_lad[edges].all()) and set(band[edges].tolist()) == set(present) and present[0] == (2 if d >= 768 else 1)
+        top2 = torch.topk(R.knn_dists(c, x), 2, dim=1, largest=False).indices.sort(dim=1).values
+        for a, b, _ in R.kmeans_ladder_pairs(k):
+            assert bool(((top2[:, 0] == min(a, b)) & (top2[:, 1] == max(a, b)) & is_lad).any()), (a, b)
+    lab = R.kmeans_fp32_plain(x, c)
+    msg = R.kmeans_rule_report("plain fp32", x, c, lab, ref)
+    assert msg is None, msg
+    differs = lab != ref["ref"]
+    assert not bool((differs & ref["decidable"]).any())
+    if n >= 2048 and k >= 2:
+        assert bool(differs.any())
+
+
+def test_kmeans_rule_on_scaled_inputs_and_nan_rows():
+    """The variants the GPU module derives from the (40, 64) ladder: inputs times 2^-40 and 2^40 (every quantity of the rule scales
+    exactly: same arg-min, same decidable set) and three NaN rows (label 0 there, every other row's reference untouched); the plain
+    fp32 program obeys the rule on each."""
+    x, c, ref, _ = R.kmeans_gap_ladder(40, 64, R.KM_N_STD, 0.0)
+    for power in (-40, 40):
+        xs, cs = x * 2.0 ** power, c * 2.0 ** power
+        rs = R.kmeans_decision_ref(xs, cs)
+        assert torch.equal(rs["ref"], ref["ref"]) and torch.equal(rs["decidable"], ref["decidable"])
+        for name in ("gap", "e"):                                     # (to rounding: a float64 matrix product need not repeat its order)
+            assert torch.allclose(rs[name], ref[name] * 4.0 ** power, rtol=1e-12, atol=0)
+        assert R.kmeans_rule_report("plain fp32", xs, cs, R.kmeans_fp32_plain(xs, cs), rs) is None
+    xn = x.clone()
+    xn[0, 3], xn[300], xn[-1, -1] = float("nan"), float("nan"), float("nan")
+    rn = R.kmeans_decision_ref(xn, c)
+    keep = ~rn["nan"]
+    assert rn["nan"].nonzero()[:, 0].tolist() == [0, 300, R.KM_N_STD - 1] and not bool(rn["decidable"][~keep].any())
+    assert all(torch.equal(rn[name][keep], ref[name][keep]) for name in ("ref", "decidable", "low", "same"))
+    assert all(torch.allclose(rn[name][keep], ref[name][keep], rtol=1e-12, atol=0) for name in ("gap", "e"))
+    lab = R.kmeans_fp32_plain(xn, c)
+    assert lab[~keep].tolist() == [0, 0, 0] and R.kmeans_rule_report("plain fp32", xn, c, lab, rn) is None
+    lab[300] = 1
+    assert "1 NaN rows are not 0" in R.kmeans_rule_report("plain fp32", xn, c, lab, rn)
