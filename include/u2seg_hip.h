@@ -833,6 +833,28 @@ int u2_sgd_clip_step(float* params, const float* grads, float* momentum_buf, con
                      const long long* chunk_begin, const int* chunk_len, int n_chunks, float* partial /*[n_chunks]*/,
                      const int* tensor_first_chunk /*[n_tensors + 1]*/, const float* wd_per_tensor, float lr, float momentum,
                      float clip, float grad_scale, void* stream);
+/* The same step with the solver's other options (solver/build.py:29-46 CLIP_TYPE / NORM_TYPE, :130-139 NESTEROV, :187-199
+ * BIAS_LR_FACTOR); u2_sgd_clip_step is what the default configuration keeps calling.  The arithmetic restates torch's, fp32:
+ *   norm pass (clip_mode 2, 3, 4 only): partial[c] = sum g^2 (2: L2), sum |g| (3: L1) or max |g| (4: inf) over chunk c, 1024
+ *     threads and float4 over head / body / tail as in the L2 pass, which IS that of u2_sgd_clip_step; sums in a fixed order,
+ *     no atomics, so every data-parallel rank forms the same coefficient.  Per tensor t: total = sqrt(sum) (2), sum (3) or
+ *     max (4) of its partials, times grad_scale;  coef = min(clip / (total + 1e-6f), 1)  - clip_grad_norm_(p, clip, norm_type),
+ *     per parameter.
+ *   step pass (always one launch), per element:
+ *     g' = g (coef grad_scale)                        clip_mode 2, 3, 4
+ *     g' = clamp(g grad_scale, -clip, +clip)          clip_mode 1: clip_grad_value_(p, clip) on the averaged gradient
+ *     g' = g grad_scale                               clip_mode 0
+ *     d = g' + wd[t] p;   m' = momentum m + d;   u = nesterov ? d + momentum m' : m';   p' = p - lr_t u,
+ *     lr_t = lr_class_per_tensor[t] ? lr_bias : lr    (the two rates a yacs config can form: BASE_LR, BASE_LR BIAS_LR_FACTOR)
+ *   A zero-filled momentum arena gives torch's first-step rule buf = d, with Nesterov too (u = d + momentum d, as torch).
+ *   Non-finite gradients: the inf norm's fmaxf drops a NaN where torch's max propagates it (the clamp of mode 1 keeps it).
+ * clip_mode outside 0..4, or a clip <= 0 with clip_mode != 0, is refused (-1): "no clipping" is mode 0. */
+int u2_sgd_step_opts(float* params, const float* grads, float* momentum_buf, const int* chunk_tensor,
+                     const long long* chunk_begin, const int* chunk_len, int n_chunks, float* partial /*[n_chunks]*/,
+                     const int* tensor_first_chunk /*[n_tensors + 1]*/, const float* wd_per_tensor,
+                     const int* lr_class_per_tensor /* 0: lr, 1: lr_bias */, float lr, float lr_bias, float momentum,
+                     int nesterov, int clip_mode /* 0 none, 1 value, 2 L2, 3 L1, 4 inf */, float clip, float grad_scale,
+                     void* stream);
 
 /* ---- k-means over DINO embeddings (kmeans.hip): u2seg/Instance_Clustering/shared/utils/nn_utils.py:304-379 ---- */
 /* labels[i] = argmin_j |x_i - c_j|^2 (first minimum).  workspace: u2_kmeans_assign_workspace_floats(N, D, K) floats (contents

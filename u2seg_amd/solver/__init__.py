@@ -1,3 +1,3 @@
-from .build import FlatSGD, WarmupMultiStepLR, build_lr_scheduler, build_optimizer
+from .build import FlatSGD, WarmupLR, WarmupMultiStepLR, build_lr_scheduler, build_optimizer
 
-__all__ = ["FlatSGD", "WarmupMultiStepLR", "build_lr_scheduler", "build_optimizer"]
+__all__ = ["FlatSGD", "WarmupLR", "WarmupMultiStepLR", "build_lr_scheduler", "build_optimizer"]

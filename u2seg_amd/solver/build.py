@@ -3,8 +3,11 @@
 All trainable tensors live in one flat fp32 arena (parameters, gradients and momentum are views), so that
  * data-parallel gradient exchange is a handful of large RCCL all-reduces over xGMI instead of 248 small ones,
  * per-parameter L2 clipping (CLIP_TYPE "norm", applied per tensor as in solver/build.py:36-37,63-73) + SGD with
-   momentum and weight decay is two kernel launches (u2_sgd_clip_step)."""
+   momentum and weight decay is two kernel launches (u2_sgd_clip_step).
+The solver's other options - CLIP_TYPE value, NORM_TYPE 1 / inf, NESTEROV, BIAS_LR_FACTOR - go through u2_sgd_step_opts, the same
+stream with the options as kernel arguments; the default configuration keeps the two launches of u2_sgd_clip_step."""
 import bisect
+import math
 
 import torch
 import torch.distributed as dist
@@ -13,11 +16,43 @@ from .. import _hip
 from ..layers.modules import BatchNorm2d, GroupNorm
 
 CHUNK = 1 << 16
+CLIP_NONE, CLIP_VALUE, CLIP_L2, CLIP_L1, CLIP_INF = range(5)   # clip_mode of u2_sgd_step_opts (include/u2seg_hip.h)
+
+
+def clip_mode_of(clip_type, norm_type, clip_value):
+    """SOLVER.CLIP_GRADIENTS.{CLIP_TYPE, NORM_TYPE, CLIP_VALUE} -> clip_mode (solver/build.py:29-46).  A CLIP_VALUE of 0 is this
+    package's "no clipping" (what build_optimizer hands over with CLIP_GRADIENTS.ENABLED False)."""
+    if clip_type not in ("value", "norm"):
+        raise ValueError("SOLVER.CLIP_GRADIENTS.CLIP_TYPE must be 'value' or 'norm', got %r" % (clip_type,))
+    if float(clip_value) < 0:
+        raise ValueError("SOLVER.CLIP_GRADIENTS.CLIP_VALUE must not be negative, got %r" % (clip_value,))
+    if float(clip_value) == 0:
+        return CLIP_NONE
+    if clip_type == "value":
+        return CLIP_VALUE
+    try:
+        nt = float(norm_type)   # yaml writes the infinity norm as .inf or as the string "inf": float() reads both
+    except (TypeError, ValueError):
+        nt = None
+    mode = {1.0: CLIP_L1, 2.0: CLIP_L2, math.inf: CLIP_INF}.get(nt)
+    if mode is None:
+        raise ValueError("SOLVER.CLIP_GRADIENTS.NORM_TYPE must be 1, 2 or inf, got %r: a general p-norm needs powf per element and "
+                         "has no derived error bound here" % (norm_type,))
+    return mode
 
 
 class FlatSGD:
     def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, weight_decay_norm=0.0, weight_decay_bias=None,
-                 clip_value=0.0, bucket_bytes=64 << 20):
+                 clip_value=0.0, bucket_bytes=64 << 20, nesterov=False, clip_type="norm", norm_type=2.0, bias_lr_factor=1.0):
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")   # torch.optim.SGD's own words
+        self.nesterov = bool(nesterov)
+        self.clip_mode = clip_mode_of(clip_type, norm_type, clip_value)
+        # the bias override carries the learning rate too (solver/build.py:187-199): BASE_LR * BIAS_LR_FACTOR, in doubles, for
+        # every parameter literally named "bias" - a normalisation layer's included
+        self.has_bias_lr = bias_lr_factor is not None and float(bias_lr_factor) != 1.0
+        self.initial_lr_bias = lr * bias_lr_factor if self.has_bias_lr else lr
+        self.lr_bias = self.initial_lr_bias
         # per-parameter hyper-parameters by the reference's rule (solver/build.py:218-236 get_default_optimizer_params): the
         # module tree is walked in named_modules order, a normalisation layer's parameters take WEIGHT_DECAY_NORM, and the
         # legacy bias override - applied after it, to every parameter literally named "bias" - WEIGHT_DECAY_BIAS
@@ -25,7 +60,8 @@ class FlatSGD:
         # hands weight_decay to get_default_optimizer_params (solver/build.py:123-129), torch fills it in from the SGD default -
         # and gains a "weight_decay" entry only where an override applied.  So a parameter without override (key None) and one
         # whose override EQUALS the default still sit in different groups, and all overridden parameters of one value share one.
-        wd_of, key_of, seen = {}, {}, set()
+        # With BIAS_LR_FACTOR != 1 the dict's "lr" differs too, so the key is (lr, weight-decay override or None).
+        wd_of, key_of, bias_of, seen = {}, {}, {}, set()
         for mod in model.modules():
             for pname, p in mod.named_parameters(recurse=False):
                 if not p.requires_grad or id(p) in seen:
@@ -36,7 +72,8 @@ class FlatSGD:
                     key = float(weight_decay_norm)
                 if pname == "bias" and weight_decay_bias is not None:
                     key = float(weight_decay_bias)
-                key_of[id(p)] = key
+                bias_of[id(p)] = int(self.has_bias_lr and pname == "bias")
+                key_of[id(p)] = (self.initial_lr_bias if bias_of[id(p)] else lr, key)
                 wd_of[id(p)] = float(weight_decay) if key is None else key
         self.params = [p for p in model.parameters() if p.requires_grad]
         assert len(self.params) == len(wd_of)
@@ -44,8 +81,11 @@ class FlatSGD:
         # appearance (reduce_param_groups, solver/build.py:255-279); torch numbers the parameters group after group.  That
         # numbering is the key of a reference checkpoint's optimizer state (state_dict / load_state_dict below).
         group_keys = list(dict.fromkeys(key_of[id(p)] for p in self.params))
-        self.group_wd = [float(weight_decay) if k is None else k for k in group_keys]
+        self.group_wd = [float(weight_decay) if k is None else k for _, k in group_keys]
         self.group_members = [[i for i, p in enumerate(self.params) if key_of[id(p)] == k] for k in group_keys]
+        # 1: the group's rate is lr_bias.  (A group never mixes the two: its key holds the rate.  With a base rate of 0 both
+        # rates are 0 and the reference merges them; the class of the first member then serves all.)
+        self.group_lr_class = [bias_of[id(self.params[m[0]])] for m in self.group_members]
         dev = self.params[0].device
         total = sum(p.numel() for p in self.params)
         self.total = total
@@ -72,6 +112,7 @@ class FlatSGD:
         self.chunk_begin = torch.tensor(chunk_begin, dtype=torch.int64, device=dev)
         self.chunk_len = torch.tensor(chunk_len, dtype=torch.int32, device=dev)
         self.wd = torch.tensor(wds, dtype=torch.float32, device=dev)
+        self.lr_class = torch.tensor([bias_of[id(p)] for p in self.params], dtype=torch.int32, device=dev)
         first_chunk.append(len(chunk_tensor))
         self.first_chunk = torch.tensor(first_chunk, dtype=torch.int32, device=dev)
         self.partial = torch.zeros(len(chunk_tensor), dtype=torch.float32, device=dev)
@@ -162,9 +203,16 @@ class FlatSGD:
         from ..layers.functional import join_all_streams
 
         join_all_streams()
-        _hip.call("u2_sgd_clip_step", self.flat_param, self.flat_grad, self.flat_mom, self.chunk_tensor, self.chunk_begin,
-                  self.chunk_len, self.chunk_tensor.numel(), self.partial, self.first_chunk, self.wd, float(self.lr),
-                  float(self.momentum), float(self.clip_value), float(grad_scale))
+        if not self.nesterov and not self.has_bias_lr and self.clip_mode in (CLIP_NONE, CLIP_L2):
+            # every option at its default (clip_value 0 = no clipping): the two launches the shipped configs have always run
+            _hip.call("u2_sgd_clip_step", self.flat_param, self.flat_grad, self.flat_mom, self.chunk_tensor, self.chunk_begin,
+                      self.chunk_len, self.chunk_tensor.numel(), self.partial, self.first_chunk, self.wd, float(self.lr),
+                      float(self.momentum), float(self.clip_value), float(grad_scale))
+        else:
+            _hip.call("u2_sgd_step_opts", self.flat_param, self.flat_grad, self.flat_mom, self.chunk_tensor, self.chunk_begin,
+                      self.chunk_len, self.chunk_tensor.numel(), self.partial, self.first_chunk, self.wd, self.lr_class,
+                      float(self.lr), float(self.lr_bias), float(self.momentum), int(self.nesterov), self.clip_mode,
+                      float(self.clip_value), float(grad_scale))
         self.refresh_layouts()
 
     def _register_layout(self, param, key, entry):
@@ -213,10 +261,12 @@ class FlatSGD:
         reads what a reference trainer wrote.  (Before the first step torch has no state entries; here the buffers exist
         from the start and are written as zeros, which is what torch's first step computes from: buf = grad.)"""
         groups, state, n = [], {}, 0
-        for wd, members in zip(self.group_wd, self.group_members):
-            groups.append({"lr": float(self.lr), "momentum": float(self.momentum), "dampening": 0, "weight_decay": wd,
-                           "nesterov": False, "maximize": False, "foreach": True, "differentiable": False, "fused": None,
-                           "initial_lr": float(self.base_lr), "params": list(range(n, n + len(members)))})
+        for wd, members, cls in zip(self.group_wd, self.group_members, self.group_lr_class):
+            groups.append({"lr": float(self.lr_bias if cls else self.lr), "momentum": float(self.momentum), "dampening": 0,
+                           "weight_decay": wd, "nesterov": self.nesterov, "maximize": False, "foreach": True,
+                           "differentiable": False, "fused": None,
+                           "initial_lr": float(self.initial_lr_bias if cls else self.base_lr),
+                           "params": list(range(n, n + len(members)))})
             for i in members:
                 off = self.param_offset[i]
                 p = self.params[i]
@@ -233,15 +283,40 @@ class FlatSGD:
         if [len(g["params"]) for g in groups] != [len(m) for m in self.group_members]:
             raise ValueError("loaded state dict has a different number of parameter groups / parameters per group: %s vs %s"
                              % ([len(g["params"]) for g in groups], [len(m) for m in self.group_members]))
-        lrs = {float(g["lr"]) for g in groups}
-        assert len(lrs) == 1, "per-group learning rates (BIAS_LR_FACTOR != 1) are not implemented"
-        self.lr = lrs.pop()
+        # groups are matched by position; the kernel knows two rates, the base class's and the bias class's (BIAS_LR_FACTOR)
+        def rate_of(key, cls):
+            found = {}
+            for gi, g in enumerate(groups):
+                if self.group_lr_class[gi] == cls:
+                    found.setdefault(float(g[key]), []).append(gi)
+            if len(found) > 1:
+                raise ValueError("param_groups %s hold different '%s' values %s within the %s class: this optimizer steps with two "
+                                 "rates, SOLVER.BASE_LR and SOLVER.BASE_LR * SOLVER.BIAS_LR_FACTOR%s"
+                                 % (sorted(found.values()), key, sorted(found), "bias" if cls else "base",
+                                    "" if self.has_bias_lr else " (built with BIAS_LR_FACTOR 1: one rate)"))
+            return next(iter(found), None)
+
+        flags = {(bool(g.get("nesterov", False)), float(g.get("momentum", self.momentum))) for g in groups}
+        if len(flags) > 1:
+            raise ValueError("param_groups differ in 'nesterov' / 'momentum' %s: SOLVER.NESTEROV and SOLVER.MOMENTUM hold for all"
+                             % sorted(flags))
+        for gi, g in enumerate(groups):
+            for key in ("dampening", "maximize"):
+                if g.get(key, 0):
+                    raise ValueError("param_groups[%d]['%s'] = %r: not implemented (the reference's build_optimizer never sets it)"
+                                     % (gi, key, g[key]))
+        nesterov, momentum = flags.pop()
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        lr, lr_bias = rate_of("lr", 0), rate_of("lr", 1)
+        self.nesterov = nesterov
+        self.lr = self.lr if lr is None else lr
+        self.lr_bias = self.lr if not self.has_bias_lr else (self.lr_bias if lr_bias is None else lr_bias)
         if all("initial_lr" in g for g in groups):  # written once a torch LR scheduler has touched the optimizer
-            base = {float(g["initial_lr"]) for g in groups}
-            assert len(base) == 1, base
-            self.base_lr = base.pop()
+            base, base_bias = rate_of("initial_lr", 0), rate_of("initial_lr", 1)
+            self.base_lr = self.base_lr if base is None else base
+            self.initial_lr_bias = self.base_lr if not self.has_bias_lr else (self.initial_lr_bias if base_bias is None else base_bias)
         for gi, (g, members) in enumerate(zip(groups, self.group_members)):
-            assert not g.get("nesterov", False) and not g.get("dampening", 0) and not g.get("maximize", False), g
             self.momentum = float(g.get("momentum", self.momentum))
             wd = float(g.get("weight_decay", self.group_wd[gi]))
             if wd != self.group_wd[gi]:
@@ -265,12 +340,13 @@ def build_optimizer(cfg, model):
     s = cfg.SOLVER
     clip = 0.0
     if s.CLIP_GRADIENTS.ENABLED:
-        assert s.CLIP_GRADIENTS.CLIP_TYPE == "norm" and float(s.CLIP_GRADIENTS.NORM_TYPE) == 2.0, \
-            "only per-parameter L2 norm clipping (the U2Seg setting) is implemented"
         clip = float(s.CLIP_GRADIENTS.CLIP_VALUE)
-    assert float(s.BIAS_LR_FACTOR) == 1.0 and not s.NESTEROV
+        if clip <= 0:
+            raise ValueError("SOLVER.CLIP_GRADIENTS.CLIP_VALUE must be positive with CLIP_GRADIENTS.ENABLED, got %r" % (clip,))
     return FlatSGD(model, lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY,
-                   weight_decay_norm=s.WEIGHT_DECAY_NORM, weight_decay_bias=s.WEIGHT_DECAY_BIAS, clip_value=clip)
+                   weight_decay_norm=s.WEIGHT_DECAY_NORM, weight_decay_bias=s.WEIGHT_DECAY_BIAS, clip_value=clip,
+                   nesterov=s.NESTEROV, clip_type=s.CLIP_GRADIENTS.CLIP_TYPE, norm_type=s.CLIP_GRADIENTS.NORM_TYPE,
+                   bias_lr_factor=s.BIAS_LR_FACTOR)
 
 
 class WarmupMultiStepLR:
@@ -316,9 +392,104 @@ class WarmupMultiStepLR:
         self.resume_at(state["last_iter"] if "last_iter" in state else state["last_epoch"])
 
 
+def multistep_schedule(milestones, gamma, max_iter):
+    """where in [0, 1] -> gamma^(#milestones passed): fvcore's MultiStepParamScheduler with values [gamma^k]
+    (solver/build.py:289-301), whose iteration is int((where + 1e-6) * max_iter)."""
+    milestones = sorted(milestones)
+    return lambda where: gamma ** bisect.bisect_right(milestones, int((where + 1e-6) * max_iter))
+
+
+def cosine_schedule(end):
+    """where -> end + (1 - end) (1 + cos(pi where)) / 2: fvcore's CosineParamScheduler(1, end) (solver/build.py:302-305)."""
+    return lambda where: end + 0.5 * (1.0 - end) * (1.0 + math.cos(math.pi * where))
+
+
+class WarmupLR:
+    """The reference's LRMultiplier over a WarmupParamScheduler (solver/lr_scheduler.py:22-58,61-125): one multiplier per
+    iteration, and every group's rate is its initial rate times it - optimizer.lr = base_lr * m, and optimizer.lr_bias =
+    optimizer.initial_lr_bias * m where the optimizer has a bias class (BIAS_LR_FACTOR), both in Python doubles as torch's
+    scheduler forms them.  `schedule` maps where = iteration / max_iter to the main schedule's value (multistep_schedule,
+    cosine_schedule).  The warm-up, restated from lr_scheduler.py:46-58 and the composite it builds:
+        start = warmup_factor * schedule(0)
+        end   = schedule(0) if rescale_interval else schedule(warmup_length),  warmup_length = min(warmup_iters / max_iter, 1)
+        iteration < warmup_iters:  "constant": start;  "linear": end a + start (1 - a),  a = where / warmup_length
+        afterwards:                schedule(where), or schedule((where - warmup_length) / (1 - warmup_length)) when rescaled
+    Which part serves an iteration is decided on the integers (iteration < warmup_iters) where fvcore's composite compares
+    where + 1e-6 with warmup_length: the same below a million iterations.  fvcore is not available to pin these values against;
+    tests/test_solver_options_host.py checks them against numbers worked out by hand from the lines above."""
+
+    def __init__(self, optimizer, base_lr, max_iter, schedule, warmup_factor, warmup_iters, warmup_method="linear",
+                 rescale_interval=False):
+        if warmup_method not in ("linear", "constant"):
+            raise ValueError("SOLVER.WARMUP_METHOD must be 'linear' or 'constant', got %r" % (warmup_method,))
+        self.optimizer, self.base_lr, self.max_iter, self.schedule = optimizer, base_lr, int(max_iter), schedule
+        self.warmup_factor, self.warmup_iters = warmup_factor, min(int(warmup_iters), int(max_iter))
+        self.warmup_method, self.rescale_interval = warmup_method, bool(rescale_interval)
+        self.last_iter = 0
+        self._apply()
+
+    def multiplier(self, it):
+        where = it / self.max_iter
+        length = min(self.warmup_iters / self.max_iter, 1.0)
+        if it < self.warmup_iters:
+            start = self.warmup_factor * self.schedule(0.0)
+            if self.warmup_method == "constant":
+                return start
+            end = self.schedule(0.0) if self.rescale_interval else self.schedule(length)
+            a = where / length
+            return end * a + start * (1 - a)
+        if self.rescale_interval and length < 1.0:
+            where = (where - length) / (1 - length)
+        return self.schedule(where)
+
+    def get_lr(self, it):
+        return self.base_lr * self.multiplier(it)
+
+    def _apply(self):
+        m = self.multiplier(self.last_iter)
+        self.optimizer.lr = self.base_lr * m
+        if getattr(self.optimizer, "has_bias_lr", False):
+            self.optimizer.lr_bias = self.optimizer.initial_lr_bias * m
+
+    def step(self):
+        self.last_iter += 1
+        self._apply()
+
+    def resume_at(self, iteration):
+        """Continue the schedule at `iteration` (the next step to run), as WarmupMultiStepLR.resume_at."""
+        self.last_iter = int(iteration)
+        self._apply()
+
+    def state_dict(self):
+        # what LRMultiplier.state_dict writes: the groups' initial rates and the position
+        opt = self.optimizer
+        classes = getattr(opt, "group_lr_class", [0])
+        base_lrs = [opt.initial_lr_bias if c and getattr(opt, "has_bias_lr", False) else self.base_lr for c in classes]
+        return {"last_iter": self.last_iter, "last_epoch": self.last_iter, "base_lrs": base_lrs}
+
+    def load_state_dict(self, state):
+        self.resume_at(state["last_iter"] if "last_iter" in state else state["last_epoch"])
+
+
 def build_lr_scheduler(cfg, optimizer):
     s = cfg.SOLVER
-    assert s.LR_SCHEDULER_NAME == "WarmupMultiStepLR"
-    steps = [x for x in s.STEPS if x <= s.MAX_ITER]
-    return WarmupMultiStepLR(optimizer, s.BASE_LR, steps, s.GAMMA, s.WARMUP_FACTOR, min(s.WARMUP_ITERS, s.MAX_ITER),
-                             s.WARMUP_METHOD)
+    name = s.LR_SCHEDULER_NAME
+    warmup_iters = min(s.WARMUP_ITERS, s.MAX_ITER)
+    rescale = bool(s.RESCALE_INTERVAL)
+    if name == "WarmupMultiStepLR":
+        steps = [x for x in s.STEPS if x <= s.MAX_ITER]
+        if s.WARMUP_METHOD == "linear" and not rescale and not getattr(optimizer, "has_bias_lr", False):
+            # the shipped configs: the class they have always run, and its values to the bit
+            return WarmupMultiStepLR(optimizer, s.BASE_LR, steps, s.GAMMA, s.WARMUP_FACTOR, warmup_iters, s.WARMUP_METHOD)
+        schedule = multistep_schedule(steps, s.GAMMA, s.MAX_ITER)
+    elif name == "WarmupCosineLR":
+        end = s.BASE_LR_END / s.BASE_LR
+        if not 0.0 <= end <= 1.0:
+            raise ValueError("SOLVER.BASE_LR_END / SOLVER.BASE_LR must lie in [0, 1], got %r" % (end,))
+        schedule = cosine_schedule(end)
+    elif name == "WarmupStepWithFixedGammaLR":
+        raise ValueError("SOLVER.LR_SCHEDULER_NAME 'WarmupStepWithFixedGammaLR' is not implemented: its step rule lives in fvcore "
+                         "(StepWithFixedGammaParamScheduler), which is not available to pin a restatement against")
+    else:
+        raise ValueError("Unknown SOLVER.LR_SCHEDULER_NAME: %r" % (name,))
+    return WarmupLR(optimizer, s.BASE_LR, s.MAX_ITER, schedule, s.WARMUP_FACTOR, warmup_iters, s.WARMUP_METHOD, rescale)
