@@ -314,6 +314,28 @@ int u2_add_n(const void* a, const void* b, const void* c, const void* d, void* o
  * (engine/train_loop.py:479-521 leaves that accumulation to torch). */
 int u2_wgrad_permute_add(const float* scratch, float* grad, int N, int Cin, int T, int Cp, void* stream);
 
+/* ---- training through FrozenBatchNorm2d (frozen.hip) --------------------------------------------
+ * layers/batch_norm.py:13-100: y * scale + shift with fixed scale = weight * rsqrt(running_var + eps).  The scale is folded into
+ * the weights of the convolution in front of the norm, W'[n][c][t] = bf16(w[n][c][t] * s[n]) (one fp32 product, one rounding to
+ * bf16), the shift rides as the conv epilogue's fp32 bias.  One launch writes both kernel layouts of W' for a whole table of
+ * layers: fwd = [N][T][Cp] (u2_weight_layout mode 0), dgrad = [Cp][T][Npad] with the taps reversed (mode 1); either may be NULL.
+ * Output channels N..Npad-1 of dgrad are written as zeros; input channels Cin..Cp-1 of both are NOT written (the caller
+ * allocates the layouts zeroed once).  Cp and Npad must be even (bf16 pairs are stored; an odd entry is skipped).  An entry owns ceil(Npad / 64) * ceil(Cin * T / 64) work-groups from block_begin on. */
+typedef struct U2FrozenFoldDesc {
+  const float* w;   /* [N][Cin][T] fp32 master weights */
+  const float* s;   /* [N] fp32 scale */
+  void* fwd;        /* bf16 [N][T][Cp] or NULL */
+  void* dgrad;      /* bf16 [Cp][T][Npad] or NULL */
+  int N, Cin, T, Cp, Npad;
+  int block_begin;  /* prefix sum of the entries' work-group counts */
+  int reserved[2];
+} U2FrozenFoldDesc;
+int u2_frozen_fold(const U2FrozenFoldDesc* table, int n_entries, int total_blocks, void* stream);
+/* The transpose of the fold: grad[n][c][t] += s[n] * scratch[n][t][c] for n < N, c < Cin - the kernel-layout weight gradient of W'
+ * (u2_conv_wgrad, fp32 [Npad][T][Cp]) scaled (one fp32 rounding) and accumulated (one more) into the parameter's own gradient
+ * storage fp32 [N][Cin][T].  -2: T * (Cp + 1) floats exceed 64 KB of LDS (nothing launched). */
+int u2_frozen_wgrad_scale_add(const float* scratch, const float* s, float* grad, int N, int Cin, int T, int Cp, void* stream);
+
 /* ---- pooling / resampling (pool_resize.hip) ----------------------------------------------------
  * backbone/resnet.py:358 (max_pool2d 3x3 s2 p1), backbone/fpn.py:153-155 (nearest x2 + add),
  * meta_arch/semantic_seg.py:206-211 (bilinear x2), meta_arch/rcnn.py:223-234 (normalise + pad) feeding the stem. */

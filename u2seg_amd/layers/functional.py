@@ -10,8 +10,8 @@ Every function here launches HIP kernels; none has a CPU or ATen compute fallbac
 
 This module holds the differentiable layers whose backward passes talk to each other through layers/deferred.py (conv, stem,
 norms, pooling, resampling, fan-out, ROIAlign) and is the one name the rest of the package calls the layers by: the zero pool and
-the weight layouts (weights.py), the streams (streams.py), the head losses (losses.py) and the selection wrappers (select.py)
-are imported here by name.  Functions are re-exported, mutable state never: a switch lives in exactly one module.
+the weight layouts (weights.py), the streams (streams.py), the head losses (losses.py), the selection wrappers (select.py) and
+the FrozenBN training path (frozen.py) are imported here by name.  Functions are re-exported, mutable state never: a switch lives in exactly one module.
 """
 import collections
 import ctypes
@@ -24,6 +24,7 @@ from torch.autograd import Function
 
 from .. import _hip
 from . import deferred, streams
+from .frozen import affine_relu_max_pool_train, frozen_conv2d  # noqa: F401
 from .losses import (BOX_REG_LOSS_KINDS, box_reg_l1_loss, box_reg_loss, box_reg_loss_cls, count_labels_i8, mask_predict_bce_loss,  # noqa: F401
                      mask_predict_prob, rpn_losses, sem_seg_loss, sigmoid_cross_entropy, softmax_cross_entropy)
 from .select import (_TOPK_MAX_K, _topk_rows_sorted, _topk_segments, apply_deltas, apply_deltas_cls, assign_levels, batched_nms,  # noqa: F401

@@ -92,6 +92,36 @@ class FrozenBatchNorm2d(nn.Module):
         self.register_buffer("bias", torch.zeros(num_features))
         self.register_buffer("running_mean", torch.zeros(num_features))
         self.register_buffer("running_var", torch.ones(num_features) - eps)
+        # None on a module born frozen (no state-dict entry); a converted module keeps the BatchNorm's counter (batch_norm.py:43,127)
+        self.register_buffer("num_batches_tracked", None)
+
+    @classmethod
+    def from_batch_norm(cls, bn):
+        """The frozen twin of a BatchNorm2d (SyncBN / BN): what `bn` computes in eval mode, for good.  The affine pair becomes
+        buffers holding copies; the running statistics and the batch counter (pending forwards counted in first) are the
+        BatchNorm's own tensors, so the new module sits on the same device; eps is kept."""
+        bn._flush_batches()
+        frozen = cls(bn.num_features, eps=bn.eps)
+        state = {"weight": bn.weight.detach().clone(), "bias": bn.bias.detach().clone(), "running_mean": bn.running_mean,
+                 "running_var": bn.running_var, "num_batches_tracked": bn.num_batches_tracked}
+        for name, tensor in state.items():
+            setattr(frozen, name, tensor)   # registered buffer names: nn.Module files them as buffers
+        return frozen
+
+    @classmethod
+    def convert_frozen_batchnorm(cls, module):
+        """Semantics of layers/batch_norm.py:101-133: a BatchNorm2d comes back as its frozen twin; in any other module every
+        BatchNorm2d below it is replaced on its parent, and the module itself is returned."""
+        if isinstance(module, BatchNorm2d):
+            return cls.from_batch_norm(module)
+        slots = [(parent, name, child) for parent in module.modules() for name, child in parent.named_children()
+                 if isinstance(child, BatchNorm2d)]
+        twins = {}   # a layer registered under two parents stays one layer
+        for parent, name, bn in slots:
+            if id(bn) not in twins:
+                twins[id(bn)] = cls.from_batch_norm(bn)
+            setattr(parent, name, twins[id(bn)])
+        return module
 
     def eval_scale_shift(self):
         scale = self.weight * torch.rsqrt(self.running_var + self.eps)
@@ -164,6 +194,9 @@ class Conv2d(nn.Module):
             assert residual is None
             y = F.conv2d(x, self.weight, None, self.stride, self.padding, relu=False)
             return F.group_norm_act(y, norm.weight, norm.bias, norm.num_groups, relu, norm.eps)
+        if isinstance(norm, FrozenBatchNorm2d) and torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad):
+            # FrozenBN on the training path: the arithmetic of the folded inference path below, under autograd (layers/frozen.py)
+            return F.frozen_conv2d(self, x, residual, relu)
         # fixed statistics (eval-mode BN / FrozenBN): y * scale + shift is an affine map per output channel
         if not torch.is_grad_enabled():
             folded = self._folded_eval()

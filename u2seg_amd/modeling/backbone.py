@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from ..layers import Conv2d, ShapeSpec, c2_msra_fill, c2_xavier_fill, get_norm
+from ..layers.modules import FrozenBatchNorm2d
 from ..layers import functional as F
 from ..utils.registry import Registry
 
@@ -34,6 +35,13 @@ class Backbone(nn.Module):
         }
 
 
+def _freeze_block(block):
+    """Semantics of CNNBlockBase.freeze (layers/blocks.py:43-55): no parameter of the block trains, its BatchNorm layers become FrozenBatchNorm2d."""
+    block.requires_grad_(False)
+    block.frozen = True
+    return FrozenBatchNorm2d.convert_frozen_batchnorm(block)
+
+
 class BasicStem(nn.Module):
     """conv7x7 s2 (3 -> 64) + norm + ReLU + maxpool 3x3 s2 (resnet.py:330-359)."""
 
@@ -43,6 +51,10 @@ class BasicStem(nn.Module):
         self.conv1 = Conv2d(in_channels, out_channels, kernel_size=7, stride=2, padding=3, bias=False,
                             norm=get_norm(norm, out_channels))
         c2_msra_fill(self.conv1)
+        self.frozen = False
+
+    def freeze(self):
+        return _freeze_block(self)
 
     def forward(self, images, pixel_mean, pixel_std, padded_hw):
         conv, norm = self.conv1, self.conv1.norm
@@ -59,6 +71,12 @@ class BasicStem(nn.Module):
             scale, shift = norm.eval_scale_shift()
             if fuse and not (torch.is_grad_enabled() and y.requires_grad):
                 return F.affine_relu_max_pool(y, scale.float(), shift.float())
+            if isinstance(norm, FrozenBatchNorm2d) and torch.is_grad_enabled() and y.requires_grad:
+                # a trainable stem in front of a FrozenBN: the same pass under autograd (the scale reaches the weight gradient)
+                if not fuse:
+                    raise NotImplementedError("a trainable stem with FrozenBN needs the one-pass stem tail (channels / 8 dividing "
+                                              "256, U2_STEM_TAIL_FUSE on)")
+                return F.affine_relu_max_pool_train(y, scale.float(), shift.float())
             x = F.affine_act(y, scale.float(), shift.float(), None, True)
         return F.max_pool_3x3_s2(x)
 
@@ -71,6 +89,7 @@ class BottleneckBlock(nn.Module):
         super().__init__()
         assert num_groups == 1 and dilation == 1, "grouped / dilated bottlenecks are not used by the U2Seg configs"
         self.in_channels, self.out_channels, self.stride = in_channels, out_channels, stride
+        self.frozen = False
         self.third_handle = False  # set by ResNet on the last block of a stage that is also a backbone output
         self.first_in_stage = True  # ResNet clears it on every block but the first of its stage
         if in_channels != out_channels:
@@ -89,6 +108,9 @@ class BottleneckBlock(nn.Module):
             if layer is not None:
                 c2_msra_fill(layer)
 
+    def freeze(self):
+        return _freeze_block(self)
+
     def forward(self, x):
         # the block input feeds conv1 and the shortcut; when the previous block handed out two autograd handles of it
         # (functional.batch_norm_act(twin=True)) the two gradients meet inside that block's BN backward kernel
@@ -99,7 +121,9 @@ class BottleneckBlock(nn.Module):
         # out += shortcut; relu_.  The last block of a stage that is also a backbone output hands out a third handle
         # at inference the shortcut buffer is given up: a projection shortcut is this block's own tensor, an identity shortcut
         # is the previous block's output, which inside a stage has no reader but this block
-        owned = not torch.is_grad_enabled() and not self.training and (self.shortcut is not None or not self.first_in_stage)
+        # (a frozen block runs this path in a training model too: ResNet.forward runs the frozen prefix without a graph)
+        owned = not torch.is_grad_enabled() and (not self.training or self.frozen) \
+            and (self.shortcut is not None or not self.first_in_stage)
         return self.conv3(out, residual=shortcut, relu=True, twin=3 if self.third_handle else True, residual_owned=owned)
 
 
@@ -109,8 +133,7 @@ class ResNet(Backbone):
 
     def __init__(self, stem, stages, out_features=None, freeze_at=0):
         super().__init__()
-        if freeze_at != 0:
-            raise NotImplementedError("BACKBONE.FREEZE_AT > 0 is not used by the U2Seg configs")
+        self.frozen_prefix = 0   # leading units that run without a graph: 1 = the stem, 2 = stem + res2, ... (freeze())
         self.stem = stem
         table = [("stem", stem.stride, stem.out_channels)]
         self.stages = []
@@ -132,12 +155,31 @@ class ResNet(Backbone):
         for name, seq in zip(self.stage_names[:-1], self.stages[:-1]):
             if name in self._out_features and hasattr(seq[-1], "third_handle"):
                 seq[-1].third_handle = True
+        self.freeze(freeze_at)
+
+    def freeze(self, freeze_at=0):
+        """Semantics of resnet.py:468-490: every unit whose number is at most freeze_at is frozen; returns self.  Whatever is frozen
+        as a prefix of the network runs as under torch.no_grad() - the folded inference path, no graph, an output that does
+        not require grad - so the first trainable block computes no data gradient for it."""
+        # the network as numbered units: 1 is the stem, n the stage res<n>
+        numbered = [(1, [self.stem])] + [(n, list(stage)) for n, stage in enumerate(self.stages, start=2)]
+        prefix = 0
+        for number, blocks in numbered:
+            if number <= freeze_at:
+                for blk in blocks:
+                    blk.freeze()
+            if prefix == number - 1 and all(getattr(blk, "frozen", False) for blk in blocks):
+                prefix = number   # frozen from the front up to and including this unit
+        self.frozen_prefix = prefix
+        return self
 
     def forward(self, images, pixel_mean, pixel_std, padded_hw):
         outputs = {}
-        x = self.stem(images, pixel_mean, pixel_std, padded_hw)
-        for name, stage in zip(self.stage_names, self.stages):
-            x = stage(x)
+        with torch.set_grad_enabled(torch.is_grad_enabled() and self.frozen_prefix < 1):
+            x = self.stem(images, pixel_mean, pixel_std, padded_hw)
+        for number, (name, stage) in enumerate(zip(self.stage_names, self.stages), start=2):
+            with torch.set_grad_enabled(torch.is_grad_enabled() and self.frozen_prefix < number):
+                x = stage(x)
             if name in self._out_features:
                 # a stage output read by the next stage (conv1 + shortcut: the two twin handles) AND by the caller: the caller
                 # gets the third handle, so that all three gradients meet inside one BatchNorm backward kernel
