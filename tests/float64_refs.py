@@ -1,6 +1,6 @@
 """Float64 reference helpers of tests/test_gpu_optim_resample_float64.py, tests/test_gpu_conv_float64.py,
-tests/test_gpu_inference_tails_float64.py, tests/test_gpu_box_decisions_float64.py, tests/test_gpu_kmeans_update_float64.py and
-tests/test_gpu_kmeans_assign_float64.py, in a plain module so that the CPU tests of
+tests/test_gpu_inference_tails_float64.py, tests/test_gpu_box_decisions_float64.py, tests/test_gpu_kmeans_update_float64.py,
+tests/test_gpu_kmeans_assign_float64.py and (the streaming kernels' launch geometry) tests/test_gpu_tail_bwd_fused.py, in a plain module so that the CPU tests of
 tests/test_float64_refs_host.py check exactly what the GPU tests use.  Plain torch ops only; nothing here touches the HIP
 library.  Every function works on whatever device its inputs live on."""
 import math
@@ -256,9 +256,10 @@ def bf16_round(t):
     return t.float().bfloat16().to(F64)
 
 
-def conv_operands(geom, mode, amp=None):
+def conv_operands(geom, mode, amp=None, forward_only=False):
     """Operands of one convolution case as float64 tensors whose values are bf16 numbers: x [B, Cin, H, W], w [N, Cin, KH, KW],
-    bias [N], gy [B, N, Ho, Wo], old [B, N, Ho, Wo] (the accumulating epilogue's stored values).
+    bias [N], gy [B, N, Ho, Wo], old [B, N, Ho, Wo] (the accumulating epilogue's stored values; gy and old are None with
+    forward_only, for the cases whose outputs are large: x, w and bias are the same either way).
     geom = (B, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w).
     mode "exact": small integers (amplitudes by exact_amp of the forward and data-gradient sum lengths - the taps that fall
       inside the map, not those in the padding - or `amp` for all).
@@ -273,7 +274,10 @@ def conv_operands(geom, mode, amp=None):
         inside = float(_cols(torch.ones((1, 1, h, wd), dtype=F64), kh, kw, stride, ph, pw).sum(1).mean())
         a_f = amp or exact_amp(max(1, round(cin * inside)))
         x, w = ints((b, cin, h, wd), a_f, g), ints((cout, cin, kh, kw), a_f, g)
-        bias, old = ints((cout,), 16 * a_f, g), ints((b, cout, ho, wo), 16 * a_f, g)
+        bias = ints((cout,), 16 * a_f, g)
+        if forward_only:
+            return x, w, bias, None, None
+        old = ints((b, cout, ho, wo), 16 * a_f, g)
         # data gradient: taps * Cout terms, of which a stride-s layer meets one in s^2
         a_g = amp or exact_amp(max(1, round(cout * inside * ho * wo / (h * wd))), a_f)   # every term of y is one of dx too
         gy = ints((b, cout, ho, wo), a_g, g)
@@ -289,6 +293,8 @@ def conv_operands(geom, mode, amp=None):
     w = torch.randn((cout, cin, kh, kw), generator=g, dtype=F64) / k ** 0.5 \
         + (torch.rand((cout, 1, 1, 1), generator=g, dtype=F64) * 2 - 1) / k
     bias = torch.randn((cout,), generator=g, dtype=F64) * 0.1
+    if forward_only:
+        return tuple(bf16_round(t) for t in (x, w, bias)) + (None, None)
     gy = torch.randn((b, cout, ho, wo), generator=g, dtype=F64) * 2.0 ** -10
     old = torch.relu(torch.randn((b, cout, ho, wo), generator=g, dtype=F64) + 1)
     return tuple(bf16_round(t) for t in (x, w, bias, gy, old))
@@ -323,6 +329,87 @@ def stream_pixel_counts(cin):
 
 
 STREAM_GEOMS = [g3(1, 1, m, cin, cout, 1) for cin in STREAM_CIN for cout in STREAM_COUT for m in stream_pixel_counts(cin)]
+
+# (TM pixels per tile, waves along the pixels, waves per work-group) of the three tail instantiations, by reduction width C
+TAIL_CFG = {64: (128, 1, 4), 128: (64, 1, 4), 256: (64, 2, 8)}
+
+
+def stream_cfg(c, n, tail=False):
+    """(TM, PSW, NWV, KSS) of the instantiation launch_conv_stream / launch_conv_stream_tail pick for C input and N output
+    channels; KSS: 32-channel slabs per ring step (a tile of C = 32 KS channels arrives in KS / KSS steps)."""
+    if tail:
+        assert (c, n) in ((64, 256), (128, 512), (256, 1024)), "launch_conv_stream_tail serves these three"
+        return TAIL_CFG[c] + (c // 32,)
+    psw = 1 if n > 128 else 2 if n > 64 else 4
+    if c == 256:
+        return (64, 2, 8, 8) if n > 128 else (64, psw, 4, 4)
+    return {32: 128, 64: 128, 128: 64}[c], psw, 4, c // 32
+
+
+def stream_geometry(c, n, m, tiny, tail=False):
+    """launch_stream_cfg and the first lines of conv_stream_kernel, restated: the ring depth, the grid and the pixel tiles every
+    work-group of one channel block walks.  XCD x (work-groups x, x + 8, ...) owns a contiguous range of xcnt pixel tiles; its
+    work-groups are (walker, channel block) pairs and the nwalk walkers of a channel block take the range's tiles round robin
+    (walker k: tiles k, k + nwalk, ...); walkers beyond the range return at once.  my_tiles[xcd][walker] is 0 for those.
+    tiny: the 8-work-groups-per-channel-block grid of CV_TINY_GRID; otherwise 256 work-groups per resident group of a CU."""
+    tm, psw, nwv, kss = stream_cfg(c, n, tail)
+    stage = tm * kss * 64
+    per_cu = 2 if nwv == 4 else 1
+    ring = min(8, (80 if per_cu == 2 else 160) * 1024 // stage)
+    tiles_m = -(-m // tm)
+    tiles_n = -(-n // (nwv // psw * 64))
+    grid = 8 * tiles_n if tiny else 256 * per_cu
+    assert ring >= 2 and grid // 8 >= tiles_n, "the launcher declines"
+    nwalk = grid // 8 // tiles_n
+    q8, r8 = divmod(tiles_m, 8)
+    xcnt = [q8 + (x < r8) for x in range(8)]
+    xbase = [x * (q8 + 1) if x < r8 else r8 * (q8 + 1) + (x - r8) * q8 for x in range(8)]
+    my_tiles = [[(xcnt[x] - k + nwalk - 1) // nwalk if k < xcnt[x] else 0 for k in range(nwalk)] for x in range(8)]
+    return dict(TM=tm, PSW=psw, NWV=nwv, steps_per_tile=c // 32 // kss, ring=ring, tiles_m=tiles_m, tiles_n=tiles_n, grid=grid,
+                nwalk=nwalk, xcnt=xcnt, xbase=xbase, my_tiles=my_tiles,
+                served_unforced=None if tiny else tiles_m * tiles_n >= 6 * grid)   # (the fill rule is not applied to the tiny grid)
+
+
+def walker_tiles(geo):
+    """The tile counts of the work-groups that have work, as a sorted list of the distinct values."""
+    return sorted({t for row in geo["my_tiles"] for t in row if t > 0})
+
+
+def stream_stats_depth(geo):
+    """Longest chain of fp32 additions behind one column sum of the streaming kernel's epilogues, from its launch geometry: a
+    lane's running sum over the NF rows it holds of a tile, the 16-row transposing sum (4), one addition per tile of the
+    work-group into the lane's total (the busiest walker's count), the work-group flush over its waves, one atomicAdd per
+    work-group of the channel block."""
+    nf = geo["TM"] // geo["PSW"] // 16
+    return nf + 4 + max(walker_tiles(geo)) + geo["NWV"] + 8 * geo["nwalk"]
+
+
+def tail_depth(c, n, m, tiny):
+    """Longest chain of fp32 additions behind one column sum of the TAIL epilogue (launch_stream_cfg / conv_stream_kernel):
+    a lane's running sum over the NF rows it holds of a tile, the 16-row transposing sum (4), one addition per tile of the
+    work-group into the lane's total (the busiest walker's count, from stream_geometry), the work-group flush over its waves,
+    one atomicAdd per work-group of the channel block."""
+    return stream_stats_depth(stream_geometry(c, n, m, tiny, tail=True))
+
+
+def stream_steady_pixels(cin, cout):
+    """The smallest pixel count at which the production grid of the plain streaming kernel is in steady state with uneven shares:
+    some walker owns ring + 2 tiles, another ring + 1, the XCDs' ranges differ in length and the last tile is ragged (one row)."""
+    tm = stream_cfg(cin, cout)[0]
+    geo = stream_geometry(cin, cout, 1, False)
+    tp = 8 * (geo["ring"] + 1) * geo["nwalk"] + 1   # the longest range, ceil(tp / 8) tiles, must give its first walker ring + 2
+    while True:
+        geo = stream_geometry(cin, cout, (tp - 1) * tm + 1, False)
+        counts = walker_tiles(geo)
+        if counts[-1] >= geo["ring"] + 2 and geo["ring"] + 1 in counts and tp % 8:
+            return (tp - 1) * tm + 1
+        tp += 1
+
+
+# the plain streaming kernel on its production grid (CV_STREAM_FORCE alone): one cout with several channel blocks, one with one.
+# Not part of ALL_CONV_GEOMS: the host-side consumers of that list need no tensors of this size.
+STREAM_PROD_COUT = [520, 40]
+STREAM_PROD_GEOMS = [g3(1, 1, stream_steady_pixels(cin, cout), cin, cout, 1) for cin in STREAM_CIN for cout in STREAM_PROD_COUT]
 ACC_GEOMS = [g3(2, 37, 41, 64, 256, 1), g3(3, 20, 24, 256, 1024, 1), g3(1, 1, 1, 64, 256, 1)]
 LONGK_GEOMS = [g3(2, 5, 7, 2048, 512, 1), g3(1, 65, 1, 768, 2304, 1), g3(1, 65, 1, 3072, 768, 1)]
 FC_GEOM = g3(37, 7, 7, 256, 1024, 7, 1, 0)

@@ -841,3 +841,91 @@ def test_kmeans_rule_on_scaled_inputs_and_nan_rows():
     assert lab[~keep].tolist() == [0, 0, 0] and R.kmeans_rule_report("plain fp32", xn, c, lab, rn) is None
     lab[300] = 1
     assert "1 NaN rows are not 0" in R.kmeans_rule_report("plain fp32", xn, c, lab, rn)
+
+
+# ---- conv_stream.hip launch geometry (tests/test_gpu_tail_bwd_fused.py, tests/test_gpu_conv_float64.py) ----
+@pytest.mark.parametrize("c,n,m,tiny,tm,tiles_n,nwalk,tiles_m,xcnt,counts", [
+    # the 8-work-group grid: one walker per XCD and channel block owns its XCD's whole range
+    (64, 256, 7515, True, 128, 1, 1, 59, (8, 7), [7, 8]),
+    (128, 512, 3739, True, 64, 2, 1, 59, (8, 7), [7, 8]),
+    (256, 1024, 3739, True, 64, 4, 1, 59, (8, 7), [7, 8]),
+    # the production grid: 256 work-groups per resident group, nwalk walkers per XCD and channel block
+    (256, 1024, 26779, False, 64, 4, 8, 419, (53, 52), [6, 7]),
+    (128, 512, 106651, False, 64, 2, 32, 1667, (209, 208), [6, 7]),
+    (64, 256, 426331, False, 128, 1, 64, 3331, (417, 416), [6, 7]),
+    (64, 256, 546, False, 128, 1, 64, 5, (1, 0), [1]),
+    (128, 512, 546, False, 64, 2, 32, 9, (2, 1), [1]),
+    (256, 1024, 546, False, 64, 4, 8, 9, (2, 1), [1]),
+    (256, 1024, 5595, False, 64, 4, 8, 88, (11, 11), [1, 2]),
+    (256, 1024, 33600, False, 64, 4, 8, 525, (66, 65), [8, 9]),
+    # the shapes the tests had before: never past the ring's end
+    (64, 256, 1024, True, 128, 1, 1, 8, (1, 1), [1]),
+    (256, 1024, 1024, True, 64, 4, 1, 16, (2, 2), [2]),
+])
+def test_stream_geometry_of_the_tail_cases(c, n, m, tiny, tm, tiles_n, nwalk, tiles_m, xcnt, counts):
+    """The restated launch geometry on hand-worked values (59 = 8 * 7 + 3 tiles: XCDs 0-2 own 8, the others 7, and so on), so
+    that a slip in the helper cannot make the regime assertions of the GPU tests vacuous."""
+    geo = R.stream_geometry(c, n, m, tiny, tail=True)
+    assert geo["ring"] == 5 and geo["steps_per_tile"] == 1
+    assert (geo["TM"], geo["tiles_n"], geo["nwalk"], geo["tiles_m"]) == (tm, tiles_n, nwalk, tiles_m)
+    assert (geo["xcnt"][0], geo["xcnt"][7]) == xcnt and sum(geo["xcnt"]) == tiles_m
+    assert R.walker_tiles(geo) == counts
+    # every tile has exactly one owner: walker k of XCD x takes tiles xbase + k, xbase + k + nwalk, ...
+    owned = sorted(geo["xbase"][x] + k + i * geo["nwalk"] for x in range(8) for k in range(geo["nwalk"])
+                   for i in range(geo["my_tiles"][x][k]))
+    assert owned == list(range(tiles_m))
+    assert all(t == 0 for x in range(8) for k, t in enumerate(geo["my_tiles"][x]) if k >= geo["xcnt"][x])
+    # the fill rule: at least 6 tiles per work-group of the production grid; it is not applied to the 8-work-group grid
+    assert geo["served_unforced"] == (None if tiny else tiles_m * tiles_n >= 6 * 256 * (1 if c == 256 else 2))
+
+
+def test_stream_geometry_hand_worked_walkers():
+    """256 -> 1024 at 26 779 pixels: XCD 0 owns 53 tiles, its 8 walkers 7 7 7 7 7 6 6 6; XCD 7 owns 52: 7 7 7 7 6 6 6 6.
+    5 595 pixels (88 tiles, 11 per XCD): walkers 0-2 two tiles, 3-7 one.  546 pixels under 64 -> 256: five tiles, one walker each on
+    XCDs 0-4 and nothing anywhere else."""
+    geo = R.stream_geometry(256, 1024, 26779, False, tail=True)
+    assert geo["my_tiles"][0] == [7, 7, 7, 7, 7, 6, 6, 6] and geo["my_tiles"][7] == [7, 7, 7, 7, 6, 6, 6, 6]
+    assert geo["xbase"][:4] == [0, 53, 106, 159] and geo["xbase"][7] == 159 + 4 * 52
+    geo = R.stream_geometry(256, 1024, 5595, False, tail=True)
+    assert all(row == [2, 2, 2, 1, 1, 1, 1, 1] for row in geo["my_tiles"])
+    geo = R.stream_geometry(64, 256, 546, False, tail=True)
+    assert [sum(row) for row in geo["my_tiles"]] == [1, 1, 1, 1, 1, 0, 0, 0] and all(row[1:] == [0] * 63 for row in geo["my_tiles"])
+
+
+def test_tail_depth_follows_the_geometry():
+    # NF rows + 4 + the busiest walker's tiles + waves + 8 nwalk atomics; the three values the earlier cases were checked with
+    assert R.tail_depth(64, 256, 546, True) == 8 + 4 + 1 + 4 + 8
+    assert R.tail_depth(256, 1024, 1024, True) == 2 + 4 + 2 + 8 + 8
+    assert R.tail_depth(128, 512, 40, True) == 4 + 4 + 1 + 4 + 8
+    assert R.tail_depth(64, 256, 426331, False) == 8 + 4 + 7 + 4 + 512
+    assert R.tail_depth(256, 1024, 33600, False) == 2 + 4 + 9 + 8 + 64
+    # the plain kernel's statistics: 32 -> 40 has 4 waves along the pixels (NF = 2), 64 walkers; 256 -> 520: NF = 2, 8 waves, 10 walkers
+    assert R.stream_stats_depth(R.stream_geometry(32, 40, 589825, False)) == 2 + 4 + 10 + 4 + 512
+    assert R.stream_stats_depth(R.stream_geometry(256, 520, 30721, False)) == 2 + 4 + 7 + 8 + 80
+
+
+@pytest.mark.parametrize("cin,cout,cfg,ring,nwalk,steps", [
+    (32, 520, (128, 1, 4, 1), 8, 21, 1), (32, 40, (128, 4, 4, 1), 8, 64, 1), (64, 520, (128, 1, 4, 2), 5, 21, 1),
+    (64, 104, (128, 2, 4, 2), 5, 64, 1), (128, 40, (64, 4, 4, 4), 5, 64, 1), (256, 520, (64, 2, 8, 8), 5, 10, 1),
+    (256, 104, (64, 2, 4, 4), 5, 64, 2), (256, 40, (64, 4, 4, 4), 5, 64, 2)])
+def test_stream_geometry_of_the_plain_kernel(cin, cout, cfg, ring, nwalk, steps):
+    """The twelve instantiations' tile, ring and walker counts as conv_stream.hip's launcher states them (a 256-channel tile of
+    the narrow layers arrives in two 128-channel ring steps), and STREAM_RING_PIXELS restated."""
+    assert R.stream_cfg(cin, cout) == cfg
+    geo = R.stream_geometry(cin, cout, 1000, False)
+    assert (geo["ring"], geo["nwalk"], geo["steps_per_tile"]) == (ring, nwalk, steps)
+    if steps == 1:
+        assert geo["ring"] * geo["TM"] == R.STREAM_RING_PIXELS[cin]
+
+
+def test_stream_production_geoms_are_in_steady_state():
+    assert len(R.STREAM_PROD_GEOMS) == 8 and not set(R.STREAM_PROD_GEOMS) & set(R.ALL_CONV_GEOMS)
+    for geom in R.STREAM_PROD_GEOMS:
+        m, cin, cout = geom[2], geom[3], geom[4]
+        geo = R.stream_geometry(cin, cout, m, False)
+        counts = R.walker_tiles(geo)
+        assert counts[-1] == geo["ring"] + 2 and geo["ring"] + 1 in counts, (geom, counts)
+        assert len(set(geo["xcnt"])) == 2 and m % geo["TM"] == 1
+        assert (geo["tiles_n"] > 1) == (cout == 520)
+        # the smallest such count: one tile fewer leaves no walker with ring + 2 tiles
+        assert max(R.walker_tiles(R.stream_geometry(cin, cout, m - 1, False))) == geo["ring"] + 1

@@ -92,8 +92,8 @@ def check_bf16(name, got, ref, a, length, mode, relu=False, old=None):
 
 
 def check_f32(name, got, ref, a, length, mode):
-    """An fp32 output against float64: equal (exact) or within E (real).  All elements."""
-    got = got.to(F64).cpu()
+    """An fp32 output against float64: equal (exact) or within E (real).  All elements.  On the reference's device."""
+    got = got.to(F64).to(ref.device)
     assert got.shape == ref.shape, (name, got.shape, ref.shape)
     if mode == "exact":
         assert float(a.max()) < R.TWO24, (name, "precondition: sum |term| = %g" % float(a.max()))
@@ -109,10 +109,23 @@ def check_f32(name, got, ref, a, length, mode):
             name, int(bad.sum()), bad.numel(), i, float(got[i]), float(ref[i]), float(e[i])))
 
 
-def check_stats(name, stats, y, mode, need_exact_squares=False):
-    """[sum | sum of squares] over the STORED outputs y (float64 [B, N, H, W] of bf16 values; y^2 is an fp32 value)."""
+def check_stats(name, stats, y, mode, need_exact_squares=False, depth=None):
+    """[sum | sum of squares] over the STORED outputs y (float64 [B, N, H, W] of bf16 values; y^2 is an fp32 value).
+    depth: the longest chain of fp32 additions behind a column sum by the launch geometry (float64_refs.stream_stats_depth), for
+    maps with so many pixels that sum |y| passes 2^24 at the exact generator's amplitudes (which are chosen for the outputs'
+    rounding).  Recursive summation over chains of length d errs by at most d u sum |term|, so both rows are then held to
+    (depth + 2) 2^-24 sum |term| instead of (pixels + 2) 2^-24 sum |term| - in both modes - and the column sum stays exact
+    wherever its own sum |y| is below 2^24."""
     m = y.shape[0] * y.shape[2] * y.shape[3]
     s0, a0, s1 = y.sum((0, 2, 3)), y.abs().sum((0, 2, 3)), (y * y).sum((0, 2, 3))
+    if depth is not None:
+        assert depth < m
+        small = a0 < R.TWO24
+        if mode == "exact" and bool(small.any()):
+            check_f32(name + " stats[0] (columns below 2^24)", stats[0][small.to(stats.device)], s0[small], a0[small], depth, "exact")
+        check_f32(name + " stats[0]", stats[0], s0, a0, depth, "real")
+        check_f32(name + " stats[1]", stats[1], s1, s1, depth, "real")
+        return
     check_f32(name + " stats[0]", stats[0], s0, a0, m, mode)
     squares_exact = mode == "exact" and float(s1.max()) < R.TWO24
     if need_exact_squares:
@@ -372,6 +385,52 @@ def test_conv_stream_ring(F, geom, mode):
     code = stream_code(cin, cout)
     variant = STREAM | (TINY if m > 63 else 0)
     run_layer(F, geom, mode, conv=variant, fwd_code=code, bias_leg="fwd", name="stream")
+
+
+def stream_forward_on_device(F, geom, mode, variant, code, name):
+    """run_layer's forward legs - plain with the fused statistics, bias + ReLU - with the operands drawn on the host as ever and the
+    float64 references formed on the device: an output of these cases has up to 10^8 elements.  1x1 / stride 1 only."""
+    b, h, w, cin, cout, kh, kw, stride, ph, pw = geom
+    assert (kh, kw, stride, ph, pw) == (1, 1, 1, 0, 0)
+    name = "%s %s %s" % (name, geom, mode)
+    x, wt, bias, _, _ = R.conv_operands(geom, mode, forward_only=True)
+    xd, wd, bd = dev_act(x), wt.float().to(DEV), bias.float().to(DEV)
+    x64 = xd[..., :cin].to(F64).view(-1, cin)
+    w64 = wt.to(DEV).view(cout, cin).t().contiguous()
+    y_ref, a_ref = x64 @ w64, x64.abs() @ w64.abs()
+    del x64
+
+    def stored(y):   # [B, H, W, Np] -> float64 [M, cout]; the padded channels must hold zeros
+        assert y.shape[3] == cout or float(y[..., cout:].float().abs().max()) == 0.0, name
+        return y[..., :cout].to(F64).view(-1, cout)
+
+    with forced(conv=variant), torch.no_grad():
+        y, st = F._Conv2dFn.apply(xd, wd, None, 1, 0, False, True)
+        assert last_kernel() == code, (name, "forward ran kernel %d, expected %d" % (last_kernel(), code))
+        y2, _ = F._Conv2dFn.apply(xd, wd, bd, 1, 0, True, False)
+        assert last_kernel() == code, (name, last_kernel(), code)
+    if mode == "exact":
+        assert big_share(y_ref) > 0.25, (name, big_share(y_ref))
+    yy = stored(y)
+    check_bf16(name + " fwd", yy, y_ref, a_ref, cin, mode)
+    depth = R.stream_stats_depth(R.stream_geometry(cin, cout, b * h * w, False))
+    check_stats(name, st, yy.t().reshape(1, cout, 1, -1), mode, depth=depth)
+    b64 = bias.to(DEV)
+    check_bf16(name + " fwd bias relu", stored(y2), y_ref + b64, a_ref + b64.abs(), cin, mode, relu=True)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("geom", R.STREAM_PROD_GEOMS)
+def test_conv_stream_production_grid(F, geom, mode):
+    """conv_stream.hip forced onto its production grid (256 work-groups per resident group: 64 / 21 / 10 walkers per XCD and
+    channel block, tiles taken nwalk apart) at the smallest pixel count that has it in steady state with uneven shares
+    (float64_refs.stream_steady_pixels): some walker owns ring + 2 tiles, another ring + 1, the XCDs' ranges differ by a tile, the
+    last tile holds one pixel.  One cout with three channel blocks (520), one with a single 64-channel block (40)."""
+    cin, cout, m = geom[3], geom[4], geom[2]
+    geo = R.stream_geometry(cin, cout, m, False)
+    counts = R.walker_tiles(geo)
+    assert counts[-1] == geo["ring"] + 2 and geo["ring"] + 1 in counts and len(set(geo["xcnt"])) == 2 and m % geo["TM"] == 1
+    stream_forward_on_device(F, geom, mode, STREAM, stream_code(cin, cout), "stream production grid")
 
 
 # ---- 6. accumulating epilogue ----
