@@ -375,6 +375,17 @@ int u2_label_pad_batch(const void* const* imgs, const int* hs, const int* ws, in
 /* All images of the batch (host arrays of device pointers / sizes; images may differ in size) in one launch. */
 int u2_stem_im2col_batch(const void* const* imgs, const int* hs, const int* ws, int n_imgs, int is_uint8, const float* mean,
                          const float* stdv, void* col, int Hpad, int Wpad, int KP, void* stream);
+/* The same convolution without the matrix (stem_conv.hip): out bf16 [n_imgs][Ho][Wo][64] = conv of the normalised, zero-padded
+ * images with wk bf16 [64][KP = 160] (K order (kh, kw, c), columns 147..159 zero); stats (nullable) fp32 [2][64] accumulates the
+ * column sums and sums of squares of the stored output.  Operand values are those of u2_stem_im2col_batch bit for bit; the fp32
+ * summation order differs from the GEMM's.  Returns 1 and launches nothing for a call it does not serve (N != 64, KP != 160, an
+ * output of 4 GB or more): the caller takes the im2col path. */
+int u2_stem_conv_fwd(const void* const* imgs, const int* hs, const int* ws, int n_imgs, int is_uint8, const float* mean,
+                     const float* stdv, const void* wk, void* out, float* stats, int Hpad, int Wpad, int N, int KP, void* stream);
+/* Its weight gradient: dw fp32 [64][KP] += sum over pixels of dy[m][n] * a[m][k], dy bf16 [n_imgs][Ho][Wo][64]; columns 147..159
+ * are left alone.  One flush of fp32 atomics per persistent work-group.  Same answer 1 for a call it does not serve. */
+int u2_stem_conv_wgrad(const void* const* imgs, const int* hs, const int* ws, int n_imgs, int is_uint8, const float* mean,
+                       const float* stdv, const void* dy, float* dw, int Hpad, int Wpad, int N, int KP, void* stream);
 
 /* ---- losses (losses.hip) -----------------------------------------------------------------------
  * meta_arch/semantic_seg.py:255-267, roi_heads/fast_rcnn.py:307-347,424-463, roi_heads/mask_head.py:33-112,

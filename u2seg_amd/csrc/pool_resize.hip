@@ -7,6 +7,7 @@
 //   image normalisation + zero pad + im2col       detectron2/modeling/meta_arch/rcnn.py:223-234 feeding the
 //                                                 7x7 s2 stem conv of backbone/resnet.py:355-357
 #include "common.h"
+#include "stem_window.h"
 #include "u2seg_hip.h"
 
 namespace {
@@ -504,8 +505,8 @@ __global__ __launch_bounds__(256) void bilinear2_bwd_kernel(const bf16_t* __rest
 //      One work-group = 8 x 32 output pixels of one image: the 21 x 69 x 3 input window is normalised once into LDS
 //      (zero outside the image), then every 16-byte chunk of the 256 K-rows is assembled from LDS through a k -> offset
 //      table and stored coalesced (320 B per pixel row). ----
-constexpr int ST_TH = 8, ST_TW = 32, ST_IH = 2 * ST_TH + 5, ST_IW = 2 * ST_TW + 5, ST_IWP = ST_IW + 1;
-struct StemImages { const void* img[32]; int h[32]; int w[32]; };
+//      (the window and its staging: stem_window.h, shared with the direct kernels of stem_conv.hip)
+constexpr int ST_IWP = ST_IW + 1;
 
 template <typename T>
 __global__ __launch_bounds__(256) void stem_im2col_kernel(const StemImages imgs, const float* __restrict__ mean,
@@ -519,16 +520,7 @@ __global__ __launch_bounds__(256) void stem_im2col_kernel(const StemImages imgs,
   const int h = imgs.h[bi], w = imgs.w[bi];
   const int oy0 = blockIdx.y * ST_TH, ox0 = blockIdx.x * ST_TW;
   const int iy0 = oy0 * 2 - 3, ix0 = ox0 * 2 - 3;
-  const size_t plane = (size_t)h * w;
-  for (int i = tid; i < 3 * ST_IH * ST_IW; i += 256) {
-    const int x = i % ST_IW;
-    const int r = (i / ST_IW) % ST_IH;
-    const int c = i / (ST_IW * ST_IH);
-    const int iy = iy0 + r, ix = ix0 + x;
-    float v = 0.f;
-    if (iy >= 0 && iy < h && ix >= 0 && ix < w) v = ((float)img[c * plane + (size_t)iy * w + ix] - mean[c]) / stdv[c];
-    tile[(c * ST_IH + r) * ST_IWP + x] = f2bf(v);
-  }
+  stem_stage_window<T, ST_IWP>(tile, img, h, w, iy0, ix0, mean, stdv, tid);
   for (int k = tid; k < KP; k += 256) {
     short o = -1;
     if (k < 147) {

@@ -40,6 +40,7 @@ from .weights import (BF16, _check_act, _conv_bias, _weight_layout, ceil32, grad
 # --------------------------------------------------------------------------------------------
 _DET_STATS = False   # set_deterministic_stats()
 STEM_TAIL_FUSE = os.environ.get("U2_STEM_TAIL_FUSE", "1") != "0"   # the stem's norm -> ReLU -> max pool as one pass (stem_tail_ok)
+STEM_DIRECT = os.environ.get("U2_STEM_DIRECT", "1") != "0"   # the stem conv and its weight gradient without the im2col matrix
 FUSED_BWD_MIN_PIXELS = int(os.environ.get("U2_FUSED_BWD_MIN_PIXELS", "200000"))
 # Three backward folds hand autograd a zero placeholder and leave the gradient to the node that receives it (layers/deferred.py):
 # - the batch-norm backward apply step of an expanding 1x1 layer evaluated inside that layer's fused backward launch (0: separate)
@@ -343,8 +344,13 @@ def linear(x2d, weight, bias=None, relu=False):
 
 
 class _StemConvFn(Function):
-    """(x - mean)/std, zero pad to the batch canvas, 7x7 stride-2 pad-3 conv of 3 -> 64 channels as an
-    im2col GEMM (rcnn.py:223-234 + backbone/resnet.py:355-357). Images need no gradient."""
+    """(x - mean)/std, zero pad to the batch canvas, 7x7 stride-2 pad-3 conv of 3 -> 64 channels
+    (rcnn.py:223-234 + backbone/resnet.py:355-357). Images need no gradient.
+
+    Production path (STEM_DIRECT): u2_stem_conv_fwd / u2_stem_conv_wgrad read the MFMA operands from the normalised image window in
+    LDS; what is kept for the backward pass is the image list.  The im2col GEMM (u2_stem_im2col_batch + u2_conv_igemm, the matrix
+    saved for u2_conv_wgrad) serves the calls the direct launcher declines, U2_STEM_DIRECT=0 and the deterministic-statistics mode,
+    whose fixed-order pass wants the stem among the recorded u2_conv_igemm launches."""
 
     KP = 160
 
@@ -354,7 +360,6 @@ class _StemConvFn(Function):
         b = len(images)
         ho, wo = (hpad + 6 - 7) // 2 + 1, (wpad + 6 - 7) // 2 + 1
         kp = _StemConvFn.KP
-        col = torch.empty((b * ho * wo, kp), dtype=BF16, device=weight.device)
         is_u8 = images[0].dtype == torch.uint8
         for img in images:
             assert img.is_cuda and img.is_contiguous() and img.shape[0] == 3
@@ -362,30 +367,42 @@ class _StemConvFn(Function):
         ptrs = (ctypes.c_void_p * b)(*[img.data_ptr() for img in images])
         hs = (ctypes.c_int * b)(*[img.shape[1] for img in images])
         ws = (ctypes.c_int * b)(*[img.shape[2] for img in images])
-        _hip.call("u2_stem_im2col_batch", ptrs, hs, ws, b, int(is_u8), pixel_mean, pixel_std, col, hpad, wpad, kp)
         # [64, 3, 7, 7] -> K order (kh, kw, c), zero padded to kp: the forward layout of a 49-tap, 3-channel conv flattened
         wk = torch.zeros((n, 1, kp), dtype=BF16, device=weight.device)
         wk[:, 0, :147] = weight.detach().permute(0, 2, 3, 1).reshape(n, 147)
         out = torch.empty((b, ho, wo, n), dtype=BF16, device=weight.device)
         stats = _stats_buffer(n, weight.device)
         m = b * ho * wo
+        ctx.n = n
+        if STEM_DIRECT and not _DET_STATS and _hip.call_status("u2_stem_conv_fwd", ptrs, hs, ws, b, int(is_u8), pixel_mean, pixel_std,
+                                                               wk, out, stats, hpad, wpad, n, kp) == 0:
+            ctx.direct = (list(images), ptrs, hs, ws, int(is_u8), pixel_mean, pixel_std, hpad, wpad)
+            ctx.mark_non_differentiable(stats)
+            return out, stats
+        ctx.direct = None
+        col = torch.empty((m, kp), dtype=BF16, device=weight.device)
+        _hip.call("u2_stem_im2col_batch", ptrs, hs, ws, b, int(is_u8), pixel_mean, pixel_std, col, hpad, wpad, kp)
         _hip.call("u2_conv_igemm", col, wk, out, None, None if _DET_STATS else stats, 1, m, 1, kp, kp, m, 1, n, n, 1, 1, 0, 0, 1,
                   1, 0, 0, 0)
         if _DET_STATS:
             stats = _fixed_order_stats(out, n)
         ctx.save_for_backward(col)
-        ctx.n = n
         ctx.mark_non_differentiable(stats)
         return out, stats
 
     @staticmethod
     def backward(ctx, dout, _ds):
-        (col,) = ctx.saved_tensors
         n, kp = ctx.n, _StemConvFn.KP
         dout = dout.contiguous()
-        m = col.shape[0]
-        dwk = zeros_f32((n, 1, kp), col.device)
-        _hip.call("u2_conv_wgrad", col, dout, dwk, 1, m, 1, kp, kp, m, 1, n, n, 1, 1, 0, 0, 1, 0)
+        dwk = zeros_f32((n, 1, kp), dout.device)
+        if ctx.direct is not None:
+            images, ptrs, hs, ws, is_u8, pixel_mean, pixel_std, hpad, wpad = ctx.direct
+            # (the forward launcher served this call, so the same checks pass here)
+            _hip.call("u2_stem_conv_wgrad", ptrs, hs, ws, len(images), is_u8, pixel_mean, pixel_std, dout, dwk, hpad, wpad, n, kp)
+        else:
+            (col,) = ctx.saved_tensors
+            m = col.shape[0]
+            _hip.call("u2_conv_wgrad", col, dout, dwk, 1, m, 1, kp, kp, m, 1, n, n, 1, 1, 0, 0, 1, 0)
         dw = dwk[:, 0, :147].view(n, 7, 7, 3).permute(0, 3, 1, 2)
         return dw, None, None, None, None, None
 
