@@ -16,7 +16,7 @@
 extern "C" {
 #endif
 
-/* ---- convolution / linear family (conv_igemm.hip) -------------------------------------------
+/* ---- convolution / linear family (entry points and dispatch: conv_api.hip) -------------------
  * Replaces F.conv2d in detectron2/layers/wrappers.py:127-134 (all Conv2d of backbone/resnet.py:194-210,
  * 355-358, backbone/fpn.py:141-158, meta_arch/semantic_seg.py:196-205, proposal_generator/rpn.py:127-134,
  * roi_heads/mask_head.py:242-251), nn.Linear in roi_heads/box_head.py:66-74 and roi_heads/fast_rcnn.py:236-239,
@@ -77,7 +77,7 @@ extern "C" {
 #define U2_CV_EXPLICIT_MASK 0xffffu
 
 /* The wgrad word: u2_conv_wgrad, u2_conv_wgrad_into, U2_WGRAD_VARIANT.
- * Bits 0-11 belong to the per-tap kernels of conv_igemm.hip (128 x 128 and 256 x 256 tiles). */
+ * Bits 0-11 belong to the per-tap kernels of conv_wgrad.hip (128 x 128 and 256 x 256 tiles). */
 #define U2_WG_REG_STAGING (1u << 0)           /* register-staged operands instead of global_load_lds */
 #define U2_WG_SCALAR_GATHER (1u << 1)         /* scalar LDS gathers instead of ds_read_b64_tr_b16 */
 #define U2_WG_FEWER_SPLITS_SHIFT 4            /* resident work-groups (pixel splits) halved this many times */
@@ -126,7 +126,7 @@ extern "C" {
 #define U2_K_STREAM_TAIL 5         /* ... or + C / 32 * 10 + this for u2_conv_dgrad_tail */
 /* conv_igemm_kernel<BK, GLDS, TM, TN, NST>: U2_K_IGEMM + BK * 10000 + TM / 64 * 1000 + TN / 64 * 100 + NST * 10 + GLDS */
 #define U2_K_IGEMM 1000000
-#define U2_K_WGRAD 2000            /* conv_wgrad_kernel<GLDS, TR>: + GLDS * 2 + TR */
+#define U2_K_WGRAD 2000            /* conv_wgrad.hip, conv_wgrad_kernel<GLDS, TR>: + GLDS * 2 + TR */
 #define U2_K_WGRAD_XCD 100         /* added to U2_K_WGRAD / U2_K_WGRAD256 codes when the launch is XCD-grouped */
 #define U2_K_WGRAD256 2256         /* conv_wgrad256_kernel */
 #define U2_K_WGRAD_STREAM 2700     /* wgrad_stream.hip: + block configuration (1-4) */
@@ -191,7 +191,7 @@ int u2_conv_dgrad_tail(const void* in, const void* wt, const void* dout2, const 
  * environment variables U2_CONV_VARIANT / U2_WGRAD_VARIANT / U2_WDGRAD_VARIANT (the variant words above). */
 int u2_conv_last_kernel(void);
 
-/* The only device memory the library owns: the conv kernels' scratch (stream-K hand-over slots of u2_conv_igemm, partial tiles of
+/* The only device memory the library owns (conv_scratch.hip): the conv kernels' scratch (stream-K hand-over slots of u2_conv_igemm, partial tiles of
  * u2_conv_wgrad), one block per (device, stream), allocated on first need at the size of that launch and grown on demand.  This
  * call drains the streams concerned and frees every block (the next launch that needs one allocates again); returns the number
  * of blocks freed.  The reference's ops (ATen conv behind layers/wrappers.py:127-134) take such workspaces from torch's caching

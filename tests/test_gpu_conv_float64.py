@@ -1,4 +1,4 @@
-"""The convolution family (conv_igemm.hip, conv_tile.hip, conv_halo.hip, conv_stream.hip, wgrad_halo.hip, wgrad_stream.hip and
+"""The convolution family (conv_igemm.hip, conv_tile.hip, conv_halo.hip, conv_stream.hip, conv_wgrad.hip, wgrad_halo.hip, wgrad_stream.hip and
 the fused 1x1 backward) per element against float64 - tests/test_gpu_kernel_variants.py holds the same kernels to 4e-3 of the
 LARGEST element of a mean-zero result, which passes truncation for rounding, a bf16 hand-over of a partial tile and a dropped
 product with small factors.
@@ -340,7 +340,7 @@ def test_asymmetric_filter_through_the_abi(F, variant, mode):
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("geom", R.STRIDE2_GEOMS)
 def test_stride2_data_gradient_parity_classes(F, geom, mode):
-    """The data gradient of a stride-2 layer runs one launch per parity class of the input map (conv_igemm.hip:u2_conv_igemm,
+    """The data gradient of a stride-2 layer runs one launch per parity class of the input map (conv_api.hip:u2_conv_igemm,
     div = 2): maps of 1 x 1, 1 x 2 and 2 x 1 pixels (classes with py >= Hout / px >= Wout), 7 x 9 and 8 x 10; 1x1 / pad 0 (three
     classes meet no tap: one zero-fill launch, N % 8 == 0) and 3x3 / pad 1; through the product path, and through the C ABI with
     a bias + ReLU and with the accumulating epilogue onto a non-zero map (every class then keeps its own launch)."""

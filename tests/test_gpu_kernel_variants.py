@@ -4,7 +4,7 @@ pick at the shapes of the benchmark configuration (u2seg_R50_800, batch 16, 800x
 Two kinds of test:
   * forced variants on small shapes: the product path passes variant 0, so the tests steer the launchers through
     U2_CONV_VARIANT / U2_WGRAD_VARIANT (same bits as the C-ABI's variant argument) and check with u2_conv_last_kernel that
-    the intended kernel really ran - every template instantiation of conv_igemm.hip and conv_tile.hip gets a forward +
+    the intended kernel really ran - every template instantiation of conv_igemm.hip, conv_wgrad.hip and conv_tile.hip gets a forward +
     data-gradient + weight-gradient comparison with fp32 F.conv2d on the same bf16-rounded operands;
   * true benchmark shapes through the AUTOMATIC dispatch (no override): the fpn_output2 layer (16 x 200 x 336, 3x3
     256 -> 256; non-temporal output stores, the deepest LDS ring, XCD-grouped wgrad) forward / dgrad / wgrad and a few

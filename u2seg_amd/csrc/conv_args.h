@@ -1,5 +1,6 @@
-// Argument block, staging and LDS-layout helpers shared by the convolution kernels (conv_igemm.hip, conv_tile.hip, conv_halo.hip,
-// conv_stream.hip, wgrad_halo.hip, wgrad_stream.hip).
+// Argument blocks, staging and LDS-layout helpers and the launcher interface shared by the convolution sources: the entry points
+// and dispatch chains (conv_api.hip), the kernel families (conv_stream.hip, conv_halo.hip, conv_tile.hip, conv_igemm.hip;
+// wgrad_stream.hip, wgrad_halo.hip, conv_wgrad.hip) and the library's device scratch (conv_scratch.hip).
 #pragma once
 #include "common.h"
 #include "conv_variant.h"
@@ -70,21 +71,51 @@ union Frag {
   s16x8 v;
 };
 
+// Argument block of the weight-gradient families (a kernel argument of conv_wgrad.hip: fields and order are fixed).
+// dW[n][tap][c] += sum_m dY[m][n] * X[src(m,tap)][c]; the entry point fills everything down to M, a launcher the rest.
+struct WgradArgs {
+  const bf16_t* x;    // NHWC input of the forward conv (pixel pitch x_ld)
+  const bf16_t* dy;   // [M][dy_ld] output gradient
+  float* dw;          // fp32, accumulated atomically at dw[n * dw_sn + tap * dw_st + c * dw_sc], n < n_valid, c < c_valid
+  long long dw_sn;
+  int dw_st, dw_sc, n_valid, c_valid;
+  const bf16_t* zero;
+  int B, Hin, Win, C, x_ld;
+  int Hout, Wout, N, dy_ld;
+  int KH, KW, pad_h, pad_w, stride;
+  int M, tiles_n, tiles_c, pix_per_wg;
+  int tiles, xcd_group;  // tiles = tiles_n * tiles_c * taps; xcd_group: 1-D launch, all tiles of a pixel split on one XCD
+  // Partial tiles instead of atomics (round 4): when `part` is set a work-group stores its fp32 tile, [c][n] with n fastest, at
+  // part + (split * tiles + tile) * TILE * TILE and wgrad_reduce_kernel sums the splits into dw afterwards.  fp32 atomics retire
+  // at ~0.25 T operations/s on this part whatever their scope (tests/native/atomics_bench: ~1 TB/s of partial sums) - the
+  // 64 KB x 512 work-group epilogue of a small-map 1x1 layer was 30 of its 77 us - plain 16-byte stores + one pass that reads
+  // the partials back from the MALL move the same bytes at 5+ TB/s.
+  float* part;
+};
+
 // Which kernel the most recent u2_conv_igemm / u2_conv_wgrad launch selected (u2_conv_last_kernel, a test / debugging aid):
-// the U2_K_ codes of include/u2seg_hip.h.
+// the U2_K_ codes of include/u2seg_hip.h.  Defined in conv_api.hip; every launcher sets the code of the kernel it launches.
 extern int g_last_conv_kernel;
 
-// conv_tile.hip: persistent 64(ch) x 128(px)-per-wave tile kernels; returns 1 when it took the launch, 0 when the shape is
-// not served (caller falls back to conv_igemm_kernel), -1000 - hipError_t on a launch failure.
+// The launcher convention.  Each family's launch_* decides for itself whether it serves the shape and the variant: it answers
+// LAUNCH_TAKEN when it launched, LAUNCH_NOT_SERVED when the caller has to try the next family of its chain, and
+// -1000 - hipError_t when its launch failed.  The two families that end a chain (launch_conv_igemm, launch_wgrad_per_tap) serve
+// everything and answer with the C status of the entry point instead.  The chains themselves are in conv_api.hip.
+constexpr int LAUNCH_NOT_SERVED = 0, LAUNCH_TAKEN = 1;
+
+// conv_tile.hip: persistent 64(ch) x 128(px)-per-wave tile kernels.
 int launch_conv_tile(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s);
 
-// conv_halo.hip: 3x3 / stride 1 / pad 1 with the input halo of a 16 x 32 pixel patch staged once per 32-channel slab; same
-// return convention as launch_conv_tile.  g_last_conv_kernel code: 300.
+// conv_halo.hip: 3x3 / stride 1 / pad 1 with the input halo of a 16 x 32 pixel patch staged once per 32-channel slab.
+// g_last_conv_kernel code: 300.
 int launch_conv_halo(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s);
 
 // conv_stream.hip: 1x1 / stride 1 layers with <= 256 input channels - weights resident in registers, whole pixel rows streamed
-// through an LDS ring; same return convention as launch_conv_tile.  g_last_conv_kernel code: 7xx.
+// through an LDS ring.  g_last_conv_kernel code: 7xx.
 int launch_conv_stream(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s);
+
+// conv_igemm.hip: the 128 x 128 ... 256 x 256 tile kernels that serve every shape, the end of the forward chain.
+int launch_conv_igemm(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s);
 
 // conv_stream.hip, tail mode: the same launch as the data gradient of a residual block's conv1, with the backward reduce of the
 // previous block's tail in the epilogue.  out = dz = mask * bf16(bf16(conv) + g2), stats[0][n] += sum dz,
@@ -98,28 +129,30 @@ struct TailArgs {
 };
 int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, const ConvVariant& v, hipStream_t s);
 
-// wgrad_halo.hip: 3x3 / stride 1 / pad 1 weight gradient, all nine taps per work-group with the input halo in LDS; same
-// return convention as launch_conv_tile.  g_last_conv_kernel code: 2900.
-int launch_wgrad_halo(const bf16_t* x, const bf16_t* dy, float* dw, long long dw_sn, int dw_st, int dw_sc, int n_valid,
-                      int c_valid, const bf16_t* zero, int B, int H, int W, int C, int x_ld, int N, int dy_ld, int rounds,
-                      int force, int part_mode, hipStream_t s);
+// wgrad_halo.hip: 3x3 / stride 1 / pad 1 weight gradient, all nine taps per work-group with the input halo in LDS.
+// g_last_conv_kernel code: 2900.
+int launch_wgrad_halo(const WgradArgs& a, const WgradVariant& v, hipStream_t s);
 
 // wgrad_stream.hip: 1x1 / stride 1 weight gradient over large maps - a persistent work-group per pixel range accumulates a whole
-// block of dW in registers, operands streamed once through an LDS ring of whole pixel rows; same return convention as
-// launch_conv_tile.  g_last_conv_kernel code: 2700 + block configuration.
-int launch_wgrad_stream(const bf16_t* x, const bf16_t* dy, float* dw, long long dw_sn, int dw_sc, int n_valid, int c_valid,
-                        const bf16_t* zero, int M, int C, int x_ld, int N, int dy_ld, int force, int tiny, int cfg, int per_cu,
-                        hipStream_t s);
+// block of dW in registers, operands streamed once through an LDS ring of whole pixel rows.  g_last_conv_kernel code: 2700 +
+// block configuration.
+int launch_wgrad_stream(const WgradArgs& a, const WgradVariant& v, hipStream_t s);
 
+// conv_wgrad.hip: one GEMM over the pixels per (n-tile, c-tile, filter tap), the end of the weight-gradient chain.  Fills the
+// launch half of `a`.
+int launch_wgrad_per_tap(WgradArgs& a, const WgradVariant& v, hipStream_t s);
+
+// wgrad_stream.hip: the streaming weight gradient with the data gradient (and optionally a batch norm's apply step) fused in.
 int launch_wdgrad_stream(const bf16_t* x, const bf16_t* dy, const bf16_t* wt, bf16_t* dx, float* dw, long long dw_sn, int dw_sc,
                          int n_valid, int c_valid, const bf16_t* zero, int M, int C, int x_ld, int N, int dy_ld, int wt_ld,
                          int dx_ld, const FusedBwdVariant& v, hipStream_t s, const bf16_t* yn = nullptr, const float* k1 = nullptr,
                          const float* k2 = nullptr, const float* k3 = nullptr);
 
-// Library-owned device scratch (conv_igemm.hip), one block per (device, stream, kind): the kernels of a stream run one after
+// Library-owned device scratch (conv_scratch.hip), one block per (device, stream, kind): the kernels of a stream run one after
 // the other, so consecutive launches share it.  Sized to the largest launch seen so far - allocated on first need, grown on
-// demand (the stream is drained before the old block is freed), never above `limit_bytes` (nullptr: the caller takes its
-// scratch-free path) - and released by u2_release_scratch().  kind 0: stream-K hand-over slots, 1: stream-K flags (zero on
+// demand by at least half (an outgrown block is retired, not freed: another host thread may still be about to launch on it),
+// never above `limit_bytes` (nullptr: the caller takes its scratch-free path).  Nothing is freed before u2_release_scratch(),
+// which drains the streams and frees the live and the retired blocks.  kind 0: stream-K hand-over slots, 1: stream-K flags (zero on
 // allocation; their consumers leave them at zero), 2: weight-gradient partial tiles.
 void* scratch_get(int kind, hipStream_t s, size_t need_bytes, size_t limit_bytes, bool zero_on_alloc);
 

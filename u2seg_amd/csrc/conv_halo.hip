@@ -352,7 +352,7 @@ int launch_halo_cfg(ConvArgs& a, int N, int tiny, hipStream_t s) {
   a.tiles_m = (int)patches;
   a.tiles_n = (N + CW * 64 - 1) / (CW * 64);
   const long long T = patches * a.tiles_n;
-  if (T >= (1 << 30)) return 0;
+  if (T >= (1 << 30)) return LAUNCH_NOT_SERVED;
   long long G = T < (tiny ? 8 : 256) ? T : (tiny ? 8 : 256);
   G = (G + 7) & ~7LL;
   static PerDeviceOnce attr_set;
@@ -362,7 +362,7 @@ int launch_halo_cfg(ConvArgs& a, int N, int tiny, hipStream_t s) {
   hipLaunchKernelGGL((conv_halo_kernel<PH, PWD, OPT, CW>), dim3((unsigned)G), dim3(512), LDS_BYTES, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return -1000 - (int)e;
-  return 1;
+  return LAUNCH_TAKEN;
 }
 
 double patch_fill(int H, int W, int ph, int pw) {
@@ -377,23 +377,23 @@ double patch_fill(int H, int W, int ph, int pw) {
 // layers with <= 128 output channels on the stride-8 maps (78-84 % full, +11 %) - and loses on small maps (50 x 84 and below,
 // 14 x 14 ROI maps), which stay on the tile kernels.  g_last_conv_kernel code: 300 (128-channel tiles) / 301 (64-channel tiles).
 int launch_conv_halo(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s) {
-  if (v.halo == Choice::Never) return 0;
-  if (v.tile_cfg != 0) return 0;  // a tile-kernel configuration was asked for explicitly
+  if (v.halo == Choice::Never) return LAUNCH_NOT_SERVED;
+  if (v.tile_cfg != 0) return LAUNCH_NOT_SERVED;  // a tile-kernel configuration was asked for explicitly
   const bool forced = v.halo == Choice::Force;
   if (a.remap_out || a.accumulate || a.ntaps != 9 || a.KW != 3 || a.wt_taps != 9 || a.pad_h != 1 || a.pad_w != 1 || a.mul != 1 ||
       a.Hin != a.Hout || a.Win != a.Wout)
-    return 0;
-  if ((C & 31) || (N & 7) || (a.out_ld & 7) || a.M < 1) return 0;
+    return LAUNCH_NOT_SERVED;
+  if ((C & 31) || (N & 7) || (a.out_ld & 7) || a.M < 1) return LAUNCH_NOT_SERVED;
   if ((unsigned long long)a.B * a.Hin * a.Win * a.in_ld * 2ull >= 0xffffffffull || (unsigned long long)N * 9 * C * 2ull >= 0xfffffff0ull)
-    return 0;
+    return LAUNCH_NOT_SERVED;
   // (an 8 x 64 patch instantiation exists as a template parameter set, but at 256 registers it spills six of them into the
   //  tile loop, and a scratch access there makes the compiler drain the LDS-DMA queue in every slab: not dispatched)
   const double fill = patch_fill(a.Hout, a.Wout, 16, 32);
   if (!forced) {
     const int tnc = N <= 64 ? 64 : TN;
     const long long tiles = (long long)a.B * ((a.Hout + 15) / 16) * ((a.Wout + 31) / 32) * ((N + tnc - 1) / tnc);
-    if (tiles < 512) return 0;                          // less than two rounds of tiles: the tile kernels' finer grain wins
-    if (!(fill >= 0.88 || (N <= 128 && fill >= 0.70))) return 0;
+    if (tiles < 512) return LAUNCH_NOT_SERVED;                          // less than two rounds of tiles: the tile kernels' finer grain wins
+    if (!(fill >= 0.88 || (N <= 128 && fill >= 0.70))) return LAUNCH_NOT_SERVED;
   }
   const int tiny = v.tiny;
   if (N <= 64 && !v.halo_tile128) {  // 64-channel tiles (U2_CV_HALO_TILE128: the 128-channel tiles anyway, for A/B runs)

@@ -424,14 +424,14 @@ int launch_stream_cfg(ConvArgs& a, int N, int tiny, int forced, int code, hipStr
   const int lds_budget = (per_cu == 2 ? 80 : 160) * 1024;
   int ring = lds_budget / STAGE;
   if (ring > 8) ring = 8;
-  if (ring < 2) return 0;
+  if (ring < 2) return LAUNCH_NOT_SERVED;
   a.tiles_m = (a.M + TM - 1) / TM;
   a.tiles_n = (N + CBW * 64 - 1) / (CBW * 64);
   long long G = tiny ? 8LL * a.tiles_n : 256LL * per_cu;
-  if ((G >> 3) < a.tiles_n) return 0;   // (work-groups of an XCD beyond walkers x channel blocks stay idle)
+  if ((G >> 3) < a.tiles_n) return LAUNCH_NOT_SERVED;   // (work-groups of an XCD beyond walkers x channel blocks stay idle)
   // at least ~6 pixel tiles per work-group: shorter-lived launches (stride-32 maps, ROI heads) stay on the tile kernels, whose
   // finer (tile, K) grain fills the chip better there
-  if (!forced && !tiny && (long long)a.tiles_m * a.tiles_n < 6 * G) return 0;
+  if (!forced && !tiny && (long long)a.tiles_m * a.tiles_n < 6 * G) return LAUNCH_NOT_SERVED;
   static PerDeviceOnce attr_set;
   if (auto once_guard = attr_set.first()) {
     (void)hipFuncSetAttribute((const void*)conv_stream_kernel<KS, TM, PSW, NWV, KSS, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -440,7 +440,7 @@ int launch_stream_cfg(ConvArgs& a, int N, int tiny, int forced, int code, hipStr
   hipLaunchKernelGGL((conv_stream_kernel<KS, TM, PSW, NWV, KSS, TAIL>), dim3((unsigned)G), dim3(NWV * 64), (size_t)ring * STAGE, s, a, ring, t);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return -1000 - (int)e;
-  return 1;
+  return LAUNCH_TAKEN;
 }
 
 }  // namespace
@@ -458,12 +458,12 @@ static bool stream_allowed(const ConvVariant& v, bool& forced, int& tiny) {
 int launch_conv_stream(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_t s) {
   bool forced;
   int tiny;
-  if (!stream_allowed(v, forced, tiny)) return 0;
+  if (!stream_allowed(v, forced, tiny)) return LAUNCH_NOT_SERVED;
   if (a.remap_out || a.accumulate || a.ntaps != 1 || a.wt_taps != 1 || a.pad_h != 0 || a.pad_w != 0 || a.mul != 1 ||
       a.Hin != a.Hout || a.Win != a.Wout)
-    return 0;
-  if (!(C == 32 || C == 64 || C == 128 || C == 256) || (N & 7) || (a.out_ld & 7) || a.in_ld < C || a.M < 1) return 0;
-  if ((unsigned long long)a.M * a.in_ld * 2ull >= 0xffffffffull) return 0;
+    return LAUNCH_NOT_SERVED;
+  if (!(C == 32 || C == 64 || C == 128 || C == 256) || (N & 7) || (a.out_ld & 7) || a.in_ld < C || a.M < 1) return LAUNCH_NOT_SERVED;
+  if ((unsigned long long)a.M * a.in_ld * 2ull >= 0xffffffffull) return LAUNCH_NOT_SERVED;
   const int code = U2_K_STREAM + (C / 32) * 10;
   if (C == 64) {
     if (N > 128) return launch_stream_cfg<2, 128, 1, 4>(a, N, tiny, forced, code, s);
@@ -493,14 +493,14 @@ int launch_conv_stream(ConvArgs& a, int N, int C, const ConvVariant& v, hipStrea
 int launch_conv_stream_tail(ConvArgs& a, const TailArgs& t, int N, int C, const ConvVariant& v, hipStream_t s) {
   bool forced;
   int tiny;
-  if (!stream_allowed(v, forced, tiny)) return 0;
+  if (!stream_allowed(v, forced, tiny)) return LAUNCH_NOT_SERVED;
   if (a.remap_out || a.accumulate || a.relu || a.bias || a.ntaps != 1 || a.wt_taps != 1 || a.pad_h != 0 || a.pad_w != 0 ||
       a.mul != 1 || a.Hin != a.Hout || a.Win != a.Wout)
-    return 0;
-  if (!((C == 64 && N == 256) || (C == 128 && N == 512) || (C == 256 && N == 1024))) return 0;
-  if (a.out_ld != N || a.in_ld < C || (a.in_ld & 7) || a.M < 1) return 0;
-  if ((unsigned long long)a.M * a.in_ld * 2ull >= 0xffffffffull || (unsigned long long)a.M * N * 2ull >= 0xffffffffull) return 0;
-  if (!a.stats || !a.out || !t.g2 || !t.y || !t.bits || !t.mean || !t.invstd) return 0;
+    return LAUNCH_NOT_SERVED;
+  if (!((C == 64 && N == 256) || (C == 128 && N == 512) || (C == 256 && N == 1024))) return LAUNCH_NOT_SERVED;
+  if (a.out_ld != N || a.in_ld < C || (a.in_ld & 7) || a.M < 1) return LAUNCH_NOT_SERVED;
+  if ((unsigned long long)a.M * a.in_ld * 2ull >= 0xffffffffull || (unsigned long long)a.M * N * 2ull >= 0xffffffffull) return LAUNCH_NOT_SERVED;
+  if (!a.stats || !a.out || !t.g2 || !t.y || !t.bits || !t.mean || !t.invstd) return LAUNCH_NOT_SERVED;
   const int code = U2_K_STREAM + U2_K_STREAM_TAIL + (C / 32) * 10;
   a.abl = 0;
   if (C == 64) return launch_stream_cfg<2, 128, 1, 4, 2, true>(a, N, tiny, forced, code, s, t);

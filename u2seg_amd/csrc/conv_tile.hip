@@ -1,6 +1,7 @@
 // Persistent tile kernels of the implicit-GEMM convolution on CDNA4 MFMA (gfx950), bf16 in / fp32 accumulate.
 //
-// Same operation and argument block as conv_igemm.hip (F.conv2d / F.linear forward and data gradient behind
+// Same operation and argument block as conv_igemm.hip, which follows it in conv_api.hip's forward chain (F.conv2d /
+// F.linear forward and data gradient behind
 // detectron2/layers/wrappers.py:127-134, roi_heads/box_head.py:94-97, roi_heads/mask_head.py:287-290), restructured
 // around three facts measured on the round-1 kernels:
 //   * a work-group that stops at the end of its tile leaves the matrix pipe idle for the tile's prologue (first operands
@@ -882,7 +883,7 @@ int launch_cfg(ConvArgs& a, int N, int per_cu, int tiny_grid, hipStream_t s, int
   a.tiles_m = (a.M + TM - 1) / TM;
   a.tiles_n = (N + TN - 1) / TN;
   const long long T = (long long)a.tiles_m * a.tiles_n;
-  if (T >= (1 << 30)) return 0;
+  if (T >= (1 << 30)) return LAUNCH_NOT_SERVED;
   long long cap = tiny_grid ? (sk == 2 ? 24 : 8) : 256LL * per_cu;
   if constexpr (!ACC) {
     const long long nkh = (long long)a.ntaps * (a.C / (32 * KT));   // stages per tile
@@ -912,7 +913,7 @@ int launch_cfg(ConvArgs& a, int N, int per_cu, int tiny_grid, hipStream_t s, int
 #ifdef U2_TILE_TRACE
       tile_trace_end((int)Gs, s, "stream-K");
 #endif
-      return 1;
+      return LAUNCH_TAKEN;
     }
   }
   long long G = T < cap ? T : cap;
@@ -930,7 +931,7 @@ int launch_cfg(ConvArgs& a, int N, int per_cu, int tiny_grid, hipStream_t s, int
 #ifdef U2_TILE_TRACE
   tile_trace_end((int)G, s, "whole tiles");
 #endif
-  return 1;
+  return LAUNCH_TAKEN;
 }
 
 }  // namespace
@@ -947,12 +948,12 @@ int launch_conv_tile(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_
   int sel = v.tile_cfg;
   const int tiny = v.tiny;
   const int sk = (int)v.streamk;  // launch_cfg's `sk`
-  if (sel == U2_CV_TILE_CFG_NEVER) return 0;
-  if ((C & 31) || (N & 7) || (a.out_ld & 7) || a.ntaps < 1 || a.M >= (1 << 24) || a.M < 1) return 0;
+  if (sel == U2_CV_TILE_CFG_NEVER) return LAUNCH_NOT_SERVED;
+  if ((C & 31) || (N & 7) || (a.out_ld & 7) || a.ntaps < 1 || a.M >= (1 << 24) || a.M < 1) return LAUNCH_NOT_SERVED;
   // the accumulating epilogue exists for configuration 4 (256ch x 128px: the 1x1 conv3 of a residual block), no statistics
-  if (a.accumulate && (a.stats || a.remap_out || (sel != 0 && sel != 4) || N < 128)) return 0;
+  if (a.accumulate && (a.stats || a.remap_out || (sel != 0 && sel != 4) || N < 128)) return LAUNCH_NOT_SERVED;
   // 32-bit byte offsets inside the kernel
-  if ((unsigned long long)a.B * a.Hin * a.Win * a.in_ld * 2ull >= 0xffffffffull || (unsigned long long)N * a.wt_taps * C * 2ull >= 0xfffffff0ull) return 0;
+  if ((unsigned long long)a.B * a.Hin * a.Win * a.in_ld * 2ull >= 0xffffffffull || (unsigned long long)N * a.wt_taps * C * 2ull >= 0xfffffff0ull) return LAUNCH_NOT_SERVED;
   const int nkh = a.ntaps * (C >> 5);
   if (sel == 0) {
     // Automatic choice, from the per-layer A/B of tests/native/selftest bench2 on the shapes of the u2seg_R50_800 step
@@ -984,14 +985,14 @@ int launch_conv_tile(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_
       else if (K >= 1024 && N >= 256 && t256 > 256 && t256 < 768) sel = 1;
       else sel = 4;                                                // 1x1 layers: 256 ch x 128 px, two groups per CU
     }
-    if (sel == 0) return 0;
+    if (sel == 0) return LAUNCH_NOT_SERVED;
   }
-  if (sel > 7) return 0;
+  if (sel > 7) return LAUNCH_NOT_SERVED;
   if (sel == 7) {
-    if ((C & 63) || a.accumulate) return 0;
+    if ((C & 63) || a.accumulate) return LAUNCH_NOT_SERVED;
     const int nks = a.ntaps * (C >> 6);
     const long long T7 = (long long)((a.M + 255) / 256) * ((N + 255) / 256);
-    if (nks * (T7 < 256 ? 1 : T7 / 256) < 3) return 0;   // a work-group needs ring + 1 stages over all its tiles
+    if (nks * (T7 < 256 ? 1 : T7 / 256) < 3) return LAUNCH_NOT_SERVED;   // a work-group needs ring + 1 stages over all its tiles
     g_last_conv_kernel = U2_K_TILE + 7;
     return launch_cfg<4, 2, 2, false, 2>(a, N, 1, tiny, s, sk);
   }
@@ -999,14 +1000,14 @@ int launch_conv_tile(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_
   if (nkh < ring) {
     // a work-group only needs RING half tiles over ALL the tiles it walks; in automatic mode fall back to the ring-3
     // configurations (K >= 64 with two or more tiles per work-group, K >= 96 otherwise)
-    if (v.tile_cfg != 0) return 0;
-    if (a.accumulate && N <= 128) return 0;  // the accumulating epilogue exists for configuration 4 only
+    if (v.tile_cfg != 0) return LAUNCH_NOT_SERVED;
+    if (a.accumulate && N <= 128) return LAUNCH_NOT_SERVED;  // the accumulating epilogue exists for configuration 4 only
     sel = (N <= 128) ? 3 : 4;
     ring = 3;
     const int TN = sel == 3 ? 128 : 256, TM = sel == 3 ? 256 : 128;
     const long long T = (long long)((a.M + TM - 1) / TM) * ((N + TN - 1) / TN);
     const long long min_tiles = (T >> 3) / 64;  // 512 work-groups: 64 per XCD
-    if (nkh * min_tiles < ring) return 0;
+    if (nkh * min_tiles < ring) return LAUNCH_NOT_SERVED;
   }
   g_last_conv_kernel = U2_K_TILE + sel;
   // stream-K form (equal shares of the (tile, half K tile) sequence): automatic where whole tiles fill the last round badly
@@ -1018,7 +1019,7 @@ int launch_conv_tile(ConvArgs& a, int N, int C, const ConvVariant& v, hipStream_
     case 4: return a.accumulate ? launch_cfg<4, 1, 3, true>(a, N, 2, tiny, s) : launch_cfg<4, 1, 3>(a, N, 2, tiny, s, sk);
     case 5: return launch_cfg<2, 2, 4>(a, N, 1, tiny, s);
     case 6: return launch_cfg<1, 4, 4>(a, N, 1, tiny, s);
-    default: return 0;
+    default: return LAUNCH_NOT_SERVED;
   }
 }
 

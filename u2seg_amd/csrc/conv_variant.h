@@ -64,7 +64,7 @@ inline ConvVariant decode_conv_variant(unsigned w) {
 
 // the wgrad word
 struct WgradVariant {
-  // per-tap kernels (conv_igemm.hip)
+  // per-tap kernels (conv_wgrad.hip)
   bool reg_staging, scalar_gather;
   int fewer_splits, ring;
   Choice xcd, wide;      // force wins over forbid in both

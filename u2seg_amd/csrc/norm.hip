@@ -4,7 +4,7 @@
 //   detectron2/layers/batch_norm.py:169-197 (get_norm) and applied in
 //   detectron2/layers/wrappers.py:131-134, backbone/resnet.py:194-210 (residual add + relu_).
 // The batch statistics themselves (sum, sum of squares per channel) are produced by the conv
-// epilogue (conv_igemm.hip) or by u2_colstats below; cross-rank reduction (SyncBN) is an RCCL
+// epilogues (u2_conv_igemm with `stats`, every conv_*.hip family) or by u2_colstats below; cross-rank reduction (SyncBN) is an RCCL
 // all-reduce of the [2][C] sums issued by the host between the stats and finalize kernels.
 #include "common.h"
 #include "u2seg_hip.h"

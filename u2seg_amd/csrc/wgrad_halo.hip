@@ -2,7 +2,7 @@
 //
 //   dW[n][tap][c] += sum over output pixels m of dY[m][n] * X[m + tap offset][c]
 //
-// conv_wgrad_kernel (conv_igemm.hip) gives every (n-tile, c-tile, tap) its own work-group, so a pixel range is streamed
+// conv_wgrad_kernel (conv_wgrad.hip) gives every (n-tile, c-tile, tap) its own work-group, so a pixel range is streamed
 // 9 x tiles times and each 32-pixel step of a wave is only 16 MFMAs between two barriers.  Here a work-group owns a
 // 128(n) x 64(c) block of ALL NINE taps: per step it stages the 32 dY pixels once and the three input rows the taps touch
 // (34 pixels each), and multiplies them into 9 x 128 x 64 accumulators: 8 waves of 64(n) x 16(c) x 9 taps, 144 accumulator
@@ -362,24 +362,27 @@ __global__ __launch_bounds__(256) void wgrad_halo_reduce_kernel(const float* __r
 
 namespace u2conv {
 
-// returns 1 when the launch was taken, 0 when the shape is not served, -1000 - hipError_t on a launch failure
-int launch_wgrad_halo(const bf16_t* x, const bf16_t* dy, float* dw, long long dw_sn, int dw_st, int dw_sc, int n_valid,
-                      int c_valid, const bf16_t* zero, int B, int H, int W, int C, int x_ld, int N, int dy_ld, int rounds,
-                      int force, int part_mode, hipStream_t s) {
-  if (H < 2 || W < 11 || (C & 7) || (N & 7)) return 0;
-  const long long Mp = (long long)B * H * (W + 1);
-  if (Mp >= (1LL << 30)) return 0;
+// 3x3 / stride 1 / pad 1, automatic when a work-group gets enough positions to reduce (below); launcher convention of conv_args.h
+int launch_wgrad_halo(const WgradArgs& g, const WgradVariant& v, hipStream_t s) {
+  if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.pad_h != 1 || g.pad_w != 1 || g.Hin != g.Hout || g.Win != g.Wout)
+    return LAUNCH_NOT_SERVED;
+  if (v.halo == Choice::Never || v.per_tap_halo) return LAUNCH_NOT_SERVED;
+  const bool force = v.halo == Choice::Force;
+  const int part_mode = v.atomics ? 1 : (v.partials_force ? 2 : 0);
+  if (g.Hin < 2 || g.Win < 11 || (g.C & 7) || (g.N & 7)) return LAUNCH_NOT_SERVED;
+  const long long Mp = (long long)g.B * g.Hin * (g.Win + 1);
+  if (Mp >= (1LL << 30)) return LAUNCH_NOT_SERVED;
   WgradHaloArgs a;
-  a.x = x; a.dy = dy; a.dw = dw; a.dw_sn = dw_sn; a.dw_st = dw_st; a.dw_sc = dw_sc; a.n_valid = n_valid; a.c_valid = c_valid;
-  a.zero = zero;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.x_ld = x_ld; a.N = N; a.dy_ld = dy_ld;
+  a.x = g.x; a.dy = g.dy; a.dw = g.dw; a.dw_sn = g.dw_sn; a.dw_st = g.dw_st; a.dw_sc = g.dw_sc;
+  a.n_valid = g.n_valid; a.c_valid = g.c_valid; a.zero = g.zero;
+  a.B = g.B; a.H = g.Hin; a.W = g.Win; a.C = g.C; a.x_ld = g.x_ld; a.N = g.N; a.dy_ld = g.dy_ld;
   a.Mp = (int)Mp;
-  const int tiles_n = (n_valid + 127) / 128;
-  a.tiles_c = (c_valid + 63) / 64;
+  const int tiles_n = (a.n_valid + 127) / 128;
+  a.tiles_c = (a.c_valid + 63) / 64;
   a.tiles = tiles_n * a.tiles_c;
   // one work-group per CU and round; pixel splits in multiples of 8 (one per XCD), at least 16 steps each so that the
   // 288 KB atomic epilogue of a work-group stays small beside its reduction
-  if (rounds < 1) rounds = 1;
+  const int rounds = v.halo_rounds < 1 ? 1 : v.halo_rounds;
   int nsplit = (256 * rounds + a.tiles - 1) / a.tiles;
   nsplit = (nsplit + 7) & ~7;
   if (nsplit < 8) nsplit = 8;
@@ -397,7 +400,7 @@ int launch_wgrad_halo(const bf16_t* x, const bf16_t* dy, float* dw, long long dw
   // positions per work-group), which keep the atomics.
   const long long per_wg = Mp / nsplit;
   const bool use_part = part_mode == 2 ? nsplit >= 2 : (part_mode == 0 && per_wg < 16000 && nsplit >= 2);
-  if (!force && per_wg < (use_part ? 384 : 4000)) return 0;
+  if (!force && per_wg < (use_part ? 384 : 4000)) return LAUNCH_NOT_SERVED;
   int ppw = (int)((Mp + nsplit - 1) / nsplit);
   ppw = (ppw + HS - 1) / HS * HS;
   a.pix_per_wg = ppw;
@@ -406,7 +409,7 @@ int launch_wgrad_halo(const bf16_t* x, const bf16_t* dy, float* dw, long long dw
   a.part = nullptr;
   if (use_part) {
     a.part = (float*)scratch_get(2, s, (size_t)nsplit * a.tiles * PART_BLOCK * sizeof(float), (size_t)96 << 20, false);
-    if (!a.part && !force && per_wg < 4000) return 0;   // no scratch: the per-tap kernel takes the small maps
+    if (!a.part && !force && per_wg < 4000) return LAUNCH_NOT_SERVED;   // no scratch: the per-tap kernel takes the small maps
   }
   static PerDeviceOnce attr_set;
   if (auto once_guard = attr_set.first()) {
@@ -425,7 +428,8 @@ int launch_wgrad_halo(const bf16_t* x, const bf16_t* dy, float* dw, long long dw
     e = hipGetLastError();
     if (e != hipSuccess) return -1000 - (int)e;
   }
-  return 1;
+  g_last_conv_kernel = U2_K_WGRAD_HALO;
+  return LAUNCH_TAKEN;
 }
 
 }  // namespace u2conv

@@ -377,7 +377,7 @@ int launch_ws(WsArgs& a, int per_cu, int tiny, int code, hipStream_t s) {
   const int lds_budget = (per_cu == 2 ? 80 : 160) * 1024;
   int ring = lds_budget / STAGE;
   if (ring > 8) ring = 8;
-  if (ring < 2) return 0;
+  if (ring < 2) return LAUNCH_NOT_SERVED;
   a.ring = ring;
   // pixel ranges: one or two work-groups per CU in total, a multiple of 8 ranges (the tiles of a range share an XCD); never
   // fewer than 2 steps per range
@@ -393,26 +393,29 @@ int launch_ws(WsArgs& a, int per_cu, int tiny, int code, hipStream_t s) {
   hipLaunchKernelGGL((wgrad_stream_kernel<WN, WC, FN, FC, DG, AP>), dim3((unsigned)(ranges * tiles)), dim3(NWV * 64), (size_t)ring * STAGE, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return -1000 - (int)e;
-  return 1;
+  return LAUNCH_TAKEN;
 }
 
 }  // namespace
 
-// 1x1 / stride 1 / unpadded weight gradients; returns 1 when it took the launch, 0 when the shape is not served, < 0 on a launch
-// failure.  `force`: every shape it can serve (tests); otherwise the large maps only.  cfg (tests / A-B runs): 0 = automatic,
-// 1 = 256(n) x 64(c), 2 = 64 x 256, 3 = 128 x 128, 4 = 256 x 256 (8 waves).  g_last_conv_kernel code: 2700 + configuration.
-int launch_wgrad_stream(const bf16_t* x, const bf16_t* dy, float* dw, long long dw_sn, int dw_sc, int n_valid, int c_valid,
-                        const bf16_t* zero, int M, int C, int x_ld, int N, int dy_ld, int force, int tiny, int cfg, int per_cu,
-                        hipStream_t s) {
-  if ((C & 7) || (N & 7) || (x_ld & 7) || (dy_ld & 7) || M < 1 || n_valid < 1 || c_valid < 1) return 0;
-  if ((unsigned long long)M * (unsigned)x_ld * 2ull >= 0xffffffffull || (unsigned long long)M * (unsigned)dy_ld * 2ull >= 0xffffffffull) return 0;
+// 1x1 / stride 1 / unpadded weight gradients, launcher convention of conv_args.h.  v.stream == Force: every shape it can serve
+// (tests); otherwise the large maps only.  v.stream_cfg (tests / A-B runs): 0 = automatic, 1 = 256(n) x 64(c), 2 = 64 x 256,
+// 3 = 128 x 128, 4 = 256 x 256 (8 waves).  g_last_conv_kernel code: 2700 + configuration.
+int launch_wgrad_stream(const WgradArgs& g, const WgradVariant& v, hipStream_t s) {
+  if (g.KH * g.KW != 1 || g.stride != 1 || g.pad_h != 0 || g.pad_w != 0 || g.Hin != g.Hout || g.Win != g.Wout) return LAUNCH_NOT_SERVED;
+  if (v.stream == Choice::Never || v.per_tap_stream) return LAUNCH_NOT_SERVED;
+  const int M = g.M, n_valid = g.n_valid, c_valid = g.c_valid, tiny = v.stream_tiny, per_cu = v.stream_per_cu;
+  if ((g.C & 7) || (g.N & 7) || (g.x_ld & 7) || (g.dy_ld & 7) || M < 1 || n_valid < 1 || c_valid < 1) return LAUNCH_NOT_SERVED;
+  if ((unsigned long long)M * (unsigned)g.x_ld * 2ull >= 0xffffffffull || (unsigned long long)M * (unsigned)g.dy_ld * 2ull >= 0xffffffffull)
+    return LAUNCH_NOT_SERVED;
   WsArgs a;
-  a.x = x; a.dy = dy; a.dw = dw; a.dw_sn = dw_sn; a.dw_sc = dw_sc; a.n_valid = n_valid; a.c_valid = c_valid; a.zero = zero;
-  a.M = M; a.N = N; a.C = C; a.x_ld = x_ld; a.dy_ld = dy_ld;
+  a.x = g.x; a.dy = g.dy; a.dw = g.dw; a.dw_sn = g.dw_sn; a.dw_sc = g.dw_sc; a.n_valid = n_valid; a.c_valid = c_valid; a.zero = g.zero;
+  a.M = M; a.N = g.N; a.C = g.C; a.x_ld = g.x_ld; a.dy_ld = g.dy_ld;
   a.steps = (M + 31) / 32;
   a.wt = nullptr; a.dx = nullptr; a.wt_ld = a.dx_ld = 0; a.c_cover = 0;
   a.yn = nullptr; a.k1 = a.k2 = a.k3 = nullptr;
-  if (!force && M < 200000) return 0;   // >= ~25 steps per work-group: shorter launches stay on the tile kernels
+  if (v.stream != Choice::Force && M < 200000) return LAUNCH_NOT_SERVED;   // >= ~25 steps per work-group: shorter launches stay on the tile kernels
+  int cfg = v.stream_cfg;
   if (cfg == 0) {
     // the block shape follows the operands: the wider one along its 256, blocks beyond 256 x 256 are tiled (the narrower
     // operand is then re-read from L2 by the tiles of a range)
@@ -430,24 +433,24 @@ int launch_wgrad_stream(const bf16_t* x, const bf16_t* dy, float* dw, long long 
     case 2: return launch_ws<1, 4, 4, 4>(a, per_cu ? per_cu : 2, tiny, 2702, s);
     case 3: return launch_ws<2, 2, 4, 4>(a, per_cu ? per_cu : 2, tiny, 2703, s);
     case 4: return launch_ws<4, 2, 4, 8>(a, 1, tiny, 2704, s);
-    default: return 0;
+    default: return LAUNCH_NOT_SERVED;
   }
 }
 
 // The same launch with the data gradient fused in (wgrad_stream_kernel<.., DG>): dx[m][c] = sum_n dy[m][n] wt[c][n] for the 1x1 /
-// stride-1 layers whose block is all of N (<= 512) by 64 input channels.  Returns 1 when it took the launch, 0 when the shape is
-// not served (the caller runs the two separate launches), < 0 on a launch failure.  g_last_conv_kernel code: 2750 + N block / 256.
+// stride-1 layers whose block is all of N (<= 512) by 64 input channels.  Launcher convention of conv_args.h; not served: the
+// caller runs the two separate launches.  g_last_conv_kernel code: 2750 + N block / 256.
 // yn / k1..k3 (optional): dy is the gradient in front of a batch normalisation's apply step, evaluated on the fly (AP above).
 int launch_wdgrad_stream(const bf16_t* x, const bf16_t* dy, const bf16_t* wt, bf16_t* dx, float* dw, long long dw_sn, int dw_sc,
                          int n_valid, int c_valid, const bf16_t* zero, int M, int C, int x_ld, int N, int dy_ld, int wt_ld,
                          int dx_ld, const FusedBwdVariant& v, hipStream_t s, const bf16_t* yn, const float* k1, const float* k2,
                          const float* k3) {
-  if ((C & 7) || (N & 7) || (x_ld & 7) || (dy_ld & 7) || (wt_ld & 7) || (dx_ld & 7) || M < 1 || n_valid < 1 || c_valid < 1) return 0;
-  if (dx_ld < C || wt_ld < N) return 0;
-  if ((unsigned long long)M * (unsigned)x_ld * 2ull >= 0xffffffffull || (unsigned long long)M * (unsigned)dy_ld * 2ull >= 0xffffffffull) return 0;
+  if ((C & 7) || (N & 7) || (x_ld & 7) || (dy_ld & 7) || (wt_ld & 7) || (dx_ld & 7) || M < 1 || n_valid < 1 || c_valid < 1) return LAUNCH_NOT_SERVED;
+  if (dx_ld < C || wt_ld < N) return LAUNCH_NOT_SERVED;
+  if ((unsigned long long)M * (unsigned)x_ld * 2ull >= 0xffffffffull || (unsigned long long)M * (unsigned)dy_ld * 2ull >= 0xffffffffull) return LAUNCH_NOT_SERVED;
   const bool small = N <= 256 && C <= 64, wide = N > 256 && N <= 512 && C <= 128;
-  if (!small && !wide) return 0;
-  if (!v.force && (M < 200000 || n_valid <= 128)) return 0;
+  if (!small && !wide) return LAUNCH_NOT_SERVED;
+  if (!v.force && (M < 200000 || n_valid <= 128)) return LAUNCH_NOT_SERVED;
   const int tiny = v.tiny;
   WsArgs a;
   a.x = x; a.dy = dy; a.dw = dw; a.dw_sn = dw_sn; a.dw_sc = dw_sc; a.n_valid = n_valid; a.c_valid = c_valid; a.zero = zero;
@@ -459,11 +462,11 @@ int launch_wdgrad_stream(const bf16_t* x, const bf16_t* dy, const bf16_t* wt, bf
   if (yn) {
     // with the normalisation's apply step in front: two N-wide images per step, so only the 256-channel block (one 8-wave
     // work-group per CU, 40 KB stages, ring of 4); code 2761
-    if (!k1 || !k2 || !k3) return 0;
+    if (!k1 || !k2 || !k3) return LAUNCH_NOT_SERVED;
     // N <= 512 (res3 tails, 128 input channels = two c-tiles that each stage and transform dz and y): 72 KB stages, ring of 2;
     // code 2763.  Only on request (U2_WD_BN_WIDE): see the measurement in DESIGN.md 5.0 item 8
     if (wide) return v.bn_wide ? launch_ws<8, 1, 4, 4, true, true>(a, 1, tiny, 2763, s) : 0;
-    if (!small) return 0;
+    if (!small) return LAUNCH_NOT_SERVED;
     if (v.bn_two_groups) return launch_ws<4, 1, 4, 4, true, true>(a, 2, tiny, 2762, s);   // two 4-wave work-groups per CU, ring of 2
     return launch_ws<8, 1, 2, 4, true, true>(a, 1, tiny, 2761, s);
   }
