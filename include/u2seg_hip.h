@@ -533,7 +533,9 @@ int u2_batched_nms(const float* boxes, const int* group, const int* cnt, void* w
 /* ---- selection with a total order (select.hip) -----------------------------------------------
  * proposal_generator/proposal_utils.py:79-96 (per-level pre-NMS topk on the objectness logits, the score sort in front of
  * batched_nms) and modeling/sampling.py:38-54 in its "k smallest random keys" form.  Every row is ranked by
- * (value descending if largest else ascending, index ascending) - torch.topk leaves the order of ties open.
+ * (value descending if largest else ascending, index ascending) - torch.topk leaves the order of ties open.  Values compare
+ * as in torch.sort: -0.0 equals +0.0 and every NaN (either sign, any payload) is the greatest value; out_vals reports them as
+ * +0.0 and as the quiet NaN 0x7fc00000.
  *   vals: fp32 (dtype 0) or bf16 (dtype 1); element i of row r is vals[r * row_stride + (i / group) * pitch + i % group]
  *         (group = pitch = 1: contiguous rows; group = A, pitch = 32: the A valid columns of a 32-wide NHWC logit map);
  *   mask (optional, int8 [rows][n]): only elements with mask == mask_value take part;

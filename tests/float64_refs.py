@@ -1,6 +1,6 @@
 """Float64 reference helpers of tests/test_gpu_optim_resample_float64.py, tests/test_gpu_conv_float64.py,
 tests/test_gpu_inference_tails_float64.py, tests/test_gpu_box_decisions_float64.py, tests/test_gpu_kmeans_update_float64.py,
-tests/test_gpu_kmeans_assign_float64.py and (the streaming kernels' launch geometry) tests/test_gpu_tail_bwd_fused.py, in a plain module so that the CPU tests of
+tests/test_gpu_kmeans_assign_float64.py, tests/test_gpu_topk_rows.py and (the streaming kernels' launch geometry) tests/test_gpu_tail_bwd_fused.py, in a plain module so that the CPU tests of
 tests/test_float64_refs_host.py check exactly what the GPU tests use.  Plain torch ops only; nothing here touches the HIP
 library.  Every function works on whatever device its inputs live on."""
 import math
@@ -1466,3 +1466,58 @@ def kmeans_check_ladder(ref, n, d):
     assert all(cnt >= 32 for cnt in counts[1 if empty else 0:]) and undecidable <= 0.4, (counts, undecidable)
     assert not empty or counts[0] == 0
     return counts, undecidable
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# row-wise top-k with a total order (u2seg_amd/csrc/select.hip; tests/test_gpu_topk_rows.py, tests/topk_cases.py)
+# ----------------------------------------------------------------------------------------------------------------------------
+def topk_view(vals, n, group=1, pitch=1):
+    """The n elements of every row of vals [rows, ...] under the (group, pitch) view: element i at (i // group) * pitch + i % group."""
+    flat = vals.reshape(vals.shape[0], -1)
+    i = torch.arange(n)
+    return flat[:, (i // group) * pitch + i % group]
+
+
+def topk_rows_ref(vals, k, largest=True, mask=None, mask_value=1, group=1, pitch=1, n=None, idx_in=None, cnt=None, cnt_group=1,
+                  idx_mod=1, idx_mul=0):
+    """The contract of u2_topk_rows / u2_topk_rows_multi, in numpy on the CPU, one lexicographic sort per row.
+    vals: [rows, ...] fp32 or bf16, read through the (group, pitch) view.  The participants of a row are the elements with
+    mask == mask_value and, under cnt [rows, n // cnt_group], i % cnt_group < cnt[row][i // cnt_group].  Each is ranked by
+    (value, reported index ascending): values compare as reals (float64 holds every fp32 / bf16 exactly), -0 equal to +0, every
+    NaN of either sign the greatest value; `largest` reverses the value order only.  The reported index is idx_in[row][i]
+    (else i) + (row % idx_mod) * idx_mul.  Returned values are canonical: +0.0 for either zero, the quiet NaN 0x7fc00000 for
+    every NaN.  Past the count: index 0, value -inf (largest) or +inf.
+    Returns (values fp32 [rows, k], indices int32 [rows, k], counts int32 [rows])."""
+    import numpy as np
+
+    rows = vals.shape[0]
+    if n is None:
+        n = vals.reshape(rows, -1).shape[1]
+    v = topk_view(vals.cpu(), n, group, pitch).to(torch.float64).numpy()
+    nan = np.isnan(v)
+    v = np.where(nan, 0.0, v) + 0.0           # NaNs are ranked by their own key below; -0.0 + 0.0 = +0.0
+    out_v = np.full((rows, k), -np.inf if largest else np.inf, dtype=np.float32)
+    out_i = np.zeros((rows, k), dtype=np.int32)
+    out_c = np.zeros((rows,), dtype=np.int32)
+    pos = np.arange(n)
+    for r in range(rows):
+        part = np.ones(n, dtype=bool)
+        if mask is not None:
+            part &= mask[r].cpu().numpy() == mask_value
+        if cnt is not None:
+            part &= (pos % cnt_group) < cnt[r].cpu().numpy()[pos // cnt_group]
+        rep = (idx_in[r].cpu().numpy().astype(np.int64) if idx_in is not None else pos) + (r % idx_mod) * idx_mul
+        who = np.nonzero(part)[0]
+        # np.lexsort: the last key is the primary one.  Ascending in (NaN last, value, index); descending flips the first two.
+        if largest:
+            order = np.lexsort((rep[who], -v[r, who], ~nan[r, who]))
+        else:
+            order = np.lexsort((rep[who], v[r, who], nan[r, who]))
+        who = who[order][:k]
+        c = len(who)
+        out_c[r] = c
+        out_i[r, :c] = rep[who]
+        out_v[r, :c] = np.where(nan[r, who], np.float32(np.nan), v[r, who].astype(np.float32))
+    res = torch.from_numpy(out_v)
+    res.view(torch.int32)[torch.isnan(res)] = 0x7FC00000
+    return res, torch.from_numpy(out_i), torch.from_numpy(out_c)

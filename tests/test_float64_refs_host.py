@@ -929,3 +929,69 @@ def test_stream_production_geoms_are_in_steady_state():
         assert (geo["tiles_n"] > 1) == (cout == 520)
         # the smallest such count: one tile fewer leaves no walker with ring + 2 tiles
         assert max(R.walker_tiles(R.stream_geometry(cin, cout, m - 1, False))) == geo["ring"] + 1
+
+
+def _topk_rows(kind, rows, n, bf16, seed):
+    """Rows for the checks of topk_rows_ref: random, heavily tied, or full of NaNs of both signs, infinities and zeros of both
+    signs."""
+    g = torch.Generator().manual_seed(seed)
+    v = torch.randn((rows, n), generator=g)
+    if kind == "tied":
+        v = v.mul(2).round().div(2)
+    if kind == "special":
+        v = v.round()
+        pick = torch.randint(0, 12, (rows, n), generator=g)
+        bits = v.view(torch.int32)
+        for j, b in enumerate((0x7FC00000, -0x400000, 0x7F800001, -0x7FFFFF, 0x7F800000, -0x800000, -0x80000000)):
+            bits[pick == j] = b         # NaNs (+quiet, -quiet, +signalling, -signalling), +inf, -inf, -0.0
+    return v.bfloat16() if bf16 else v
+
+
+def _canonical(v):
+    """fp32 values as the selection returns them: +0.0 for -0.0, the quiet NaN for every NaN; as bit patterns."""
+    v = torch.where(torch.isnan(v), torch.full_like(v, float("nan")), v + 0.0)
+    return v.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+@pytest.mark.parametrize("kind", ["random", "tied", "special"])
+def test_topk_rows_ref_equals_a_stable_sort(kind, bf16):
+    """topk_rows_ref against torch.sort(stable=True), which ranks every NaN greatest and -0 equal to +0: the whole order
+    (k = n), a prefix, k beyond the row; the returned values are the gathered ones in canonical form."""
+    rows, n = 3, 1500
+    v = _topk_rows(kind, rows, n, bf16, 3)
+    if kind == "special":
+        assert bool((v.float().view(torch.int32) == -0x80000000).any()) and int(torch.isnan(v.float()).sum()) > 100
+    for largest in (True, False):
+        sv, si = torch.sort(v.float(), dim=1, descending=largest, stable=True)
+        for k in (n, 1, 37, n + 5):
+            rv, ri, rc = R.topk_rows_ref(v, k, largest)
+            m = min(k, n)
+            assert rc.tolist() == [m] * rows and torch.equal(ri[:, :m].long(), si[:, :m])
+            assert torch.equal(rv[:, :m].contiguous().view(torch.int32), _canonical(sv[:, :m]))
+            assert bool((ri[:, m:] == 0).all()) and bool((rv[:, m:] == (float("-inf") if largest else float("inf"))).all())
+
+
+@pytest.mark.parametrize("kind", ["tied", "special"])
+def test_topk_rows_ref_equals_the_sorted_fallback(kind):
+    """topk_rows_ref against layers.select._topk_rows_sorted on the CPU with the same specs: a mask that leaves rows with fewer
+    participants than k and with none, the (group, pitch) view of a 32-wide map, k below and beyond the row; bit for bit."""
+    from u2seg_amd.layers.select import _topk_rows_sorted
+
+    g = torch.Generator().manual_seed(9)
+    rows, n = 4, 2000
+    for bf16 in (False, True):
+        v = _topk_rows(kind, rows, n, bf16, 5)
+        mask = torch.randint(0, 3, (rows, n), generator=g).to(torch.int8)
+        mask[2] = 0
+        mask[3, 20:] = 0
+        m = _topk_rows(kind, 2, 700 * 32, True, 6).reshape(2, 700, 32)
+        specs = [dict(vals=v, k=k, largest=largest, mask=mk, mask_value=2) for k in (1, 300, n, n + 7) for largest in (True, False)
+                 for mk in (None, mask)]
+        specs += [dict(vals=m, k=k, largest=largest, group=gr, pitch=32, n=700 * gr) for k in (50, 2100) for largest in (True, False)
+                  for gr in (3, 5)]
+        for sp in specs:
+            fv, fi, fc = _topk_rows_sorted(sp)
+            rv, ri, rc = R.topk_rows_ref(**sp)
+            assert torch.equal(fc.int(), rc) and torch.equal(fi.int(), ri), (sp["k"], sp["largest"])
+            assert torch.equal(fv.contiguous().view(torch.int32), rv.view(torch.int32)), (sp["k"], sp["largest"])

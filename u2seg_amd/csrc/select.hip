@@ -6,11 +6,16 @@
 // unspecified (and bf16 objectness logits tie constantly); here every row is ranked by the total order
 //     (value descending [or ascending], index ascending),
 // which is what a stable sort gives and what the CPU oracle uses, so index lists are bit-exact and reproducible.
+// Values compare as torch.sort compares them: -0.0 equals +0.0 (and is returned as +0.0), and every NaN, of either sign and
+// any payload, is the greatest value (first when descending, last when ascending; returned as the quiet NaN 0x7fc00000);
+// among equal zeros and among NaNs the index decides.
 //
 // One work-group (1024 threads) per row.  The k-th element of the 64-bit key (ordered value bits : ~index) is found by
 // most-significant-digit radix selection, 8 bits per sweep with an LDS histogram: 2 sweeps for bf16 values, 4 for fp32,
 // plus up to 3 over the index bits only when the k-th value is tied; the survivors are compacted into LDS, bitonic-sorted
-// there and written out.  Rows are short (<= 268 569 elements, a few hundred KB): each sweep is an L2-resident stream.
+// there and written out.  Rows are short in production (<= 268 569 elements, a few hundred KB): each sweep is an L2-resident
+// stream.  The launcher accepts any n < 2^24 (the index takes 24 key bits, and the float-reciprocal division of the (group,
+// pitch) view is exact below that); tests/test_gpu_topk_rows.py runs n = 2^24 - 1.
 #include "common.h"
 #include "u2seg_hip.h"
 
@@ -46,15 +51,18 @@ struct SelectArgs {
 };
 
 // ordered key: larger = ranked earlier.  fp32 keeps all 32 bits; bf16 is ordered on its 16 bits and shifted up, so that the
-// low 16 key bits are zero for every element (the selection then skips them).  -0.0 ranks equal to +0.0, as in a sort.
+// low 16 key bits are zero for every element (the selection then skips them).  -0.0 ranks equal to +0.0, as in a sort, and
+// every NaN (either sign, any payload) becomes the positive quiet NaN, whose bits order above +inf: the greatest value.
 __device__ __forceinline__ uint32_t order_bits(uint32_t u, int largest, int is_bf16) {
   if (is_bf16) {
     uint32_t h = u & 0xffffu;
     if (h == 0x8000u) h = 0;
+    if ((h & 0x7fffu) > 0x7f80u) h = 0x7fc0u;
     const uint32_t asc = (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
     return (largest ? asc : (~asc & 0xffffu)) << 16;
   }
   if (u == 0x80000000u) u = 0;
+  if ((u & 0x7fffffffu) > 0x7f800000u) u = 0x7fc00000u;
   const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
   return largest ? asc : ~asc;
 }

@@ -132,7 +132,8 @@ def topk_rows_multi(specs):
 
 def _topk_rows_sorted(sp):
     """topk_rows for k beyond the kernel's limit: torch's stable sort on the device under the same total order (value descending /
-    ascending, index ascending; -0.0 equal to +0.0), same outputs (padding: index 0, value -/+ inf)."""
+    ascending, index ascending; -0.0 equal to +0.0, every NaN the greatest value), same outputs (zeros as +0.0, NaNs as the quiet
+    NaN; padding: index 0, value -/+ inf)."""
     vals, k, largest = sp["vals"], int(sp["k"]), bool(sp.get("largest", True))
     mask, mask_value = sp.get("mask"), int(sp.get("mask_value", 1))
     group, pitch, n = int(sp.get("group", 1)), int(sp.get("pitch", 1)), sp.get("n")
@@ -143,6 +144,8 @@ def _topk_rows_sorted(sp):
     if group != 1 or pitch != 1:
         v = v.reshape(rows, -1, pitch)[:, : n // group, :group].reshape(rows, n)
     v = v[:, :n].float()
+    # the kernel's canonical values, so that no sort backend can order them by bit pattern: -0.0 -> +0.0, any NaN -> quiet NaN
+    v = torch.where(v != v, torch.full_like(v, float("nan")), v + 0.0)
     fill = float("-inf") if largest else float("inf")
     part = torch.ones_like(v, dtype=torch.bool) if mask is None else (mask == mask_value)
     order = torch.sort(torch.where(part, v, torch.full_like(v, fill)), dim=1, descending=largest, stable=True)[1]
