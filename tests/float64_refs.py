@@ -1521,3 +1521,90 @@ def topk_rows_ref(vals, k, largest=True, mask=None, mask_value=1, group=1, pitch
     res = torch.from_numpy(out_v)
     res.view(torch.int32)[torch.isnan(res)] = 0x7FC00000
     return res, torch.from_numpy(out_i), torch.from_numpy(out_c)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# head losses (u2seg_amd/csrc/losses.hip; tests/test_gpu_losses_float64.py, tests/loss_cases.py): plain torch in float64 on the
+# bf16 / fp32 values the kernels read, from the formulas the header comment of losses.hip cites.  Each returns a dict: the loss
+# sum, the gradient before scaling and the pieces the derived bounds are made of.  They run on the inputs' device.
+# ----------------------------------------------------------------------------------------------------------------------------
+def softmax_ce_ref(z, labels, nc):
+    """cross_entropy(sum) over the first nc columns of z [R, LP] (fast_rcnn.py:344) and softmax - onehot."""
+    zz = z[:, :nc].to(F64)
+    mx = zz.amax(1, keepdim=True)
+    lse = mx + torch.log(torch.exp(zz - mx).sum(1, keepdim=True))
+    p = torch.exp(zz - lse)
+    oh = TF.one_hot(labels, nc).to(F64)
+    zt = zz.gather(1, labels[:, None])
+    rows = lse - zt
+    return dict(loss=rows.sum(), grad=p - oh, rows=rows, p=p, oh=oh, mx=mx, lse=lse, zt=zt, z=zz)
+
+
+def semseg_ce_ref(logits, target, nc, ignore=255):
+    """semantic_seg.py:255-267 with the sum in place of the mean: F.interpolate(x4, bilinear, align_corners=False) of the first nc
+    channels of logits [B, h, w, LP], cross_entropy(sum, ignore_index), the gradient through autograd.  Keeps the graph of `up`
+    (from the leaf `z` [B, nc, h, w]) so that a per-pixel bound can be sent through the transposed interpolation."""
+    z = logits[..., :nc].to(F64).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    up = TF.interpolate(z, scale_factor=4, mode="bilinear", align_corners=False)
+    t = target.long()
+    ce = TF.cross_entropy(up, t, ignore_index=ignore, reduction="sum")
+    (g,) = torch.autograd.grad(ce, z, retain_graph=True)
+    valid = t != ignore
+    return dict(loss=ce.detach(), grad=g.permute(0, 2, 3, 1), count=int(valid.sum()), z=z, up=up, target=t, valid=valid)
+
+
+def mask_bce_ref(x, w, b, cls, tgt, z=None):
+    """mask_head.py:258 + :33-112 with the sum in place of the mean: the gt class's channel of the 1x1 predictor (weights and bias
+    rounded to bf16, the autocast conv's operands) and BCE-with-logits.  x [N, P, C] in pixel order, w [K, C], b [K], cls [N],
+    tgt [N, P].  The loss and the gradients are taken at z [N, P] where given (the kernel's own rounded logit), else at the
+    float64 logit.  logit_abs (the dot product's, without the bias), dW_abs, db_abs: the sums of magnitudes of the same terms."""
+    k = w.shape[0]
+    xx, t = x.to(F64), tgt.to(F64)
+    wq, bq = bf16_round(w)[cls], bf16_round(b)[cls]                              # [N, C], [N]
+    logit = torch.einsum("npc,nc->np", xx, wq) + bq[:, None]
+    logit_abs = torch.einsum("npc,nc->np", xx.abs(), wq.abs())
+    z = logit if z is None else z.to(F64)
+    terms = z.clamp_min(0) - z * t + torch.log1p(torch.exp(-z.abs()))
+    g = torch.sigmoid(z) - t
+    put = lambda v: torch.zeros((k,) + v.shape[1:], dtype=F64, device=v.device).index_add_(0, cls, v)   # noqa: E731
+    return dict(logit=logit, logit_abs=logit_abs, z=z, terms=terms, loss=terms.sum(), g=g, wq=wq, dx=g[:, :, None] * wq[:, None, :],
+                dW=put(torch.einsum("np,npc->nc", g, xx)), dW_abs=put(torch.einsum("np,npc->nc", g.abs(), xx.abs())),
+                db=put(g.sum(1)), db_abs=put(g.abs().sum(1)))
+
+
+def rpn_level_ref(obj, dlt, labels, match, gt, anchors, a):
+    """rpn.py:366-429 for one level, sums: BCE-with-logits over the anchors labelled 0 / 1, L1 between the deltas and
+    get_deltas(anchor, matched gt; unit weights) over those labelled 1.  obj [B, HW, >= a], dlt [B, HW, >= 4 a] (the valid
+    columns first), labels / match [B, HW * a] of the level, gt [B, G, 4], anchors [HW * a, 4]."""
+    from tests.box_loss_refs import get_deltas
+
+    bsz, hw = obj.shape[0], obj.shape[1]
+    lab = labels.long().view(bsz, hw, a)
+    mt = match.long().view(bsz, hw, a)
+    zz = obj[..., :a].to(F64)
+    valid, pos = lab >= 0, lab == 1
+    t = lab.clamp_min(0).to(F64)
+    zero = torch.zeros_like(zz)
+    terms = torch.where(valid, zz.clamp_min(0) - zz * t + torch.log1p(torch.exp(-zz.abs())), zero)
+    dobj = torch.where(valid, torch.sigmoid(zz) - t, zero)
+    bi = torch.arange(bsz, device=obj.device)[:, None, None].expand(bsz, hw, a)
+    an = anchors.to(F64).view(hw, a, 4)[None].expand(bsz, hw, a, 4)
+    tg = get_deltas(an[pos], gt.to(F64)[bi[pos], mt[pos]], (1.0, 1.0, 1.0, 1.0))                       # [npos, 4]
+    pr = dlt[..., : 4 * a].to(F64).view(bsz, hw, a, 4)
+    df = pr[pos] - tg
+    ddlt = torch.zeros_like(pr)
+    ddlt[pos] = torch.sign(df)
+    src = anchors.view(hw, a, 4)[None].expand(bsz, hw, a, 4)[pos]      # the positives' anchors and boxes as the kernel reads them
+    return dict(loss_cls=terms.sum(), loss_loc=df.abs().sum(), terms=terms, dobj=dobj, ddlt=ddlt, df=df, tgt=tg, pred=pr[pos],
+                pos=pos, valid=valid, src=src, dst=gt[bi[pos], mt[pos]], z=zz, t=t)
+
+
+def box_l1_ref(pred, prop, gtb, labels, bg, weights):
+    """fast_rcnn.py:424-463 with smooth_l1(beta = 0), class agnostic, the sum: L1 between pred[:, :4] and
+    get_deltas(proposal, gt; weights) over the foreground rows (0 <= label < bg), and its sign."""
+    from tests.box_loss_refs import get_deltas
+
+    fg = (labels >= 0) & (labels < bg)
+    tg = get_deltas(prop.to(F64), gtb.to(F64), weights)
+    df = torch.where(fg[:, None], pred[:, :4].to(F64) - tg, torch.zeros_like(tg))
+    return dict(loss=df.abs().sum(), grad=torch.sign(df), df=df, tgt=tg, fg=fg)

@@ -995,3 +995,136 @@ def test_topk_rows_ref_equals_the_sorted_fallback(kind):
             rv, ri, rc = R.topk_rows_ref(**sp)
             assert torch.equal(fc.int(), rc) and torch.equal(fi.int(), ri), (sp["k"], sp["largest"])
             assert torch.equal(fv.contiguous().view(torch.int32), rv.view(torch.int32)), (sp["k"], sp["largest"])
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# head losses (tests/test_gpu_losses_float64.py): each reference against an independent formulation, float64 against float64
+# ----------------------------------------------------------------------------------------------------------------------------
+def _close12(got, ref, what):
+    scale = float(ref.abs().max()) if ref.numel() else 0.0
+    assert got.shape == ref.shape and float((got - ref).abs().max()) <= 1e-12 * max(scale, 1e-300), (
+        what, float((got - ref).abs().max()), scale)
+
+
+@pytest.mark.parametrize("case", [(5, 81, 88), (37, 11, 13), (9, 513, 520), (1, 2, 8)])
+def test_softmax_ce_ref_equals_autograd_of_cross_entropy(case):
+    from tests import loss_cases as C
+
+    z, lab = C.softmax_case(*case)
+    nc = case[1]
+    ref = R.softmax_ce_ref(z, lab, nc)
+    zz = z[:, :nc].to(F64).requires_grad_(True)
+    ce = TF.cross_entropy(zz, lab, reduction="sum")
+    ce.backward()
+    _close12(ref["loss"], ce.detach(), "loss")
+    _close12(ref["grad"], zz.grad, "grad")
+    _close12(ref["rows"][:, 0], TF.cross_entropy(zz.detach(), lab, reduction="none"), "rows")
+    assert float((ref["p"].sum(1) - 1).abs().max()) < 1e-12
+
+
+@pytest.mark.parametrize("case", [(3, 1, 1, 28, 32, 255, False), (1, 8, 1, 28, 32, 255, False), (3, 1, 16, 28, 32, 255, False),
+                                  (3, 8, 16, 17, 64, 255, False), (1, 8, 16, 28, 32, 255, True), (1, 7, 15, 28, 32, 0, False),
+                                  (3, 8, 16, 1, 8, 255, False)])
+def test_semseg_ce_ref_equals_two_tap_index_arithmetic(case):
+    """The loss, the count and the gradient from an explicit per-pixel two-tap interpolation (_source_index / _bilinear) and its
+    transpose written as four scatter-adds."""
+    from tests import loss_cases as C
+
+    b, h, w, nc, lp, ignore, sat = case
+    z, t = C.sem_case(*case)
+    ref = R.semseg_ce_ref(z, t, nc, ignore)
+    x = z[..., :nc].to(F64).permute(0, 3, 1, 2)
+    ys, xs = R._source_index(4 * h, h, 0.25), R._source_index(4 * w, w, 0.25)
+    up = R._bilinear(x, ys, xs)                                   # [b, nc, 4h, 4w]
+    _close12(ref["up"].detach(), up, "up")
+    tl = t.long()
+    valid = tl != ignore
+    lse = torch.logsumexp(up, 1)
+    zt = up.gather(1, tl.clamp_max(nc - 1)[:, None])[:, 0]
+    loss = torch.where(valid, lse - zt, torch.zeros_like(lse)).sum()
+    assert ref["count"] == int(valid.sum()) and 0 < ref["count"] < valid.numel()
+    _close12(ref["loss"], loss, "loss")
+    gp = torch.exp(up - lse[:, None]) - TF.one_hot(tl.clamp_max(nc - 1), nc).permute(0, 3, 1, 2).to(F64)
+    gp = gp * valid[:, None]
+    (y0, y1, ly), (x0, x1, lx) = ys, xs
+    gz = torch.zeros((b, nc, h, w), dtype=F64)
+    for yi, wy in ((y0, 1 - ly), (y1, ly)):
+        for xi, wx in ((x0, 1 - lx), (x1, lx)):
+            flat = (yi[:, None] * w + xi[None, :]).reshape(-1)
+            gz.view(b, nc, h * w).index_add_(2, flat, (gp * wy[:, None] * wx[None, :]).reshape(b, nc, -1))
+    _close12(ref["grad"], gz.permute(0, 2, 3, 1), "grad")
+
+
+@pytest.mark.parametrize("case", [(3, 7, False, 5), (2, 12, True, 80), (1, 2, False, 1)])
+def test_mask_bce_ref_equals_bce_with_logits_of_conv2d(case):
+    from tests import loss_cases as C
+
+    n, side, _, k = case
+    x, w, bias, cls, tgt = C.mask_case(*case)
+    ref = R.mask_bce_ref(x, w, bias, cls, tgt)
+    xd = x.to(F64).view(n, side, side, -1).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    wd = R.bf16_round(w).view(k, -1, 1, 1).requires_grad_(True)
+    bd = R.bf16_round(bias).requires_grad_(True)
+    conv = TF.conv2d(xd, wd, bd)                                                        # [n, k, side, side]
+    sel = conv[torch.arange(n), cls].reshape(n, -1)
+    _close12(ref["logit"], sel.detach(), "logit")
+    loss = TF.binary_cross_entropy_with_logits(sel, tgt.to(F64), reduction="sum")
+    loss.backward()
+    _close12(ref["loss"], loss.detach(), "loss")
+    _close12(ref["dx"], xd.grad.permute(0, 2, 3, 1).reshape(n, side * side, -1), "dx")
+    _close12(ref["dW"], wd.grad.view(k, -1), "dW")
+    _close12(ref["db"], bd.grad, "db")
+    # the magnitude sums bound their sums; at a given z the loss moves with it
+    assert bool((ref["logit_abs"] + R.bf16_round(bias)[cls].abs()[:, None] >= ref["logit"].abs()).all())
+    assert bool((ref["dW_abs"] >= ref["dW"].abs() - 1e-15).all())
+    z = R.rne_bf16(ref["logit"])
+    at = R.mask_bce_ref(x, w, bias, cls, tgt, z)
+    _close12(at["loss"], TF.binary_cross_entropy_with_logits(z, tgt.to(F64), reduction="sum"), "loss at z")
+    # phases: the re-ordering is a permutation and its own inverse pair
+    if side % 2 == 0:
+        assert torch.equal(C.from_phases(C.to_phases(x, side), side), x)
+        s = side // 2
+        p = ((3 % s) * s + (1 % s)) * 4 + 2 + 1
+        assert torch.equal(C.to_phases(x, side)[:, p], x[:, (2 * (3 % s) + 1) * side + 2 * (1 % s) + 1])
+
+
+@pytest.mark.parametrize("case", [(3, 255, 2, 8, 16, False), (2, 257, 3, 16, 0, True), (1, 1, 1, 8, 16, False), (2, 64, 4, 8, 16, False)])
+def test_rpn_level_ref_equals_the_oracle_statement(case):
+    """The statement of test_rpn_loss (tests/test_gpu_parity.py), in float64: oracle.ops.get_deltas on the anchors and the
+    matched boxes, L1 over the positives, BCE-with-logits over the labelled anchors, autograd."""
+    from oracle import ops as O
+    from tests import loss_cases as C
+
+    c = C.rpn_case(*case)
+    a, bsz = c["a"], case[0]
+    o, d, lab, mt = C.rpn_views(c)
+    ref = R.rpn_level_ref(o, d, lab, mt, c["gt"], c["anchors"], a)
+    oc = o.to(F64).reshape(bsz, -1).requires_grad_(True)
+    dc = d.to(F64).reshape(bsz, -1, 4).requires_grad_(True)
+    lab = lab.long()
+    pos, valid = lab == 1, lab >= 0
+    tgt = torch.stack([O.get_deltas(c["anchors"].to(F64), c["gt"][b].to(F64)[mt[b].long()], (1.0, 1.0, 1.0, 1.0)) for b in range(bsz)])
+    loc = (dc[pos] - tgt[pos]).abs().sum()
+    cls = TF.binary_cross_entropy_with_logits(oc[valid], lab[valid].to(F64), reduction="sum")
+    (cls + loc).backward()
+    _close12(ref["loss_cls"], cls.detach(), "cls")
+    _close12(ref["loss_loc"], loc.detach(), "loc")
+    _close12(ref["dobj"].reshape(bsz, -1), oc.grad, "dobj")
+    assert torch.equal(ref["ddlt"].reshape(bsz, -1, 4), dc.grad)
+    assert int(pos.sum()) > 0 and int((~valid).sum()) > 0 or bsz == 1
+
+
+@pytest.mark.parametrize("weights", R.CASCADE_WEIGHTS)
+def test_box_l1_ref_equals_the_oracle_get_deltas(weights):
+    from oracle import ops as O
+    from tests import loss_cases as C
+
+    pred, prop, gt, lab, _ = C.box_case(257, 32, False, weights)
+    ref = R.box_l1_ref(pred, prop, gt, lab, C.BOX_BG, weights)
+    fg = lab < C.BOX_BG
+    pd = pred[:, :4].to(F64).requires_grad_(True)
+    loss = (pd[fg] - O.get_deltas(prop.to(F64), gt.to(F64), weights)[fg]).abs().sum()
+    loss.backward()
+    _close12(ref["loss"], loss.detach(), "loss")
+    assert torch.equal(ref["grad"], pd.grad) and torch.equal(ref["fg"], fg) and 0 < int(fg.sum()) < 257
+    assert list(C.BOX_WEIGHTS) == list(R.CASCADE_WEIGHTS)
