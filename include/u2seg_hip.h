@@ -862,6 +862,21 @@ int u2_aug_resize_nearest_u8(const void* block, long long block_bytes, const voi
 int u2_aug_rle_masks(const void* block, long long block_bytes, const void* tables_host, void* mask_out,
                      long long mask_out_bytes, int* counts, int num_counts, const U2AugImage* images, int num_images,
                      void* stream);
+/* The same decode through a window of a larger annotation (INPUT.CROP), with the tight box of what was
+ * written.  windows: HOST array, one per image.  Mask m of image i is a run-length code over mask_h x mask_w, column-major;
+ * the descriptor's (h, w) is the size of the window, its nx / ny index the window, and output pixel (y, x) reads position
+ * p = (x0 + nx[x]) * mask_h + y0 + ny[y].  mask_out and counts as above.  boxes: int32 [num_counts][4] on the device,
+ * boxes[first_mask + m] = (min x, min y, max x + 1, max y + 1) over the 1 bytes written, (0, 0, 0, 0) when there are none;
+ * cleared by the call.  Integer min / max only: no result depends on an order.  The walk's waves send atomic minima / maxima
+ * (the maxima with the + 1) into boxes preset to (INT_MAX, INT_MAX, 0, 0); a short second kernel on the same stream then zeroes
+ * the boxes of the masks without a pixel - a second pass, not an encoding.
+ * Checked on the host before anything is launched (status -1, for the run ends -2): x0, y0 >= 0, x0 + w <= mask_w,
+ * y0 + h <= mask_h, mask_h * mask_w < 2^31, every mask's last run end == mask_h * mask_w, boxes not NULL where there are masks.
+ * With the window (0, 0, h, w) mask_out and counts are those of u2_aug_rle_masks. */
+typedef struct U2AugWindow { int x0, y0, mask_h, mask_w; } U2AugWindow;
+int u2_aug_rle_masks_boxes(const void* block, long long block_bytes, const void* tables_host, void* mask_out,
+                           long long mask_out_bytes, int* counts, int* boxes, int num_counts, const U2AugImage* images,
+                           const U2AugWindow* windows, int num_images, void* stream);
 
 /* ---- optimizer (optim.hip): solver/build.py:36-37,63-73,119-139 ------------------------------- */
 int u2_sgd_clip_step(float* params, const float* grads, float* momentum_buf, const int* chunk_tensor,

@@ -7,7 +7,10 @@ Prints one JSON line per worker count; the training step consumes ~197 img/s per
 --device-mapper: every worker count runs twice in the same process, the host mapper first and then the DeviceMapper whose raw
 records DevicePrefetcher finishes on the GPU; also prints the mapper time per image in one process for
 both mappers, the bytes per batch that cross the shared-memory slot, and the HIP-event time of the three augmentation calls on
-a full per-GPU batch.  --out FILE collects every line into one JSON file."""
+a full per-GPU batch, and of the two mask entries (u2_aug_rle_masks, u2_aug_rle_masks_boxes with the whole image as its window)
+on one identical batch of 16 uncropped records.  --crop TYPE H W: the same runs with INPUT.CROP enabled,
+so that the host-mapper and device-mapper img/s stand side by side for every worker count.
+--out FILE collects every line into one JSON file."""
 import argparse
 import json
 import os
@@ -94,11 +97,15 @@ def kernel_times(cfg, dicts, device, batch_size, repeats=20):
     counts = torch.empty(max(masks, 1), dtype=torch.int32, device=device)
     need = int(_hip.call_nostream("u2_aug_resize_bilinear_scratch_bytes", descs, n))
     scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    windows = dm.describe_windows(dev)  # None without a crop: the batch takes the plain mask entry, like launch_batch
+    boxes = torch.empty((max(masks, 1), 4), dtype=torch.int32, device=device)
     calls = [("bilinear", lambda: _hip.call("u2_aug_resize_bilinear_u8", block, nbytes, host.data_ptr(), image, img_bytes, scratch,
                                              need, descs, n)),
              ("nearest", lambda: _hip.call("u2_aug_resize_nearest_u8", block, nbytes, host.data_ptr(), labels, lab_elems, descs, n)),
              ("rle_masks", lambda: _hip.call("u2_aug_rle_masks", block, nbytes, host.data_ptr(), mask_out, mask_bytes, counts,
-                                              masks, descs, n))]
+                                              masks, descs, n)) if windows is None else
+             ("rle_masks_boxes", lambda: _hip.call("u2_aug_rle_masks_boxes", block, nbytes, host.data_ptr(), mask_out, mask_bytes,
+                                                    counts, boxes, masks, descs, windows, n))]
     times = {name: [] for name, _ in calls}
     for it in range(repeats + 3):
         for name, fn in calls:
@@ -115,6 +122,51 @@ def kernel_times(cfg, dicts, device, batch_size, repeats=20):
     return out
 
 
+def mask_entry_times(cfg, dicts, device, batch_size=16, repeats=20, warmup=5):
+    """HIP-event time of u2_aug_rle_masks and of u2_aug_rle_masks_boxes (window = the whole image) on one identical batch of
+    uncropped raw records at the training size, alternating in one process (ms per call, median of `repeats` after `warmup`)."""
+    from u2seg_amd import _hip
+    from u2seg_amd.data import device_mapper as dm
+    from u2seg_amd.data.slots import layout_batch, unpack, write_batch
+
+    cfg = cfg.clone()
+    cfg.merge_from_list(["INPUT.CROP.ENABLED", False])
+    np.random.seed(0)
+    mapper = dm.DeviceMapper(cfg, True)
+    records = [mapper(dicts[i % len(dicts)]) for i in range(batch_size)]
+    staged, nbytes, samples = layout_batch(records)
+    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    write_batch(host.numpy(), staged)
+    block = host.to(device)
+    dev = unpack(block, samples)
+    descs, _, _, mask_bytes, masks = dm.describe_batch(dev, block.data_ptr())
+    windows = (dm._AugWindow * len(dev))()
+    for win, d in zip(windows, dev):
+        win.x0, win.y0, win.mask_h, win.mask_w = 0, 0, d[dm.RAW_KEY]["h"], d[dm.RAW_KEY]["w"]
+    outs = [torch.zeros(max(mask_bytes, 1), dtype=torch.bool, device=device) for _ in range(2)]  # (the alignment gaps are never written)
+    counts = [torch.empty(max(masks, 1), dtype=torch.int32, device=device) for _ in range(2)]
+    boxes = torch.empty((max(masks, 1), 4), dtype=torch.int32, device=device)
+    calls = [("rle_masks", lambda: _hip.call("u2_aug_rle_masks", block, nbytes, host.data_ptr(), outs[0], mask_bytes, counts[0],
+                                              masks, descs, len(dev))),
+             ("rle_masks_boxes", lambda: _hip.call("u2_aug_rle_masks_boxes", block, nbytes, host.data_ptr(), outs[1], mask_bytes,
+                                                    counts[1], boxes, masks, descs, windows, len(dev)))]
+    times = {name: [] for name, _ in calls}
+    for it in range(repeats + warmup):
+        for name, fn in calls:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if it >= warmup:
+                times[name].append(e0.elapsed_time(e1))
+    assert torch.equal(outs[0], outs[1]) and torch.equal(counts[0], counts[1])
+    out = {name: round(float(np.median(v)), 4) for name, v in times.items()}
+    out.update({name + "_min_max": [round(float(min(v)), 4), round(float(max(v)), 4)] for name, v in times.items()})
+    out.update({"images": len(dev), "masks": masks, "mask_bytes": mask_bytes})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=48)
@@ -124,6 +176,8 @@ def main():
     ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--device-mapper", action="store_true", help="run every worker count with the host mapper and with the "
                     "DeviceMapper (needs a GPU: there is no host fallback)")
+    ap.add_argument("--crop", nargs=3, metavar=("TYPE", "H", "W"), default=None, help="enable INPUT.CROP with this TYPE and SIZE "
+                    "(relative_range 0.9 0.9, absolute 512 512, ...)")
     ap.add_argument("--out", default=None, help="also write every result line into this JSON file")
     a = ap.parse_args()
     if a.device_mapper and not a.device.startswith("cuda"):
@@ -144,6 +198,10 @@ def main():
     register_all_coco(root)
     cfg = get_cfg()
     cfg.merge_from_file(os.path.join(ROOT, "configs", "COCO-PanopticSegmentation", "u2seg_R50_800.yaml"))
+    if a.crop:
+        size = [float(v) if a.crop[0].startswith("relative") else int(v) for v in a.crop[1:]]
+        cfg.merge_from_list(["INPUT.CROP.ENABLED", True, "INPUT.CROP.TYPE", a.crop[0], "INPUT.CROP.SIZE", size])
+    emit({"crop": [a.crop[0]] + size if a.crop else None})
     emit({"dataset": "%d synthetic JPEGs 480x640 / 640x480, 7 RLE instances each" % a.images,
           "build_s": round(time.time() - t0, 1), "short_edges": list(cfg.INPUT.MIN_SIZE_TRAIN)})
     if a.device_mapper:
@@ -155,6 +213,8 @@ def main():
                   "ms_per_image": round(mapper_ms_per_image(cfg, dm_on, dicts), 2)})
         emit(dict({"metric": "augmentation kernels, HIP-event ms per batch"},
                   **kernel_times(cfg, dicts, a.device, cfg.SOLVER.IMS_PER_BATCH)))
+        emit(dict({"metric": "mask entries on one identical uncropped batch, window = whole image, HIP-event ms per call"},
+                  **mask_entry_times(cfg, dicts, a.device)))
     for nw, dm_on in [(nw, dm_on) for nw in a.workers for dm_on in ((False, True) if a.device_mapper else (False,))]:
         cfg.defrost()
         cfg.merge_from_list(["DATALOADER.NUM_WORKERS", nw])

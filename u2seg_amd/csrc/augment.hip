@@ -7,7 +7,10 @@
 // mask kernel cannot do that without a search per byte: there a thread owns a column, searches the run of its first pixel and
 // walks, and a wave-instruction stores 64 contiguous bytes of a row.
 // Everything is integer work: no result depends on the order of an addition.
+// With INPUT.CROP the mask kernel reads its code through a window and also reduces the tight box of what it writes (integer
+// wave min / max, one atomic per coordinate per wave); a short second kernel on the same stream puts the empty masks' boxes right.
 #include <algorithm>
+#include <climits>
 
 #include "common.h"
 #include "u2seg_hip.h"
@@ -152,27 +155,31 @@ __global__ __launch_bounds__(AG_THREADS) void aug_nearest_kernel(const AugBatch 
 // grid (column blocks x row chunks of the largest image, masks of the image with most, images); a thread owns output column x
 // and walks AG_ROWS rows: j = number of run ends <= p is found by bisection for its first pixel and followed in both
 // directions afterwards (ny is monotone for a resize and a flip, so the walk is short; any table gives the right answer).
-__global__ __launch_bounds__(AG_THREADS) void aug_rle_masks_kernel(const AugBatch batch, const uint8_t* __restrict__ block,
-                                                                    uint8_t* __restrict__ mask_out, int* __restrict__ counts,
-                                                                    int col_blocks) {
-  const U2AugImage& im = batch.im[blockIdx.z].d;
+// The code is one of mask_h x mask_w read through the window at (wx0, wy0); the plain decode is the window (0, 0) of an h x w code.
+// BOXES: the tight box of the 1 bytes.  A lane's candidate is its column and the first and last set row of its walk; a wave
+// that saw a set pixel reduces the four coordinates and sends one atomic min / max each (boxes: (INT_MAX, INT_MAX, 0, 0) before,
+// x1 / y1 carry the + 1; aug_boxes_kernel behind it puts the empty masks right).
+template <bool BOXES>
+__device__ __forceinline__ void rle_masks_walk(const U2AugImage& im, int wx0, int wy0, int mask_h, const uint8_t* __restrict__ block,
+                                               uint8_t* __restrict__ mask_out, int* __restrict__ counts, int* __restrict__ boxes,
+                                               int col_blocks) {
   const int m = (int)blockIdx.y;
   const int cb = (int)blockIdx.x % col_blocks, rc = (int)blockIdx.x / col_blocks;
   const int x = cb * AG_THREADS + (int)threadIdx.x, y0 = rc * AG_ROWS;
   if (m >= im.num_masks || cb * AG_THREADS >= im.W || y0 >= im.H) return;
-  const int H = im.H, W = im.W, h = im.h;
+  const int H = im.H, W = im.W;
   const int* tab = reinterpret_cast<const int*>(block);
   const int* offs = tab + im.mask_offs;
   const unsigned* ends = reinterpret_cast<const unsigned*>(tab) + im.ends_base + offs[m];
   const int nruns = offs[m + 1] - offs[m];
   const int* ny = tab + im.ny;
-  int ones = 0;
+  int ones = 0, first = INT_MAX, last = -1;
   if (x < W) {
-    const unsigned colbase = (unsigned)tab[im.nx + x] * (unsigned)h;
+    const unsigned colbase = (unsigned)(wx0 + tab[im.nx + x]) * (unsigned)mask_h + (unsigned)wy0;
     const int y1 = min(y0 + AG_ROWS, H);
     uint8_t* dst = mask_out + im.mask_out_offset + ((long long)m * H + y0) * W + x;
     unsigned p = colbase + (unsigned)ny[y0];
-    int lo = 0, hi = nruns;                                      // first j with ends[j] > p; ends[nruns - 1] == h * w > p
+    int lo = 0, hi = nruns;                                      // first j with ends[j] > p; ends[nruns - 1] == mask_h * mask_w > p
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
       if (ends[mid] <= p) lo = mid + 1; else hi = mid;
@@ -186,10 +193,56 @@ __global__ __launch_bounds__(AG_THREADS) void aug_rle_masks_kernel(const AugBatc
       *dst = (uint8_t)v;
       dst += W;
       ones += v;
+      if (BOXES && v) {
+        first = min(first, y);
+        last = y;
+      }
     }
   }
+  const int mine = ones;
   ones = wave_isum(ones);
-  if ((threadIdx.x & 63) == 0 && ones) atomicAdd(&counts[im.first_mask + m], ones);
+  if (!ones) return;                                             // the same for every lane of the wave
+  if (BOXES) {
+    const int bx0 = wave_imin(mine ? x : INT_MAX), bx1 = wave_imax(mine ? x + 1 : 0);
+    const int by0 = wave_imin(first), by1 = wave_imax(last + 1);
+    if ((threadIdx.x & 63) == 0) {
+      int* b = boxes + 4LL * (im.first_mask + m);
+      atomicMin(b + 0, bx0);
+      atomicMin(b + 1, by0);
+      atomicMax(b + 2, bx1);
+      atomicMax(b + 3, by1);
+    }
+  }
+  if ((threadIdx.x & 63) == 0) atomicAdd(&counts[im.first_mask + m], ones);
+}
+
+__global__ __launch_bounds__(AG_THREADS) void aug_rle_masks_kernel(const AugBatch batch, const uint8_t* __restrict__ block,
+                                                                    uint8_t* __restrict__ mask_out, int* __restrict__ counts,
+                                                                    int col_blocks) {
+  const U2AugImage& im = batch.im[blockIdx.z].d;
+  rle_masks_walk<false>(im, 0, 0, im.h, block, mask_out, counts, nullptr, col_blocks);
+}
+
+struct AugWindows { U2AugWindow w[AG_MAXIMG]; };
+
+__global__ __launch_bounds__(AG_THREADS) void aug_rle_masks_boxes_kernel(const AugBatch batch, const AugWindows windows,
+                                                                          const uint8_t* __restrict__ block,
+                                                                          uint8_t* __restrict__ mask_out, int* __restrict__ counts,
+                                                                          int* __restrict__ boxes, int col_blocks) {
+  const U2AugWindow& win = windows.w[blockIdx.z];
+  rle_masks_walk<true>(batch.im[blockIdx.z].d, win.x0, win.y0, win.mask_h, block, mask_out, counts, boxes, col_blocks);
+}
+
+// before the walk (finish == 0): every box (INT_MAX, INT_MAX, 0, 0); behind it (finish == 1): a box no wave touched is zeros
+__global__ void aug_boxes_kernel(int* __restrict__ boxes, int n, int finish) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int4* b = reinterpret_cast<int4*>(boxes) + i;
+  if (!finish) {
+    *b = make_int4(INT_MAX, INT_MAX, 0, 0);
+  } else if (b->z == 0) {
+    *b = make_int4(0, 0, 0, 0);
+  }
 }
 
 // ---- host side: the contract, checked on the host copy of the tables ----------------------------------------------------
@@ -349,9 +402,10 @@ extern "C" int u2_aug_resize_nearest_u8(const void* block, long long block_bytes
   return 0;
 }
 
-extern "C" int u2_aug_rle_masks(const void* block, long long block_bytes, const void* tables_host, void* mask_out,
-                                long long mask_out_bytes, int* counts, int num_counts, const U2AugImage* images, int num_images,
-                                void* stream) {
+// The two mask entries: windows == nullptr is the plain decode (no boxes), otherwise the windowed one with boxes.
+static int rle_masks_launch(const void* block, long long block_bytes, const void* tables_host, void* mask_out,
+                            long long mask_out_bytes, int* counts, int* boxes, int num_counts, const U2AugImage* images,
+                            const U2AugWindow* windows, int num_images, void* stream) {
   if (num_images <= 0) return num_images < 0 ? -1 : 0;
   if (!images || !block_ok(block, block_bytes, tables_host) || num_counts < 0) return -1;
   const Tables tb{(const int*)tables_host, block_bytes / 4};
@@ -359,8 +413,17 @@ extern "C" int u2_aug_rle_masks(const void* block, long long block_bytes, const 
   for (int i = 0; i < num_images; ++i) {
     const U2AugImage& im = images[i];
     if (!geometry_ok(im)) return -1;
+    long long code = (long long)im.h * im.w;
+    if (windows) {
+      const U2AugWindow& win = windows[i];
+      if (win.x0 < 0 || win.y0 < 0 || win.mask_h < 1 || win.mask_w < 1) return -1;
+      if ((long long)win.x0 + im.w > win.mask_w || (long long)win.y0 + im.h > win.mask_h) return -1;
+      code = (long long)win.mask_h * win.mask_w;
+      if (code >= (1LL << 31)) return -1;
+    }
     if (im.num_masks == 0) continue;
     if (im.num_masks > 65535 || !mask_out || !counts) return -1;
+    if (windows && (!boxes || ((uintptr_t)boxes & 15))) return -1;
     int rc = nearest_axis_ok(tb, im.nx, im.W, im.w);
     if (rc) return rc;
     rc = nearest_axis_ok(tb, im.ny, im.H, im.h);
@@ -369,7 +432,7 @@ extern "C" int u2_aug_rle_masks(const void* block, long long block_bytes, const 
     const long long out_bytes = (long long)im.num_masks * im.H * im.W;
     if (im.mask_out_offset < 0 || out_bytes > mask_out_bytes || im.mask_out_offset > mask_out_bytes - out_bytes) return -1;
     if (!tb.has(im.mask_offs, (long long)im.num_masks + 1)) return -1;
-    const unsigned hw = (unsigned)((long long)im.h * im.w);
+    const unsigned hw = (unsigned)code;
     for (int m = 0; m < im.num_masks; ++m) {
       const long long o0 = tb.t[im.mask_offs + m], o1 = tb.t[im.mask_offs + m + 1];
       if (im.ends_base < 0 || im.ends_base > tb.n || o0 < 0 || o1 <= o0 || !tb.has(im.ends_base + o0, o1 - o0)) return -2;
@@ -385,14 +448,27 @@ extern "C" int u2_aug_rle_masks(const void* block, long long block_bytes, const 
     u2_zero_words(counts, (size_t)num_counts, s);
     U2_CHECK_LAUNCH();
   }
-  if (!masks) return 0;
+  if (!masks) {
+    if (windows && boxes && num_counts > 0) {                     // rows nobody owns: cleared like the counts
+      u2_zero_words(boxes, 4 * (size_t)num_counts, s);
+      U2_CHECK_LAUNCH();
+    }
+    return 0;
+  }
+  if (windows) {
+    hipLaunchKernelGGL(aug_boxes_kernel, dim3((unsigned)((num_counts + AG_THREADS - 1) / AG_THREADS)), dim3(AG_THREADS), 0, s, boxes,
+                       num_counts, 0);
+    U2_CHECK_LAUNCH();
+  }
   for (int i0 = 0; i0 < num_images; i0 += AG_MAXIMG) {
     AugBatch b;
+    AugWindows wb;
     const int nb = num_images - i0 < AG_MAXIMG ? num_images - i0 : AG_MAXIMG;
     int max_w = 0, max_h = 0, max_n = 0;
     for (int i = 0; i < nb; ++i) {
       b.im[i].d = images[i0 + i];
       b.im[i].scratch_offset = 0;
+      if (windows) wb.w[i] = windows[i0 + i];
       if (!b.im[i].d.num_masks) continue;
       max_w = std::max(max_w, b.im[i].d.W);
       max_h = std::max(max_h, b.im[i].d.H);
@@ -400,9 +476,34 @@ extern "C" int u2_aug_rle_masks(const void* block, long long block_bytes, const 
     }
     if (!max_n) continue;
     const int col_blocks = (max_w + AG_THREADS - 1) / AG_THREADS, row_chunks = (max_h + AG_ROWS - 1) / AG_ROWS;
-    hipLaunchKernelGGL(aug_rle_masks_kernel, dim3((unsigned)(col_blocks * row_chunks), (unsigned)max_n, (unsigned)nb), dim3(AG_THREADS),
-                       0, s, b, (const uint8_t*)block, (uint8_t*)mask_out, counts, col_blocks);
+    const dim3 grid((unsigned)(col_blocks * row_chunks), (unsigned)max_n, (unsigned)nb);
+    if (windows)
+      hipLaunchKernelGGL(aug_rle_masks_boxes_kernel, grid, dim3(AG_THREADS), 0, s, b, wb, (const uint8_t*)block, (uint8_t*)mask_out,
+                         counts, boxes, col_blocks);
+    else
+      hipLaunchKernelGGL(aug_rle_masks_kernel, grid, dim3(AG_THREADS), 0, s, b, (const uint8_t*)block, (uint8_t*)mask_out, counts,
+                         col_blocks);
+    U2_CHECK_LAUNCH();
+  }
+  if (windows) {
+    hipLaunchKernelGGL(aug_boxes_kernel, dim3((unsigned)((num_counts + AG_THREADS - 1) / AG_THREADS)), dim3(AG_THREADS), 0, s, boxes,
+                       num_counts, 1);
     U2_CHECK_LAUNCH();
   }
   return 0;
+}
+
+extern "C" int u2_aug_rle_masks(const void* block, long long block_bytes, const void* tables_host, void* mask_out,
+                                long long mask_out_bytes, int* counts, int num_counts, const U2AugImage* images, int num_images,
+                                void* stream) {
+  return rle_masks_launch(block, block_bytes, tables_host, mask_out, mask_out_bytes, counts, nullptr, num_counts, images, nullptr,
+                          num_images, stream);
+}
+
+extern "C" int u2_aug_rle_masks_boxes(const void* block, long long block_bytes, const void* tables_host, void* mask_out,
+                                      long long mask_out_bytes, int* counts, int* boxes, int num_counts, const U2AugImage* images,
+                                      const U2AugWindow* windows, int num_images, void* stream) {
+  if (num_images > 0 && !windows) return -1;
+  return rle_masks_launch(block, block_bytes, tables_host, mask_out, mask_out_bytes, counts, boxes, num_counts, images, windows,
+                          num_images, stream);
 }

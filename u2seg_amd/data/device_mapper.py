@@ -4,7 +4,9 @@
 ships target-size pixels.  `DeviceMapper` loads the same files and draws the same augmentation parameters from numpy's global
 stream in the same order, but applies nothing to pixels: it returns a *raw record* - the source-size image and label map, the
 RLE masks as run ends (never decoded), the boxes (transformed on the host as before) and small per-axis tables that say, for
-every output index, which source indices feed it and with what weight.  csrc/augment.hip turns a batch of raw records into what
+every output index, which source indices feed it and with what weight.  With INPUT.CROP the record
+holds the window's pixels and tables, the run ends of the whole annotation and the window's place in it; with masks the
+boxes are then the masks' tight boxes, made on the device next to the decode.  csrc/augment.hip turns a batch of raw records into what
 `DatasetMapper` would have produced (data/build.py: DevicePrefetcher), bit for bit: everything PIL does here is integer
 arithmetic once the tables exist, and the tables are built below in float64 in PIL's own order of operations
 (src/libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc; Geometry.c: ImagingScaleAffine).
@@ -23,7 +25,7 @@ from ..structures import BitMasks, Boxes, Instances
 from . import detection_utils as utils
 from . import rle
 from . import transforms as T
-from .dataset_mapper import DatasetMapper
+from .dataset_mapper import DatasetMapper, crop_from_config
 
 PRECISION_BITS = 32 - 8 - 2  # Resample.c: coefficients carry 22 fractional bits
 RAW_KEY = "dm_meta"          # a dict with this key is a raw record
@@ -185,11 +187,13 @@ def host_labels(labels, tables):
     return np.asarray(labels)[tables["ny"][:, None], tables["nx"][None, :]].astype(np.int64)
 
 
-def host_masks(ends_per_mask, h, tables):
+def host_masks(ends_per_mask, h, tables, window=None):
     """Run ends -> (bool [N, H, W], int32 [N] pixel counts): output pixel (y, x) reads source (ny[y], nx[x]), whose column-major
-    position is p = nx[x] * h + ny[y]; its value is the parity of the number of run ends <= p."""
+    position is p = nx[x] * h + ny[y]; its value is the parity of the number of run ends <= p.  window = (x0, y0, mask_h,
+    mask_w): the tables index a window at (x0, y0) of a mask_h x mask_w code, p = (x0 + nx[x]) * mask_h + y0 + ny[y]."""
     H, W = len(tables["ny"]), len(tables["nx"])
-    p = tables["nx"].astype(np.int64)[None, :] * h + tables["ny"].astype(np.int64)[:, None]
+    x0, y0, h = (0, 0, h) if window is None else (window[0], window[1], window[2])
+    p = (x0 + tables["nx"].astype(np.int64))[None, :] * h + (y0 + tables["ny"].astype(np.int64))[:, None]
     out = np.zeros((len(ends_per_mask), H, W), dtype=bool)
     for m, ends in enumerate(ends_per_mask):
         out[m] = (np.searchsorted(np.asarray(ends, dtype=np.int64), p.reshape(-1), side="right") & 1).reshape(H, W).astype(bool)
@@ -207,17 +211,23 @@ def finish_on_host(raw):
     if "dm_sem_seg" in raw:
         out["sem_seg"] = torch.from_numpy(host_labels(raw["dm_sem_seg"].numpy(), tables))
     if meta["has_instances"]:
-        masks = counts = None
+        masks = counts = tight = None
         if meta["has_masks"]:
-            masks, counts = host_masks(ends, meta["h"], tables)
+            masks, counts = host_masks(ends, meta["h"], tables, meta.get("window"))
             masks = torch.from_numpy(masks)
-        out["instances"] = assemble_instances(meta, raw["dm_boxes"], raw["dm_classes"], masks, counts)
+            if meta.get("recompute_boxes"):
+                tight = BitMasks(masks).get_bounding_boxes().tensor
+        out["instances"] = assemble_instances(meta, raw["dm_boxes"], raw["dm_classes"], masks, counts, tight)
     return out
 
 
-def assemble_instances(meta, boxes, classes, masks, counts):
+def assemble_instances(meta, boxes, classes, masks, counts, tight=None):
     """Instances from the box-kept rows: rows whose mask has no pixel are dropped (the by_mask half of
-    filter_empty_instances).  `counts`: host int32 [N]; the tensors may live on any device."""
+    filter_empty_instances).  `counts`: host int32 [N]; the tensors may live on any device.  tight (fp32 [N, 4], records with
+    recompute_boxes): the masks' tight boxes, which replace `boxes`; there the host kept every row, a mask with a pixel has a
+    tight box of at least 1 x 1 and an empty one a zero box, so count > 0 is by_box & by_mask."""
+    if tight is not None:
+        boxes = tight
     if masks is not None and counts is not None and not bool((np.asarray(counts) > 0).all()):
         keep = torch.from_numpy(np.flatnonzero(np.asarray(counts) > 0)).to(boxes.device)
         boxes, classes, masks = boxes[keep], classes[keep], masks[keep]
@@ -230,6 +240,25 @@ def assemble_instances(meta, boxes, classes, masks, counts):
 
 
 # ---- the device side: a batch of raw records through csrc/augment.hip -----------------------------------------------------
+class _AugWindow(ctypes.Structure):
+    """Mirror of U2AugWindow (include/u2seg_hip.h)."""
+
+    _fields_ = [(k, ctypes.c_int) for k in ("x0", "y0", "mask_h", "mask_w")]
+
+
+def describe_windows(records):
+    """The windows of a batch for u2_aug_rle_masks_boxes (a record without one: the whole of its own h x w), or None when no
+    record of the batch has masks and a window (or boxes to recompute) - such a batch takes u2_aug_rle_masks."""
+    if not any((d[RAW_KEY].get("window") is not None or d[RAW_KEY].get("recompute_boxes")) and d[RAW_KEY]["num_masks"]
+               for d in records):
+        return None
+    windows = (_AugWindow * len(records))()
+    for win, d in zip(windows, records):
+        meta = d[RAW_KEY]
+        win.x0, win.y0, win.mask_h, win.mask_w = meta.get("window") or (0, 0, meta["h"], meta["w"])
+    return windows
+
+
 class _AugImage(ctypes.Structure):
     """Mirror of U2AugImage (include/u2seg_hip.h)."""
 
@@ -274,9 +303,10 @@ class PendingBatch:
     way to pinned memory.  `finish()` (after the event the launching stream recorded behind that copy) applies the by_mask
     filter and gives the list of mapped dicts."""
 
-    def __init__(self, records, block, image, labels, masks, counts_host, descs):
+    def __init__(self, records, block, image, labels, masks, counts_host, descs, boxes=None):
         self.records, self.block, self.image, self.labels, self.masks = records, block, image, labels, masks
         self.counts_host, self.descs = counts_host, descs
+        self.boxes = boxes  # int32 [masks, 4] on the device: the tight boxes (batches with a cropped record with masks), or None
 
     def outputs(self, i):
         """What the kernels wrote for record i, unfiltered: (image [3, H, W], label map [H, W] or None, masks [N, H, W], counts
@@ -294,8 +324,8 @@ class PendingBatch:
         nothing that is handed out keeps that allocation alive - unmarked, it would go back to the launching stream's pool
         and be overwritten by the next batch's kernels while the gather is still queued."""
         if stream is not None:
-            for t in (self.block, self.image, self.labels, self.masks):
-                if t.is_cuda:
+            for t in (self.block, self.image, self.labels, self.masks, self.boxes):
+                if t is not None and t.is_cuda:
                     t.record_stream(stream)
         out = []
         for a, d in zip(self.descs, self.records):
@@ -305,11 +335,13 @@ class PendingBatch:
             if a.lab_offset >= 0:
                 rec["sem_seg"] = self.labels[a.lab_out_offset:a.lab_out_offset + hw].view(a.H, a.W)
             if meta["has_instances"]:
-                masks = counts = None
+                masks = counts = tight = None
                 if meta["has_masks"]:
                     masks = self.masks[a.mask_out_offset:a.mask_out_offset + a.num_masks * hw].view(a.num_masks, a.H, a.W)
                     counts = self.counts_host[a.first_mask:a.first_mask + a.num_masks].numpy()
-                rec["instances"] = assemble_instances(meta, d["dm_boxes"], d["dm_classes"], masks, counts)
+                    if meta.get("recompute_boxes"):  # the boxes stay on the device: only the counts crossed
+                        tight = self.boxes[a.first_mask:a.first_mask + a.num_masks].to(torch.float32)
+                rec["instances"] = assemble_instances(meta, d["dm_boxes"], d["dm_classes"], masks, counts, tight)
             out.append(rec)
         return out
 
@@ -339,19 +371,27 @@ def launch_batch(records, block, host_block, counts_host=None):
     _hip.call("u2_aug_resize_bilinear_u8", block, nbytes, host_ptr, image, img_bytes, scratch, need, descs, n)
     if lab_elems:
         _hip.call("u2_aug_resize_nearest_u8", block, nbytes, host_ptr, labels, lab_elems, descs, n)
-    if masks:
+    windows, boxes = describe_windows(records), None
+    if masks and windows is None:
         _hip.call("u2_aug_rle_masks", block, nbytes, host_ptr, mask_out, mask_bytes, counts, masks, descs, n)
+    elif masks:  # a cropped record with masks: the windowed decode, and the tight boxes with it
+        boxes = torch.empty((masks, 4), dtype=torch.int32, device=dev)
+        _hip.call("u2_aug_rle_masks_boxes", block, nbytes, host_ptr, mask_out, mask_bytes, counts, boxes, masks, descs, windows, n)
     if counts_host is None or counts_host.numel() < masks:
         counts_host = torch.empty(max(masks, 1), dtype=torch.int32, pin_memory=True)
     if masks:
         counts_host[:masks].copy_(counts[:masks], non_blocking=True)
-    return PendingBatch(records, block, image, labels, mask_out, counts_host, descs)
+    return PendingBatch(records, block, image, labels, mask_out, counts_host, descs, boxes)
 
 
-def make_raw_record(passthrough, image, labels, tables, ends, boxes=None, classes=(), has_masks=False):
+def make_raw_record(passthrough, image, labels, tables, ends, boxes=None, classes=(), has_masks=False, window=None,
+                    recompute_boxes=False):
     """The raw record of one sample: `passthrough` plus the source image (HWC uint8) and label map (uint8 or None) as they
     were loaded, the tables of build_tables and the run ends of the box-kept masks in one int32 tensor, the box-kept boxes
-    (fp32 [N, 4], None: a sample without annotations) and classes, and the sizes and offsets the device side needs."""
+    (fp32 [N, 4], None: a sample without annotations) and classes, and the sizes and offsets the device side needs.
+    window = (x0, y0, mask_h, mask_w), a cropped sample: image and labels are the window's pixels, the tables those of the
+    window, the run ends still those of the whole mask_h x mask_w annotation.  recompute_boxes: nothing was dropped by its box
+    and `boxes` is replaced by the masks' tight boxes when the record is finished."""
     record = dict(passthrough)
     h, w = image.shape[:2]
     H, W = len(tables["ny"]), len(tables["nx"])
@@ -370,12 +410,16 @@ def make_raw_record(passthrough, image, labels, tables, ends, boxes=None, classe
                        "y_identity": bool(tables["y_identity"]), "row0": int(rows.min()),
                        "nrows": int(rows.max() - rows.min()), "num_masks": len(ends), "has_instances": boxes is not None,
                        "has_masks": bool(has_masks), "offsets": where}
+    if window is not None:
+        record[RAW_KEY]["window"] = tuple(int(v) for v in window)
+    if recompute_boxes and has_masks:
+        record[RAW_KEY]["recompute_boxes"] = True
     return record
 
 
 # ---- the mapper -----------------------------------------------------------------------------------------------------------
-_ACCEPTED_AUGMENTATIONS = (T.ResizeShortestEdge, T.RandomFlip)
-_ACCEPTED_TRANSFORMS = (T.ResizeTransform, T.HFlipTransform, T.VFlipTransform, T.NoOpTransform)
+_ACCEPTED_AUGMENTATIONS = (T.ResizeShortestEdge, T.RandomFlip, T.RandomCrop)
+_ACCEPTED_TRANSFORMS = (T.ResizeTransform, T.HFlipTransform, T.VFlipTransform, T.NoOpTransform, T.CropTransform)
 
 
 class DeviceMapper:
@@ -383,30 +427,36 @@ class DeviceMapper:
     gives a raw record (see the module docstring); `DevicePrefetcher` finishes it on the GPU."""
 
     def __init__(self, cfg=None, is_train=True, *, augmentations=None, image_format=None, use_instance_mask=None,
-                 instance_mask_format=None):
+                 instance_mask_format=None, recompute_boxes=None):
         if not is_train:
             raise NotImplementedError("DeviceMapper serves the training loader; the test-mode loader keeps DatasetMapper")
         if cfg is not None:
-            unsupported = cfg.INPUT.CROP.ENABLED or cfg.MODEL.KEYPOINT_ON or cfg.MODEL.LOAD_PROPOSALS
-            assert not unsupported, "crop / keypoint / precomputed-proposal inputs are not part of the U2Seg configs"
-            if augmentations is None:
-                augmentations = utils.build_augmentation(cfg, is_train)
+            unsupported = cfg.MODEL.KEYPOINT_ON or cfg.MODEL.LOAD_PROPOSALS
+            assert not unsupported, "keypoint / precomputed-proposal inputs are not part of the U2Seg configs"
+            augmentations, recompute_boxes = crop_from_config(cfg, is_train, augmentations, recompute_boxes)
             image_format = image_format or cfg.INPUT.FORMAT
             use_instance_mask = cfg.MODEL.MASK_ON if use_instance_mask is None else use_instance_mask
             instance_mask_format = instance_mask_format or cfg.INPUT.MASK_FORMAT
         self.is_train = True
         self.augmentations = list(augmentations)
-        for a in self.augmentations:
+        for i, a in enumerate(self.augmentations):
+            if i > 0 and isinstance(a, (T.RandomCrop, T.CropTransform)):
+                raise NotImplementedError("DeviceMapper cannot run %s at position %d of the augmentations (behind %s): the "
+                                          "device path crops at position 0 only, in front of the resize and of any flip"
+                                          % (type(a).__name__, i, type(self.augmentations[i - 1]).__name__))
             ok = isinstance(a, _ACCEPTED_TRANSFORMS) if isinstance(a, T.Transform) else isinstance(a, _ACCEPTED_AUGMENTATIONS)
             if not ok:
                 raise NotImplementedError("DeviceMapper cannot run %s on the device: it takes ResizeShortestEdge / RandomFlip "
-                                          "(ResizeTransform, HFlipTransform, VFlipTransform, NoOpTransform)" % type(a).__name__)
+                                          "(ResizeTransform, HFlipTransform, VFlipTransform, NoOpTransform) behind an optional "
+                                          "RandomCrop / CropTransform" % type(a).__name__)
             if isinstance(a, (T.ResizeShortestEdge, T.ResizeTransform)) and a.interp != T.Image.BILINEAR:
                 raise NotImplementedError("DeviceMapper cannot run %s with interpolation %r on the device: bilinear only"
                                           % (type(a).__name__, a.interp))
         self.image_format = image_format
         self.use_instance_mask = bool(use_instance_mask)
         self.instance_mask_format = instance_mask_format or "polygon"
+        self.recompute_boxes = bool(recompute_boxes)
+        assert self.use_instance_mask or not self.recompute_boxes, "recompute_boxes requires instance masks"
 
     def _load(self, record):
         return DatasetMapper._load(self, record)  # the same files, exif handling and size check
@@ -423,6 +473,9 @@ class DeviceMapper:
             if isinstance(t, T.ResizeTransform):
                 assert (t.h, t.w) == (h, w), ((t.h, t.w), (h, w))
                 h, w = t.new_h, t.new_w
+            elif isinstance(t, T.CropTransform):
+                assert 0 <= t.x0 and 0 <= t.y0 and t.x0 + t.w <= w and t.y0 + t.h <= h and t.w > 0 and t.h > 0, (vars(t), (h, w))
+                h, w = t.h, t.w
             tfms.append(t)
         return T.TransformList(tfms), (h, w)
 
@@ -450,8 +503,15 @@ class DeviceMapper:
         resizes = [t for t in transforms if isinstance(t, T.ResizeTransform)]
         if len(resizes) > 1:
             raise NotImplementedError("DeviceMapper: more than one ResizeTransform")
-        H, W, hflip, vflip = self._geometry(transforms, (h, w))
-        tables = build_tables(h, w, H, W, hflip, vflip)
+        window = None
+        if len(transforms) and isinstance(transforms[0], T.CropTransform):  # position 0 (the constructor): the window goes up
+            crop = transforms[0]
+            window = (crop.x0, crop.y0, h, w)
+            image = crop.apply_image(image)
+            labels = None if labels is None else crop.apply_image(labels)
+        sh, sw = image.shape[:2]
+        H, W, hflip, vflip = self._geometry(transforms, (sh, sw))
+        tables = build_tables(sh, sw, H, W, hflip, vflip)
         annotations = record.pop("annotations", None)
         ends, has_instances, has_masks = [], annotations is not None, False
         boxes, classes = np.zeros((0, 4), dtype=np.float32), []
@@ -474,6 +534,8 @@ class DeviceMapper:
                          if kept else np.zeros((0, 4)))
             box_t = torch.as_tensor(all_boxes, dtype=torch.float32).reshape(-1, 4)
             keep = Boxes(box_t).nonempty(threshold=1e-5).numpy()  # the by_box half of filter_empty_instances
+            if self.recompute_boxes and has_masks:
+                keep[:] = True  # the boxes will be those of the masks: the device says which rows have one
             boxes = box_t.numpy()[keep]
             classes = [int(a["category_id"]) for a, k in zip(kept, keep) if k]
             if has_masks:
@@ -488,4 +550,5 @@ class DeviceMapper:
                     e = run_ends(counts, h, w)
                     if k:
                         ends.append(e)
-        return make_raw_record(record, image, labels, tables, ends, boxes if has_instances else None, classes, has_masks)
+        return make_raw_record(record, image, labels, tables, ends, boxes if has_instances else None, classes, has_masks,
+                               window, self.recompute_boxes)

@@ -88,6 +88,24 @@ class ResizeTransform(Transform):
         return self.apply_image(segmentation, interp=Image.NEAREST)
 
 
+class CropTransform(Transform):
+    """fvcore's CropTransform: the window [y0, y0 + h) x [x0, x0 + w) of an image of orig_h x orig_w (kept for inspection)."""
+
+    def __init__(self, x0, y0, w, h, orig_w=None, orig_h=None):
+        self.x0, self.y0, self.w, self.h, self.orig_w, self.orig_h = x0, y0, w, h, orig_w, orig_h
+
+    def apply_image(self, img):
+        return img[self.y0:self.y0 + self.h, self.x0:self.x0 + self.w]
+
+    def apply_coords(self, coords):
+        coords[:, 0] -= self.x0
+        coords[:, 1] -= self.y0
+        return coords
+
+    def apply_polygons(self, polygons):
+        raise NotImplementedError("CropTransform does not clip polygons: INPUT.CROP trains on INPUT.MASK_FORMAT 'bitmask'")
+
+
 class TransformList(Transform):
     def __init__(self, transforms):
         flat = []
@@ -196,6 +214,46 @@ class RandomFlip(Augmentation):
         if np.random.uniform(0, 1.0) < self.prob:
             return HFlipTransform(w) if self.horizontal else VFlipTransform(h)
         return NoOpTransform()
+
+
+class RandomCrop(Augmentation):
+    """augmentation_impl.py:373-432: a window of the image at a uniformly drawn place.  crop_type / crop_size:
+    "relative" (fractions of height and width), "relative_range" (fractions drawn from [size, 1] per axis), "absolute" (pixels,
+    capped by the image), "absolute_range" (one (min, max) for both axes, capped by the image).  The draws from numpy's global
+    stream are the reference's, in its order: rand(2) for relative_range, two randint for absolute_range, then the origin's
+    randint(h - croph + 1), randint(w - cropw + 1)."""
+
+    TYPES = ("relative_range", "relative", "absolute", "absolute_range")
+
+    def __init__(self, crop_type, crop_size):
+        if crop_type not in self.TYPES:
+            raise ValueError("INPUT.CROP.TYPE '%s': one of %s" % (crop_type, ", ".join(self.TYPES)))
+        self.crop_type, self.crop_size = crop_type, crop_size
+
+    def get_transform(self, image):
+        h, w = image.shape[:2]
+        croph, cropw = self.get_crop_size((h, w))
+        assert h >= croph and w >= cropw, "Shape computation in RandomCrop(%s, %s) has bugs." % (self.crop_type, self.crop_size)
+        h0 = np.random.randint(h - croph + 1)
+        w0 = np.random.randint(w - cropw + 1)
+        return CropTransform(w0, h0, cropw, croph, w, h)
+
+    def get_crop_size(self, image_size):
+        """(height, width) of the window for an image of image_size = (height, width)."""
+        h, w = image_size
+        if self.crop_type == "relative":
+            ch, cw = self.crop_size
+            return int(h * ch + 0.5), int(w * cw + 0.5)
+        if self.crop_type == "relative_range":
+            crop_size = np.asarray(self.crop_size, dtype=np.float32)
+            ch, cw = crop_size + np.random.rand(2) * (1 - crop_size)
+            return int(h * ch + 0.5), int(w * cw + 0.5)
+        if self.crop_type == "absolute":
+            return min(self.crop_size[0], h), min(self.crop_size[1], w)
+        assert self.crop_size[0] <= self.crop_size[1]
+        ch = np.random.randint(min(h, self.crop_size[0]), min(h, self.crop_size[1]) + 1)
+        cw = np.random.randint(min(w, self.crop_size[0]), min(w, self.crop_size[1]) + 1)
+        return ch, cw
 
 
 class AugmentationList(Augmentation):

@@ -57,6 +57,20 @@ class BitMasks:
     def nonempty(self):
         return self.tensor.flatten(1).any(dim=1)
 
+    def get_bounding_boxes(self):
+        """Tight boxes [first x, first y, last x + 1, last y + 1] over the set pixels of every mask, fp32 on the masks' device;
+        a mask without a pixel gives zeros (masks.py:224-240).  Plain torch: the yardstick of u2_aug_rle_masks_boxes."""
+        from .boxes import Boxes
+
+        masks = self.tensor
+        boxes = torch.zeros(masks.shape[0], 4, dtype=torch.float32, device=masks.device)
+        x_any, y_any = torch.any(masks, dim=1), torch.any(masks, dim=2)
+        for idx in range(masks.shape[0]):
+            x, y = torch.where(x_any[idx, :])[0], torch.where(y_any[idx, :])[0]
+            if len(x) > 0 and len(y) > 0:
+                boxes[idx, :] = torch.stack([x[0], y[0], x[-1] + 1, y[-1] + 1]).to(torch.float32)
+        return Boxes(boxes)
+
     @staticmethod
     def cat(bitmasks_list):
         assert len(bitmasks_list) > 0
