@@ -10,8 +10,9 @@
 The norm's four buffers get no gradient and the shift t no bias-gradient work.
 
 Cost against the unfrozen path, not parity: a 1x1 layer there adds its weight gradient straight into the arena slot
-(u2_conv_wgrad_into); here every layer, 1x1 included, pays zeroed kernel-layout scratch, u2_conv_wgrad into it and one more
-weight-sized pass for the scaled add (52 launches, about 1.3 ms per step on the side stream for a ResNet-50)."""
+(conv_launch.wgrad_into); here every layer, 1x1 included, pays zeroed kernel-layout scratch, u2_conv_wgrad into it
+(conv_launch.wgrad_scratch) and one more weight-sized pass for the scaled add (52 launches, about 1.3 ms per step on the side
+stream for a ResNet-50)."""
 import weakref
 
 import numpy as np
@@ -19,6 +20,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _hip
+from . import conv_launch
 from .streams import _conv_variant, _run_wgrad
 from .weights import BF16, _check_act, ceil32, grad_slot, zeros_f32
 
@@ -127,24 +129,17 @@ class _FrozenConvFn(Function):
     @staticmethod
     def forward(ctx, x, weight, residual, s, t, wk, wd, stride, pad, relu, slot_box):
         _check_act(x)
-        n, cin, kh, kw = weight.shape
-        b, h, w_, cp = x.shape
-        ho = (h + 2 * pad - kh) // stride + 1
-        wo = (w_ + 2 * pad - kw) // stride + 1
-        npad = ceil32(n)
-        alloc = torch.zeros if npad != n else torch.empty
-        out = alloc((b, ho, wo, npad), dtype=BF16, device=x.device)
+        g = ctx.geom = conv_launch.ConvGeom.of(x.shape, weight.shape, stride, pad)
+        out = conv_launch.alloc_out(g, x.device)
         ctx.variant = _conv_variant()
-        _hip.call("u2_conv_igemm", x, wk, out, t, None, b, h, w_, cp, cp, ho, wo, n, npad, kh, kw, pad, pad, stride, 1,
-                  int(relu and residual is None), 0, ctx.variant)
+        conv_launch.forward(g, x, wk, out, t, None, relu and residual is None, 0, ctx.variant)
         if residual is not None:
             _check_act(residual)
             assert tuple(residual.shape) == tuple(out.shape), (tuple(residual.shape), tuple(out.shape))
-            one, zero = _unit_affine(npad, x.device)
+            one, zero = _unit_affine(g.npad, x.device)
             y, out = out, torch.empty_like(out)
-            _hip.call("u2_affine_act", y, one, zero, residual, out, 1, b * ho * wo, npad, npad, int(relu), None)
+            _hip.call("u2_affine_act", y, one, zero, residual, out, 1, g.m_out, g.npad, g.npad, int(relu), None)
         ctx.save_for_backward(x, out if relu else None)
-        ctx.geom = (b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad)
         ctx.relu = relu
         # the layouts and the scale as this pass used them (rewritten in place only after the optimizer has stepped)
         ctx.wd, ctx.s = wd, s
@@ -158,7 +153,7 @@ class _FrozenConvFn(Function):
         if g is None:
             return (None,) * 11
         x, out = ctx.saved_tensors
-        b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = ctx.geom
+        geom = ctx.geom
         need_dx, need_dw, need_dr = ctx.needs_input_grad[:3]
         g = g.contiguous()
         dz = g
@@ -168,22 +163,21 @@ class _FrozenConvFn(Function):
         dx = None
         if need_dx:
             dx = torch.empty_like(x)
-            _hip.call("u2_conv_igemm", dz, ctx.wd, dx, None, None, b, ho, wo, npad, npad, h, w_, cp, cp, kh, kw,
-                      kh - 1 - pad, kw - 1 - pad, 1, stride, 0, 0, ctx.variant)
+            conv_launch.dgrad(geom, dz, ctx.wd, dx, ctx.variant)
         dw = None
         if need_dw:
-            s, taps = ctx.s, kh * kw
+            s = ctx.s
 
             def accumulate(dst):   # dst += s * dW', dW' in the kernel's layout in scratch zeroed by the pool of the stream this runs on
-                dwk = zeros_f32((npad, taps, cp), x.device)
-                _hip.call("u2_conv_wgrad", x, dz, dwk, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride, 0)
-                _hip.call("u2_frozen_wgrad_scale_add", dwk, s, dst, n, cin, taps, cp)
+                dwk = zeros_f32((geom.npad, geom.taps, geom.cp), x.device)
+                conv_launch.wgrad_scratch(geom, x, dz, dwk)
+                _hip.call("u2_frozen_wgrad_scale_add", dwk, s, dst, geom.n, geom.cin, geom.taps, geom.cp)
 
             if ctx.slot is not None:
                 slot = ctx.slot
                 _run_wgrad(x.device, (x, dz), lambda: accumulate(slot))
             else:
-                dw = torch.zeros((n, cin, kh, kw), dtype=torch.float32, device=x.device)
+                dw = torch.zeros((geom.n, geom.cin, geom.kh, geom.kw), dtype=torch.float32, device=x.device)
                 accumulate(dw)
         return (dx, dw, dz if need_dr else None) + (None,) * 8
 

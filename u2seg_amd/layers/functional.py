@@ -12,6 +12,7 @@ This module holds the differentiable layers whose backward passes talk to each o
 norms, pooling, resampling, fan-out, ROIAlign) and is the one name the rest of the package calls the layers by: the zero pool and
 the weight layouts (weights.py), the streams (streams.py), the head losses (losses.py), the selection wrappers (select.py) and
 the FrozenBN training path (frozen.py) are imported here by name.  Functions are re-exported, mutable state never: a switch lives in exactly one module.
+A convolution's shapes and the argument lists of its launches are written once, in conv_launch.py (used here and in frozen.py, not re-exported).
 """
 import collections
 import ctypes
@@ -23,7 +24,7 @@ import torch.distributed as dist
 from torch.autograd import Function
 
 from .. import _hip
-from . import deferred, streams
+from . import conv_launch, deferred, streams
 from .frozen import affine_relu_max_pool_train, frozen_conv2d  # noqa: F401
 from .losses import (BOX_REG_LOSS_KINDS, box_reg_l1_loss, box_reg_loss, box_reg_loss_cls, count_labels_i8, mask_predict_bce_loss,  # noqa: F401
                      mask_predict_prob, rpn_losses, sem_seg_loss, sigmoid_cross_entropy, softmax_cross_entropy)
@@ -106,15 +107,11 @@ class _Conv2dFn(Function):
         # conv2d() - Function.forward runs with autograd disabled, where grad_slot() answers None)
         param = param_ref[0] if param_ref is not None else None
         wgrad_dst = param_ref[1] if param_ref is not None and len(param_ref) > 1 else None
-        n, cin, kh, kw = weight.shape
-        b, h, w_, cp = x.shape
-        assert cin <= cp
-        ho = (h + 2 * pad - kh) // stride + 1
-        wo = (w_ + 2 * pad - kw) // stride + 1
-        npad = ceil32(n)
-        wk = weight_fwd_layout(weight, cp, param)
-        alloc = torch.zeros if npad != n else torch.empty
-        out = alloc((b, ho, wo, npad), dtype=BF16, device=x.device)
+        g = conv_launch.ConvGeom.of(x.shape, weight.shape, stride, pad)
+        n = g.n
+        assert g.cin <= g.cp
+        wk = weight_fwd_layout(weight, g.cp, param)
+        out = conv_launch.alloc_out(g, x.device)
         stats = _stats_buffer(n, x.device) if want_stats else None
         # autocast casts every floating-point argument of a convolution, the bias included (pinned by the reference run under
         # bf16 autocast, tests/golden/bf16_units_golden.npz); a folded eval-mode norm shift is not a conv bias and stays fp32
@@ -122,14 +119,13 @@ class _Conv2dFn(Function):
         if bias is not None:
             bias_f = _conv_bias(bias, round_bias)
         ctx.variant = _conv_variant()
-        _hip.call("u2_conv_igemm", x, wk, out, bias_f, None if _DET_STATS else stats, b, h, w_, cp, cp, ho, wo, n, npad, kh, kw,
-                  pad, pad, stride, 1, int(relu), 0, ctx.variant)
+        conv_launch.forward(g, x, wk, out, bias_f, None if _DET_STATS else stats, relu, 0, ctx.variant)
         if want_stats and _DET_STATS:
             stats = _fixed_order_stats(out, n)
         ctx.save_for_backward(x, weight, out if relu else None)
         ctx.cfg = (stride, pad, relu, bias is not None)
         # 1x1 / linear weights: the gradient is accumulated straight into the optimizer's arena slice
-        ctx.wgrad_dst = wgrad_dst if (kh * kw == 1 and wgrad_dst is not None) else None
+        ctx.wgrad_dst = wgrad_dst if (g.taps == 1 and wgrad_dst is not None) else None
         # the arena slice in the parameter's own [N, Cin, KH, KW] shape (multi-tap filters accumulate into it with a torch add)
         # (a reshaped view of the parameter - the box head's fc1 as a 7x7 conv - gets the slice in the view's shape)
         ctx.arena = None
@@ -151,8 +147,7 @@ class _Conv2dFn(Function):
         x, weight, out = ctx.saved_tensors
         stride, pad, relu, has_bias = ctx.cfg
         need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
-        # the shapes, read once for all helpers: x [b, h, w_, cp], weight [n, cin, kh, kw], dout [b, ho, wo, npad]
-        geom = (*x.shape, *weight.shape, *dout.shape[1:], stride, pad)
+        geom = conv_launch.ConvGeom.of(x.shape, weight.shape, stride, pad)   # the shapes, derived once for all helpers
         lazy = deferred.take(deferred.BN_APPLY, dout)
         if lazy is not None:   # the gradient is still (dz, y, coefficients) of the batch normalisation behind this layer
             dx, dout = _conv_bwd_lazy_bn(ctx, geom, x, weight, *lazy)
@@ -166,91 +161,81 @@ class _Conv2dFn(Function):
         return (dx, dw, db) + (None,) * 7
 
 
-def _conv_bwd_lazy_bn(ctx, geom, x, weight, lz_dz, lz_y, lz_k):
+def _conv_bwd_lazy_bn(ctx, g, x, weight, lz_dz, lz_y, lz_k):
     """The norm behind the layer left its apply step dout = k1 dz + k2 y + k3 (lz_k rows 2-4) to this backward: (dx, None) when one
     launch formed both gradients from the operands, else (None, dout) - the step as its own launch, then the usual paths."""
-    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
-    m = b * h * w_
-    assert not ctx.cfg[2] and not ctx.cfg[3] and kh == 1 and kw == 1 and stride == 1 and pad == 0
+    m, cp, npad = g.m_in, g.cp, g.npad
+    assert not ctx.cfg[2] and not ctx.cfg[3] and g.is_1x1_unit
     wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
     dx = torch.empty_like(x)
     if ctx.wgrad_dst is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _hip.call_status(
             "u2_conv1x1_bwd_fused_bn", x, lz_dz, lz_y, lz_k[2], lz_k[3], lz_k[4], wd, dx, ctx.wgrad_dst, m, cp, cp, npad, npad,
-            npad, cp, n, cin, cin, 1, 0) == 0:
+            npad, cp, g.n, g.cin, g.cin, 1, 0) == 0:
         return dx, None
     dout = torch.empty_like(lz_y)   # not served after all
     _hip.call("u2_norm_bwd_apply", lz_dz, None, lz_y, lz_k[2], lz_k[3], lz_k[4], dout, None, 1, m, npad, npad, 0, None, None)
     return None, dout
 
 
-def _conv_bwd_relu(ctx, geom, dout, out):
+def _conv_bwd_relu(ctx, g, dout, out):
     """ReLU backward -> (dz, whether the bias gradient was added to its arena slice in the same pass over dout / out)"""
-    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
     dz = torch.empty_like(dout)
     if ctx.bias_dst is not None and ctx.needs_input_grad[2]:
-        _hip.call("u2_relu_bwd_colsum", dout, out, dz, ctx.bias_dst, zeros_f32((npad,), dout.device), b * ho * wo, npad, npad, n)
+        _hip.call("u2_relu_bwd_colsum", dout, out, dz, ctx.bias_dst, zeros_f32((g.npad,), dout.device), g.m_out, g.npad, g.npad, g.n)
         return dz, True
-    _hip.call("u2_relu_bwd", dout, out, dz, b * ho * wo * npad)
+    _hip.call("u2_relu_bwd", dout, out, dz, g.m_out * g.npad)
     return dz, False
 
 
-def _conv_bwd_data(ctx, geom, x, weight, dz):
+def _conv_bwd_data(ctx, g, x, weight, dz):
     """-> (dx, whether the launch that formed it accumulated the weight gradient as well)"""
-    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
+    cp, npad = g.cp, g.npad
     dst = ctx.wgrad_dst
-    if dst is not None and ctx.needs_input_grad[1] and kh == 1 and kw == 1 and stride == 1 and pad == 0 and n > 128 \
-            and b * h * w_ >= FUSED_BWD_MIN_PIXELS:
+    if dst is not None and ctx.needs_input_grad[1] and g.is_1x1_unit and g.n > 128 and g.m_in >= FUSED_BWD_MIN_PIXELS:
         # both gradients of an expanding 1x1 layer in one pass over dz (u2_conv1x1_bwd_fused: dz is the large operand); the
         # launcher answers 1 for a shape it does not serve
-        assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == n * cin
+        assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == g.n * g.cin
         wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
         dx = torch.empty_like(x)
-        if _hip.call_status("u2_conv1x1_bwd_fused", x, dz, wd, dx, dst, b * h * w_, cp, cp, npad, npad, npad, cp, n, cin, cin, 1,
+        if _hip.call_status("u2_conv1x1_bwd_fused", x, dz, wd, dx, dst, g.m_in, cp, cp, npad, npad, npad, cp, g.n, g.cin, g.cin, 1,
                             0) == 0:
             return dx, True
     # conv1 of a bottleneck behind an identity block: the data gradient g1 is formed, summed with the residual path's gradient,
     # masked and reduced in one launch (u2_conv_dgrad_tail); what autograd carries to the previous block's tail is a placeholder,
     # (dz, sums) wait in the tail's state
-    dx = _tail_launch(ctx, geom, dz, x, weight)
+    dx = _tail_launch(ctx, g, dz, x, weight)
     if dx is not None:
         return dx, False
     dx = torch.empty_like(x)
-    if ho == 1 and wo == 1 and pad == 0 and h == kh and w_ == kw and kh * kw > 1:
-        # "fully connected" conv (box head fc1): every input pixel meets exactly one tap, so the data gradient
-        # is the plain GEMM dx[b, (kh,kw,c)] = dz[b, :] . W[:, (kh,kw,c)]
-        wt = weight_fc_dgrad_layout(weight, cp, npad, ctx.param)
-        _hip.call("u2_conv_igemm", dz, wt, dx, None, None, 1, b, 1, npad, npad, b, 1, kh * kw * cp, kh * kw * cp,
-                  1, 1, 0, 0, 1, 1, 0, 0, ctx.variant)
+    if g.is_fc:
+        conv_launch.fc_dgrad(g, dz, weight_fc_dgrad_layout(weight, cp, npad, ctx.param), dx, ctx.variant)
     else:
-        wd = weight_dgrad_layout(weight, cp, npad, ctx.param)
-        _hip.call("u2_conv_igemm", dz, wd, dx, None, None, b, ho, wo, npad, npad, h, w_, cp, cp, kh, kw,
-                  kh - 1 - pad, kw - 1 - pad, 1, stride, 0, 0, ctx.variant)
+        conv_launch.dgrad(g, dz, weight_dgrad_layout(weight, cp, npad, ctx.param), dx, ctx.variant)
     return dx, False
 
 
-def _conv_bwd_weight(ctx, geom, x, weight, dz):
+def _conv_bwd_weight(ctx, g, x, weight, dz):
     """The weight gradient: accumulated into the optimizer's arena on the side stream (-> None), or returned for autograd."""
-    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
+    n, cin, kh, kw = g.n, g.cin, g.kh, g.kw
     dst, arena = ctx.wgrad_dst, ctx.arena
 
     def scratch():   # in the kernel's layout, zeroed by the pool of the stream this runs on
-        dwk = zeros_f32((npad, kh * kw, cp), x.device)
-        _hip.call("u2_conv_wgrad", x, dz, dwk, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride, 0)
+        dwk = zeros_f32((g.npad, g.taps, g.cp), x.device)
+        conv_launch.wgrad_scratch(g, x, dz, dwk)
         return dwk
 
     if dst is not None:
         assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == n * cin
 
         def launch():
-            _hip.call("u2_conv_wgrad_into", x, dz, dst, b, h, w_, cp, cp, ho, wo, npad, npad, kh, kw, pad, pad, stride,
-                      n, cin, cin, 1, 1, 0)
+            conv_launch.wgrad_into(g, x, dz, dst)
     elif arena is not None and streams._WGRAD_SIDE:
         # multi-tap filters: kernel-layout scratch, then accumulated into the arena slice by one transposing kernel (the strided
         # torch add took 70-170 us per 3x3 layer, 1.3 ms per step) - all of it on the side stream
         def launch():
             dwk = scratch()
-            if kh * kw * (cp + 1) * 4 <= 64 * 1024 and arena.is_contiguous():
-                _hip.call("u2_wgrad_permute_add", dwk, arena, n, cin, kh * kw, cp)
+            if g.taps * (g.cp + 1) * 4 <= 64 * 1024 and arena.is_contiguous():
+                _hip.call("u2_wgrad_permute_add", dwk, arena, n, cin, g.taps, g.cp)
             else:
                 arena.add_(dwk[:n, :, :cin].view(n, kh, kw, cin).permute(0, 3, 1, 2))
     else:
@@ -259,32 +244,31 @@ def _conv_bwd_weight(ctx, geom, x, weight, dz):
     return None
 
 
-def _conv_bwd_bias(ctx, geom, dz):
+def _conv_bwd_bias(ctx, g, dz):
     """The bias gradient: added into the bias' arena slice (-> None), or returned for autograd."""
-    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
     if ctx.bias_dst is not None:
-        _hip.call("u2_colsum_add", dz, ctx.bias_dst, b * ho * wo, npad, npad, n)
+        _hip.call("u2_colsum_add", dz, ctx.bias_dst, g.m_out, g.npad, g.npad, g.n)
         return None
-    sums = zeros_f32((1, 2, npad), dz.device)
-    _hip.call("u2_colstats", dz, sums, 1, b * ho * wo, npad, npad)
-    return sums[0, 0, :n]
+    sums = zeros_f32((1, 2, g.npad), dz.device)
+    _hip.call("u2_colstats", dz, sums, 1, g.m_out, g.npad, g.npad)
+    return sums[0, 0, :g.n]
 
 
-def _tail_launch(ctx, geom, dz, x, weight):
+def _tail_launch(ctx, g, dz, x, weight):
     """_conv_bwd_data: launch the fused data gradient + tail reduce if this layer was marked for it in the forward pass, the
     other consumer's gradient has been posted and the kernel serves the shape; returns the placeholder autograd carries instead of
     dx.  None: the caller takes the two launches."""
     tail = ctx.tail
     if tail is None or not TAIL_BWD_FUSE or tail.g2 is None or tail.result is not None:
         return None
-    b, h, w_, cp, n, cin, kh, kw, ho, wo, npad, stride, pad = geom
-    if ctx.cfg[2] or kh != 1 or kw != 1 or stride != 1 or pad != 0 or tuple(tail.g2.shape) != tuple(x.shape) \
-            or tuple(tail.y.shape) != tuple(x.shape) or not tail.g2.is_contiguous() or npad != n:
+    n, cp = g.n, g.cp
+    if ctx.cfg[2] or not g.is_1x1_unit or tuple(tail.g2.shape) != tuple(x.shape) \
+            or tuple(tail.y.shape) != tuple(x.shape) or not tail.g2.is_contiguous() or g.npad != n:
         return None
     wd = weight_dgrad_layout(weight, cp, n, ctx.param)
     dzt = torch.empty_like(tail.y)
     sums = zeros_f32((2, cp), x.device)
-    if _hip.call_status("u2_conv_dgrad_tail", dz, wd, tail.g2, tail.y, tail.bits, tail.mean, tail.invstd, dzt, sums, b, h, w_, n, n,
+    if _hip.call_status("u2_conv_dgrad_tail", dz, wd, tail.g2, tail.y, tail.bits, tail.mean, tail.invstd, dzt, sums, g.b, g.h, g.w, n, n,
                         cp, cp, ctx.variant) != 0:
         return None   # declined (shape, fill rule, switched off by the variant bits): nothing was written
     ph = deferred.post(deferred.TAIL, x.device, x.shape, tail)
@@ -321,16 +305,11 @@ def conv2d_add_(x, weight, bias, out, stride=1, pad=0, relu=False, param=None):
     assert not torch.is_grad_enabled()
     _check_act(x)
     _check_act(out)
-    n, cin, kh, kw = weight.shape
-    b, h, w_, cp = x.shape
-    ho = (h + 2 * pad - kh) // stride + 1
-    wo = (w_ + 2 * pad - kw) // stride + 1
-    npad = ceil32(n)
-    assert tuple(out.shape) == (b, ho, wo, npad) and npad == n, "the accumulating epilogue has no padded output channels"
-    wk = weight_fwd_layout(weight, cp, param)
+    g = conv_launch.ConvGeom.of(x.shape, weight.shape, stride, pad)
+    assert tuple(out.shape) == (g.b, g.ho, g.wo, g.npad) and g.npad == g.n, "the accumulating epilogue has no padded output channels"
+    wk = weight_fwd_layout(weight, g.cp, param)
     bias_f = bias.detach().float().contiguous() if bias is not None else None
-    _hip.call("u2_conv_igemm", x, wk, out, bias_f, None, b, h, w_, cp, cp, ho, wo, n, npad, kh, kw, pad, pad, stride, 1, int(relu),
-              1, _conv_variant())
+    conv_launch.forward(g, x, wk, out, bias_f, None, relu, 1, _conv_variant())
     return out
 
 
@@ -382,6 +361,7 @@ class _StemConvFn(Function):
         ctx.direct = None
         col = torch.empty((m, kp), dtype=BF16, device=weight.device)
         _hip.call("u2_stem_im2col_batch", ptrs, hs, ws, b, int(is_u8), pixel_mean, pixel_std, col, hpad, wpad, kp)
+        # (a GEMM over col, here and in backward; no ConvGeom: out and dwk have n rows / columns as they are, not ceil32(n))
         _hip.call("u2_conv_igemm", col, wk, out, None, None if _DET_STATS else stats, 1, m, 1, kp, kp, m, 1, n, n, 1, 1, 0, 0, 1,
                   1, 0, 0, 0)
         if _DET_STATS:
