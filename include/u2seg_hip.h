@@ -198,6 +198,27 @@ int u2_conv_last_kernel(void);
  * allocator, where torch.cuda.empty_cache() releases them - this is the equivalent for a plain C ABI. */
 int u2_release_scratch(void);
 
+/* ---- grouped 3x3 convolution (conv_grouped.hip) -------------------------------------------------
+ * F.conv2d(groups = G) behind layers/wrappers.py:127-134 for conv2 of a ResNeXt bottleneck (backbone/resnet.py:155-166), its
+ * data gradient and its weight gradient.  Activations NHWC bf16 with C == N physical channels, C % 32 == 0, cg = C / groups;
+ * filter 3x3, pad 1, stride 1 or 2, Hout = (H + 2 - 3) / stride + 1.  All three read the fp32 parameter in the reference's own
+ * layout w[N][cg][3][3]; no bf16 layout exists outside the launch:
+ *   W'[n][c][t] = bf16(w[n][c][t] * (scale ? scale[n] : 1.0f))                 one fp32 multiply, one rounding (the FrozenBN fold)
+ *   fwd:   out[b,ho,wo,n] = bf16(relu?(sum_{t, c in group(n)} in[...][c] W'[n][c - c0][t] + bias[n])), fp32 sum and bias add;
+ *          stats ([2][N] fp32, zeroed by the caller): column sum and sum of squares of the STORED values, fp32 atomics
+ *   dgrad: dx[b,h,w,c] = bf16(sum_{t, n in group(c)} dz[b,(h+1-kh)/s,(w+1-kw)/s,n] W'[n][c - c0][t]) over the taps whose source
+ *          coordinate is integral and inside the map; every element of dx is written.  H, W: the INPUT map (dx)
+ *   wgrad: dw[n][c][kh][kw] += (scale ? scale[n] : 1) * sum_{b,ho,wo} dz[b,ho,wo,n] x[b,ho*s+kh-1,wo*s+kw-1,c0+c], fp32 atomics
+ *          into the caller's [N][cg][3][3] buffer (the arena slot or a zeroed tensor)
+ * Served: groups >= 2, C = groups * cg, cg in {4, 8, 16, 32, 64}.  Returns 0 when launched, 1 when the shape is not served
+ * (nothing is written). */
+int u2_gconv3x3_fwd(const void* in, const float* w, const float* scale, const float* bias, void* out, float* stats, int B, int H,
+                    int W, int C, int groups, int stride, int relu, void* stream);
+int u2_gconv3x3_dgrad(const void* dz, const float* w, const float* scale, void* dx, int B, int H, int W, int C, int groups,
+                      int stride, void* stream);
+int u2_gconv3x3_wgrad(const void* x, const void* dz, const float* scale, float* dw, int B, int H, int W, int C, int groups,
+                      int stride, void* stream);
+
 /* fp32 master weights [N][Cin][T] -> bf16 kernel layouts: mode 0 [N][T][Cp] (forward / wgrad), mode 1 [Cp][T][Npad] with the
  * taps reversed (data gradient), mode 2 [T][Cp][Npad] (data gradient of a fully connected conv). Zero padded. */
 int u2_weight_layout(const float* w, void* out, int N, int Cin, int T, int Cp, int Npad, int mode, void* stream);

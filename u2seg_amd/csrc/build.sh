@@ -8,7 +8,7 @@ OBJS=""
 PIDS=""
 # every header counts for every source: the newest of csrc/*.h and the public header decides
 NEWEST_H=$(ls -t *.h ../../include/u2seg_hip.h | head -1)
-for f in conv_api conv_igemm conv_wgrad conv_scratch conv_tile conv_halo conv_stream wgrad_halo wgrad_stream norm pool_resize stem_conv losses roi select optim kmeans knn usl postprocess maskeval polygon panopticeval cocoeval semeval augment vit labelprep tta frozen; do
+for f in conv_api conv_igemm conv_wgrad conv_scratch conv_tile conv_halo conv_stream conv_grouped wgrad_halo wgrad_stream norm pool_resize stem_conv losses roi select optim kmeans knn usl postprocess maskeval polygon panopticeval cocoeval semeval augment vit labelprep tta frozen; do
   if [ -n "$U2_FORCE" ] || [ ! -f $f.o ] || [ $f.hip -nt $f.o ] || [ $NEWEST_H -nt $f.o ]; then
     # compile to a temporary name so that a failed compile can never leave a stale object behind a "successful" link
     ( $HIPCC $FLAGS "$@" -c $f.hip -o $f.o.tmp && mv $f.o.tmp $f.o ) &

@@ -58,3 +58,38 @@ def wgrad_into(g, x, dz, dst):
     """A 1x1 layer's gradient added straight into its [n, cin] parameter gradient."""
     _hip.call("u2_conv_wgrad_into", x, dz, dst, g.b, g.h, g.w, g.cp, g.cp, g.ho, g.wo, g.npad, g.npad, g.kh, g.kw, g.pad, g.pad,
               g.stride, g.n, g.cin, g.cin, 1, 1, 0)
+
+
+class GroupedGeom(collections.namedtuple("GroupedGeom", "b h w c groups stride ho wo")):
+    """A grouped 3x3 / pad-1 convolution (u2_gconv3x3_*): x [b, h, w, c], weight [c, c // groups, 3, 3], output [b, ho, wo, c]."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, x_shape, weight_shape, groups, stride, pad):
+        b, h, w, c = x_shape
+        n, cg, kh, kw = weight_shape
+        assert (kh, kw, pad) == (3, 3, 1) and stride in (1, 2), "a grouped convolution is 3x3, pad 1, stride 1 or 2"
+        assert n == c and groups >= 2 and cg * groups == c, ("grouped conv: channels", c, n, cg, groups)
+        return cls(b, h, w, c, groups, stride, (h + 2 - 3) // stride + 1, (w + 2 - 3) // stride + 1)
+
+    m_out = property(lambda g: g.b * g.ho * g.wo)
+    cg = property(lambda g: g.c // g.groups)
+
+
+def grouped_served(channels, groups):
+    """Whether the u2_gconv3x3_* kernels serve a layer of `channels` in `groups` (include/u2seg_hip.h)."""
+    return groups >= 2 and channels % groups == 0 and channels % 32 == 0 and channels // groups in (4, 8, 16, 32, 64)
+
+
+def grouped_forward(g, x, w, scale, bias, out, stats, relu):
+    """`w`: the fp32 parameter [c, cg, 3, 3] itself; scale / bias / stats: fp32 [c] / [c] / [2, c] or None."""
+    _hip.call("u2_gconv3x3_fwd", x, w, scale, bias, out, stats, g.b, g.h, g.w, g.c, g.groups, g.stride, int(relu))
+
+
+def grouped_dgrad(g, dz, w, scale, dx):
+    _hip.call("u2_gconv3x3_dgrad", dz, w, scale, dx, g.b, g.h, g.w, g.c, g.groups, g.stride)
+
+
+def grouped_wgrad(g, x, dz, scale, dw):
+    """Accumulates into dw, fp32 [c, cg, 3, 3]."""
+    _hip.call("u2_gconv3x3_wgrad", x, dz, scale, dw, g.b, g.h, g.w, g.c, g.groups, g.stride)

@@ -186,6 +186,14 @@ def frozen_conv2d(conv, x, residual=None, relu=False):
     """conv (a layers.modules.Conv2d whose norm is a FrozenBatchNorm2d) on x, under autograd."""
     stride, pad = conv.stride, conv.padding
     assert isinstance(stride, int) and isinstance(pad, int)
+    if conv.groups != 1:
+        # a grouped 3x3 layer: the u2_gconv3x3_* kernels apply s themselves (W' = bf16(w * s) as they stage it, dw = s * dW' as
+        # they add it): no entry in the fold table, no scaled-add pass
+        from .functional import grouped_conv2d   # (functional imports this module by name: the import cannot stand at the top)
+
+        assert residual is None, "a grouped layer takes no residual"
+        s, t = scale_shift(conv.norm)
+        return grouped_conv2d(x, conv.weight, t, conv.groups, stride, pad, relu=bool(relu), scale=s, round_bias=False)[0]
     wk, wd, s, t = folded_layouts(conv, x.shape[3])
     return _FrozenConvFn.apply(x, conv.weight, residual, s, t, wk, wd, stride, pad, bool(relu), (grad_slot(conv.weight),))
 

@@ -276,9 +276,82 @@ def _tail_launch(ctx, g, dz, x, weight):
     return ph
 
 
-def conv2d(x, weight, bias=None, stride=1, pad=0, relu=False, want_stats=False, param=None, round_bias=True):
+class _GroupedConv2dFn(Function):
+    """F.conv2d(groups = G) of a 3x3 / pad-1 layer (+bias)(+ReLU)(+statistics), conv2 of a ResNeXt bottleneck
+    (backbone/resnet.py:155-166), on the u2_gconv3x3_* kernels.  They read the fp32 parameter itself and round it while they
+    stage it: no kernel layout is looked up, cached or rewritten on this path.  `scale` (fp32 [C], no gradient): the kernels
+    compute with W' = bf16(w * scale[n]) and return dw = scale[n] * dW' - the FrozenBN fold (layers/frozen.py) without its table."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, scale, groups, stride, pad, relu, want_stats, slot_box, round_bias):
+        _check_act(x)
+        g = ctx.geom = conv_launch.GroupedGeom.of(x.shape, weight.shape, groups, stride, pad)
+        assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.device == x.device
+        w = weight.detach()
+        out = torch.empty((g.b, g.ho, g.wo, g.c), dtype=BF16, device=x.device)
+        stats = _stats_buffer(g.c, x.device) if want_stats else None
+        bias_f = _conv_bias(bias, round_bias) if bias is not None else None
+        conv_launch.grouped_forward(g, x, w, scale, bias_f, out, None if _DET_STATS else stats, relu)
+        if want_stats and _DET_STATS:
+            stats = _fixed_order_stats(out, g.c)
+        ctx.save_for_backward(x, weight, out if relu else None, scale)
+        ctx.relu = relu
+        slot = slot_box[0] if slot_box is not None else None
+        ok = slot is not None and slot.is_contiguous() and slot.dtype == torch.float32 and tuple(slot.shape) == tuple(weight.shape)
+        ctx.slot = slot if ok else None
+        ctx.set_materialize_grads(False)
+        if want_stats:
+            ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, dout, _dstats):
+        if dout is None:
+            return (None,) * 11
+        x, weight, out, scale = ctx.saved_tensors
+        g = ctx.geom
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        # neither deferred-gradient protocol (layers/deferred.py) reaches a 3x3 layer: BN_APPLY is posted to expanding 1x1 layers,
+        # TAIL by a 1x1 conv1 - a placeholder arriving here would be a gradient silently dropped
+        assert not deferred.holds(deferred.BN_APPLY, dout) and not deferred.holds(deferred.TAIL, dout), \
+            "a deferred gradient reached a grouped 3x3 layer"
+        dz = dout.contiguous()
+        if ctx.relu:
+            dz = torch.empty_like(dz)
+            _hip.call("u2_relu_bwd", dout.contiguous(), out, dz, dz.numel())
+        dx = None
+        if need_dx:
+            dx = torch.empty_like(x)
+            conv_launch.grouped_dgrad(g, dz, weight.detach(), scale, dx)
+        dw = None
+        if need_dw:
+            if ctx.slot is not None:
+                slot = ctx.slot
+                _run_wgrad(x.device, (x, dz), lambda: conv_launch.grouped_wgrad(g, x, dz, scale, slot))
+            else:
+                dw = torch.zeros(weight.shape, dtype=torch.float32, device=x.device)
+                conv_launch.grouped_wgrad(g, x, dz, scale, dw)
+        db = None
+        if need_db:
+            sums = zeros_f32((1, 2, g.c), dz.device)
+            _hip.call("u2_colstats", dz, sums, 1, g.m_out, g.c, g.c)
+            db = sums[0, 0]
+        return (dx, dw, db) + (None,) * 8
+
+
+def grouped_conv2d(x, weight, bias, groups, stride, pad, relu=False, want_stats=False, scale=None, round_bias=True):
+    """-> (out, stats or None).  `weight`: the fp32 [C, C // groups, 3, 3] tensor the kernels read (a Parameter, or a folded copy)."""
+    slot = grad_slot(weight) if isinstance(weight, torch.nn.Parameter) else None
+    return _GroupedConv2dFn.apply(x, weight, bias, scale, groups, stride, pad, relu, want_stats, (slot,), round_bias)
+
+
+def conv2d(x, weight, bias=None, stride=1, pad=0, relu=False, want_stats=False, param=None, round_bias=True, groups=1):
     """`param`: the nn.Parameter that owns `weight`'s memory when `weight` is a reshaped view of it (defaults to `weight`
-    itself when that is a Parameter); it carries the optimizer's gradient slot and the cached kernel layouts."""
+    itself when that is a Parameter); it carries the optimizer's gradient slot and the cached kernel layouts.
+    groups > 1: a grouped 3x3 layer (_GroupedConv2dFn); `param` plays no part there, the kernels read `weight` as it stands."""
+    if groups != 1:
+        out, stats = grouped_conv2d(x, weight, bias, groups, stride, pad, relu, want_stats, None, round_bias)
+        return (out, stats) if want_stats else out
     if param is None and isinstance(weight, torch.nn.Parameter):
         param = weight
     slot = grad_slot(param) if param is not None else None

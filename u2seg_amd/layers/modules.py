@@ -157,12 +157,15 @@ class Conv2d(nn.Module):
     the batch statistics, one elementwise pass applies normalisation (+ residual) (+ ReLU)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, norm=None,
-                 activation=None):
+                 activation=None, groups=1):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size = (kernel_size, kernel_size) if isinstance(kernel_size, int) else tuple(kernel_size)
         self.stride, self.padding = stride, padding
-        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, *self.kernel_size))
+        # groups > 1: a grouped 3x3 layer on the u2_gconv3x3_* kernels (ResNeXt's conv2); the weight has torch's grouped shape
+        assert groups >= 1 and in_channels % groups == 0 and out_channels % groups == 0, (in_channels, out_channels, groups)
+        self.groups = groups
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels // groups, *self.kernel_size))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
         self.norm = norm
@@ -177,12 +180,14 @@ class Conv2d(nn.Module):
             return F.fpn_upsample_add(self.forward(x, None, relu, twin), residual_up)
         relu = (self.activation == "relu") if relu is None else relu
         norm = self.norm
+        groups = self.groups
+        assert groups == 1 or (residual is None and residual_up is None), "a grouped layer takes no residual"
         if norm is None:
             assert residual is None
-            return F.conv2d(x, self.weight, self.bias, self.stride, self.padding, relu=relu)
+            return F.conv2d(x, self.weight, self.bias, self.stride, self.padding, relu=relu, groups=groups)
         assert self.bias is None, "a conv followed by a norm layer carries no bias in this graph"
         if isinstance(norm, BatchNorm2d) and self.training:
-            y, stats = F.conv2d(x, self.weight, None, self.stride, self.padding, relu=False, want_stats=True)
+            y, stats = F.conv2d(x, self.weight, None, self.stride, self.padding, relu=False, want_stats=True, groups=groups)
             norm.count_batch()
             if residual_up is not None:
                 assert residual is None
@@ -192,7 +197,7 @@ class Conv2d(nn.Module):
                                     relu, norm.momentum, norm.eps, twin=twin, sync=norm.sync)
         if isinstance(norm, GroupNorm):
             assert residual is None
-            y = F.conv2d(x, self.weight, None, self.stride, self.padding, relu=False)
+            y = F.conv2d(x, self.weight, None, self.stride, self.padding, relu=False, groups=groups)
             return F.group_norm_act(y, norm.weight, norm.bias, norm.num_groups, relu, norm.eps)
         if isinstance(norm, FrozenBatchNorm2d) and torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad):
             # FrozenBN on the training path: the arithmetic of the folded inference path below, under autograd (layers/frozen.py)
@@ -203,12 +208,13 @@ class Conv2d(nn.Module):
             if residual is None:
                 # folded into the conv: weights scaled per output channel, shift as the bias, ReLU in the epilogue - no
                 # elementwise pass at all (the conv kernels add a bias and clamp before the one bf16 rounding)
-                return F.conv2d(x, folded[0], folded[1], self.stride, self.padding, relu=relu, param=folded[0], round_bias=False)
+                return F.conv2d(x, folded[0], folded[1], self.stride, self.padding, relu=relu, param=folded[0], round_bias=False,
+                                groups=groups)
             if residual_owned and self.out_channels % 32 == 0 and os.environ.get("U2_EVAL_RESIDUAL_FUSE", "1") != "0":
                 return F.conv2d_add_(x, folded[0], folded[1], residual, self.stride, self.padding, relu=relu, param=folded[0])
             y = F.conv2d(x, self.weight, None, self.stride, self.padding, relu=False)
             return F.affine_act(y, folded[2], folded[3], residual, relu)
-        y = F.conv2d(x, self.weight, None, self.stride, self.padding, relu=False)
+        y = F.conv2d(x, self.weight, None, self.stride, self.padding, relu=False, groups=groups)
         scale, shift = norm.eval_scale_shift()
         return F.affine_act(y, scale.float(), shift.float(), residual, relu)
 

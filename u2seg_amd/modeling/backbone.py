@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from ..layers import Conv2d, ShapeSpec, c2_msra_fill, c2_xavier_fill, get_norm
+from ..layers.conv_launch import grouped_served
 from ..layers.modules import FrozenBatchNorm2d
 from ..layers import functional as F
 from ..utils.registry import Registry
@@ -87,7 +88,10 @@ class BottleneckBlock(nn.Module):
     def __init__(self, in_channels, out_channels, *, bottleneck_channels, stride=1, num_groups=1, norm="BN",
                  stride_in_1x1=False, dilation=1):
         super().__init__()
-        assert num_groups == 1 and dilation == 1, "grouped / dilated bottlenecks are not used by the U2Seg configs"
+        # num_groups > 1 (ResNeXt): conv2 is a grouped 3x3 layer on the u2_gconv3x3_* kernels.  Dilation
+        # stays refused: the FPN takes contiguous strides only, and this project has FPN models only
+        assert dilation == 1, "dilated bottlenecks (MODEL.RESNETS.RES5_DILATION) are not built: the FPN needs contiguous strides"
+        assert num_groups >= 1 and bottleneck_channels % num_groups == 0, (bottleneck_channels, num_groups)
         self.in_channels, self.out_channels, self.stride = in_channels, out_channels, stride
         self.frozen = False
         self.third_handle = False  # set by ResNet on the last block of a stage that is also a backbone output
@@ -101,7 +105,7 @@ class BottleneckBlock(nn.Module):
         self.conv1 = Conv2d(in_channels, bottleneck_channels, kernel_size=1, stride=stride_1x1, bias=False,
                             norm=get_norm(norm, bottleneck_channels), activation="relu")
         self.conv2 = Conv2d(bottleneck_channels, bottleneck_channels, kernel_size=3, stride=stride_3x3, padding=1,
-                            bias=False, norm=get_norm(norm, bottleneck_channels), activation="relu")
+                            bias=False, norm=get_norm(norm, bottleneck_channels), activation="relu", groups=num_groups)
         self.conv3 = Conv2d(bottleneck_channels, out_channels, kernel_size=1, bias=False,
                             norm=get_norm(norm, out_channels))
         for layer in [self.conv1, self.conv2, self.conv3, self.shortcut]:
@@ -206,10 +210,18 @@ def build_resnet_backbone(cfg, input_shape):
     blocks_per_stage = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}[depth]
     bottleneck_channels = r.NUM_GROUPS * r.WIDTH_PER_GROUP
     in_channels, out_channels = r.STEM_OUT_CHANNELS, r.RES2_OUT_CHANNELS
-    assert r.RES5_DILATION == 1 and not any(r.DEFORM_ON_PER_STAGE)
+    if r.RES5_DILATION != 1:
+        raise ValueError("MODEL.RESNETS.RES5_DILATION %r: dilated stages are not built (the FPN needs contiguous strides)"
+                         % (r.RES5_DILATION,))
+    assert not any(r.DEFORM_ON_PER_STAGE)
     stages = []
     for idx in range(4):
         first_stride = 1 if idx == 0 else 2
+        if r.NUM_GROUPS != 1 and not grouped_served(bottleneck_channels, r.NUM_GROUPS):
+            raise ValueError(
+                "MODEL.RESNETS.NUM_GROUPS %d x WIDTH_PER_GROUP %d: res%d's 3x3 layer would have %d channels in %d groups; the "
+                "grouped kernels serve 4, 8, 16, 32 or 64 channels per group at a width that is a multiple of 32"
+                % (r.NUM_GROUPS, r.WIDTH_PER_GROUP, idx + 2, bottleneck_channels, r.NUM_GROUPS))
         stages.append(ResNet.make_stage(
             BottleneckBlock, blocks_per_stage[idx], in_channels=in_channels, out_channels=out_channels,
             stride_per_block=[first_stride] + [1] * (blocks_per_stage[idx] - 1),
